@@ -13,8 +13,17 @@ parameters, CMB+FIR+NIR seed fields, 64 photon energies, 512 walkers per GPU
 (weak scaling, the default: every rank adds its own 512 walkers to the ensemble;
 ``--scaling strong`` keeps the ensemble fixed and splits it).  Synthetic spectrum (seed
 20260929), inputs resident in HBM before the timed region.  The timed region is EXACTLY
-K steps between barriers; it is repeated until >= 0.5 s have been timed and ``value`` is
-the median region (min / max / first in ``timing``).
+K steps between barriers, timed once: ``ms_per_step`` is its time over K.  ``--min-time S``
+repeats it until >= S seconds have been timed, and ``value`` is then the median region
+(min / max / first in ``timing``).  A region of a few ms still sees the device clocks ramp
+(the first of many regions runs a few % slower than their median): to measure, choose K
+from ``ms_per_step`` so that the region lasts a good fraction of a second.
+
+``--dump-outputs DIR`` writes what the timed path returned after its last step, as float64
+``.npy`` files: ``coords`` [walkers, ndim], ``log_prob`` [walkers] and ``blob<j>`` (the
+model's blobs, in the order the model returns them, [walkers, ...]).  Above 64 MB in all, a
+fixed seeded sample of walkers is written, their indices in ``walker_index``.  The untimed
+spin-up is then a fixed number of steps, so the same arguments give the same outputs.
 
 Prints ONE JSON line on rank 0 with the contract keys plus
   "roofline"      the dominant kernel, from HIP events recorded around every launch
@@ -67,6 +76,7 @@ KERNEL_SYMBOL = {"half_step": "k_half_step", "integrate_tables": "k_integrate_ta
                  "particle_weights": "k_step_front (proposal+packs+weights+We)", "lnprob": "k_lnprobmodel",
                  "integrate_rows": "k_integrate_rows", "ic_seed_walkers": "k_ic_seed_walkers",
                  "tables": "k_table_*", "glue": "k_pack_rows/k_move_*"}
+DUMP_LIMIT_BYTES = 64 * 1000 ** 2  # --dump-outputs: at most this much in all
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP64_VEC_PEAK_TF = 78.6    # vendor figure quoted in SURVEY.md 8d (256 CU x 128 flop/clk x 2.4 GHz)
 
@@ -464,6 +474,24 @@ def exchange_info(sampler, comm, shared_note, ctx=None):
     return out
 
 
+def dump_outputs(path, outputs, steps_made):
+    """--dump-outputs: ``outputs`` (name -> float64 array, walkers on the first axis) as
+    ``path/<name>.npy``; above DUMP_LIMIT_BYTES the same seeded sample of walkers from every
+    array (their indices in walker_index.npy) -> the line's summary"""
+    os.makedirs(path, exist_ok=True)
+    nwalkers = len(outputs["coords"])
+    per_walker = sum(a.nbytes for a in outputs.values()) // nwalkers
+    if per_walker * nwalkers > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - 4096) // (per_walker + 8)  # (+ its index, - the .npy headers)
+        idx = np.sort(np.random.default_rng(20260929).choice(nwalkers, keep, replace=False))
+        outputs = {k: a[idx] for k, a in outputs.items()}
+        outputs["walker_index"] = idx.astype(np.float64)
+    for k, a in outputs.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return {"dir": path, "walkers_total": nwalkers, "sampled": "walker_index" in outputs,
+            "steps_made": steps_made, "arrays": {k: list(a.shape) for k, a in outputs.items()}}
+
+
 def measure(args, ctx, comm, name, scaling, walkers, walkers_total, full):
     """one workload on the ranks of ``comm``: the timed K-step regions (``full``: plus the other
     blob setting, per-kernel HIP events, roofline, CPU baseline) -> the line's dict on rank 0,
@@ -522,13 +550,15 @@ def measure(args, ctx, comm, name, scaling, walkers, walkers_total, full):
     # multi-step graph).  A short --warmup is topped up to 160 steps (at most 0.5 s of them,
     # judged by eight steps timed after the warm-up -- the warm-up itself contains one-off
     # set-up); every rank takes the same number so the collectives stay matched.
+    # (--dump-outputs: no time cap, so that the dumped state does not depend on a clock)
     spinup = 0
     if device:
         tw = time.perf_counter()
         state = sampler.run_mcmc(state, 8, store=False)
         ctx.sync()
         per_step = comm.max((time.perf_counter() - tw) / 8)
-        spinup = 8 + int(min(max(0, 152 - args.warmup), 0.5 / max(per_step, 1e-6)))
+        cap = float("inf") if args.dump_outputs else 0.5 / max(per_step, 1e-6)
+        spinup = 8 + int(min(max(0, 152 - args.warmup), cap))
         spinup = int(comm.max(spinup))
         if spinup > 8:
             state = sampler.run_mcmc(state, spinup - 8, store=False)
@@ -588,6 +618,14 @@ def measure(args, ctx, comm, name, scaling, walkers, walkers_total, full):
     dt = float(np.median(times))
     region_overheads, region_spans = list(overheads), list(spans_seen)
     final_coords = np.asarray(state.coords)
+    # what the timed path returned after its last step, read before anything below moves the
+    # ensemble on (every rank reads: the blobs of a shared ensemble are gathered collectively)
+    outputs, steps_at_dump = None, int(sampler.steps_total)
+    if args.dump_outputs and full:
+        outputs = {"coords": np.array(final_coords, dtype=np.float64),
+                   "log_prob": np.array(state.log_prob, dtype=np.float64)}
+        for j, b in enumerate(state.blobs or []):
+            outputs["blob%d" % j] = np.array(b, dtype=np.float64)
 
     # ---- the same loop with the other blob setting (the reference always stores (flux, We)
     # per walker and step, core.py:450-457, and so does the timed loop above unless
@@ -597,7 +635,9 @@ def measure(args, ctx, comm, name, scaling, walkers, walkers_total, full):
         bs = make_sampler(device, not args.no_graph, blobs=not keep_blobs)
         bst = bs.run_mcmc(final_coords, 6, store=False)
         bt = []
-        for _ in range(int(min(40, max(1, np.ceil(args.min_time / 2 / max(dt, 1e-6)))))):
+        # (a fresh sampler whose first region captures its graphs: a median over >= 0.25 s)
+        blobs_time = max(args.min_time, 0.5) / 2
+        for _ in range(int(min(40, max(1, np.ceil(blobs_time / max(dt, 1e-6)))))):
             dt_i, bst = timed_region(bs, bst)
             bt.append(dt_i)
             bs.reset()
@@ -723,6 +763,8 @@ def measure(args, ctx, comm, name, scaling, walkers, walkers_total, full):
                    "construction"}
     else:
         out["region_overhead_us"] = None  # (a loop whose launches carry no span stamps: host loop)
+    if outputs is not None:
+        out["dump_outputs"] = dump_outputs(args.dump_outputs, outputs, steps_at_dump)
     if not prof:
         return out
     # dominant kernel by accumulated HIP-event time (one category = one kernel symbol;
@@ -857,8 +899,12 @@ def main():
                          "and the main line is the default weak cfg3")
     ap.add_argument("--ball", type=float, default=0.1,
                     help="relative spread of the initial ensemble around p0 (naima: 10 %%, core.py:477-481)")
-    ap.add_argument("--min-time", type=float, default=0.5,
-                    help="repeat the K-step timed region until this many seconds have been timed")
+    ap.add_argument("--min-time", type=float, default=0.0,
+                    help="repeat the K-step timed region until this many seconds have been timed "
+                         "(default 0: one region, exactly --steps timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned after its last "
+                         "step (coords, log_prob, blobs) as DIR/<name>.npy, float64, <= 64 MB")
     ap.add_argument("--no-blobs", action="store_true",
                     help="the timed loop does not keep the blobs (emcee and the reference always do: "
                          "(flux, We) per walker and step, core.py:450-457)")

@@ -61,6 +61,39 @@ def test_one_gpu_line_has_the_contract_keys():
     assert abs(d["value"] - 512 * 20 / (d["ms_per_step"] * 20e-3)) < 1e-6 * d["value"]
 
 
+def test_dump_outputs_are_the_timed_path_s_last_step(tmp_path):
+    """--dump-outputs: one region of exactly --steps timed steps, and the arrays are what the timed
+    path returned after its last one -- every sampled walker's log-probability, model spectrum
+    and We are the oracle's at its dumped coordinates.  A second run with the same arguments
+    dumps the same arrays, bit for bit"""
+    import numpy as np
+    from numpy.testing import assert_allclose
+
+    import naima_amd as na
+    from bench import build_problem
+    from oracle import workloads_np as WN
+    argv = ["--steps", "20", "--warmup", "5", "--no-cpu", "--no-blobs-run"]
+    d = _line(_bench(argv + ["--dump-outputs", str(tmp_path / "a")]))
+    assert d["steps"] == 20 and d["timing"]["regions"] == 1
+    x = d["dump_outputs"]
+    assert not x["sampled"] and x["walkers_total"] == 512
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in ("coords", "log_prob", "blob0", "blob1")}
+    assert {k: list(v.shape) for k, v in got.items()} == x["arrays"]
+    assert got["coords"].shape == (512, 5) and got["blob0"].shape == (512, 64)
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert np.isfinite(got["log_prob"]).all()
+    _, p0, raw, _, prior, _ = build_problem("cfg3", na)
+    for i in range(0, 512, 16):
+        lp, f, We = WN.lnprob("cfg3", got["coords"][i], raw,
+                              prior=lambda q: float(np.asarray(prior(q))))
+        assert_allclose(got["blob0"][i], f, rtol=1e-9, atol=1e-300, err_msg="walker %d" % i)
+        assert_allclose(got["blob1"][i], We, rtol=1e-9, err_msg="walker %d" % i)
+        assert_allclose(got["log_prob"][i], lp, rtol=1e-7, err_msg="walker %d" % i)
+    _line(_bench(argv + ["--dump-outputs", str(tmp_path / "b")]))
+    for k, v in got.items():
+        assert np.array_equal(np.load(tmp_path / "b" / (k + ".npy")), v), k
+
+
 def test_bench_starts_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher around it: two ranks appear (here both on
     device 0, NAIMA_AMD_DEVICE), share cfg3's ensemble through each other's rings, and rank 0

@@ -440,3 +440,31 @@ def test_sorted_columns_of_an_emission_table():
             assert O.trapz_loglog(y[r0:], x[r0:]) == full or np.isclose(O.trapz_loglog(y[r0:], x[r0:]), full, rtol=1e-15)
             if r0 > 1:
                 assert O.trapz_loglog(y[:r0 + 1], x[:r0 + 1]) == 0.0
+
+
+def test_bench_dump_outputs_writes_all_or_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: within the limit every array as given, float64; above it the same
+    seeded sample of walkers from every array (indices in walker_index), the files within the
+    limit, the same sample on every call"""
+    import bench
+    assert bench.DUMP_LIMIT_BYTES == 64 * 1000 ** 2
+    rng = np.random.default_rng(5)
+    arrays = {"coords": rng.random((1000, 5)), "log_prob": rng.random(1000),
+              "blob0": rng.random((1000, 3)), "blob1": rng.random(1000)}
+    s = bench.dump_outputs(str(tmp_path / "all"), dict(arrays), 7)
+    assert not s["sampled"] and s["steps_made"] == 7 and s["walkers_total"] == 1000
+    for k, a in arrays.items():
+        b = np.load(tmp_path / "all" / (k + ".npy"))
+        assert b.dtype == np.float64 and np.array_equal(a, b)
+    assert not (tmp_path / "all" / "walker_index.npy").exists()
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 40000)
+    for d in ("s1", "s2"):
+        s = bench.dump_outputs(str(tmp_path / d), dict(arrays), 7)
+        assert s["sampled"] and sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= 40000
+    idx = np.load(tmp_path / "s1" / "walker_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "walker_index.npy"))
+    assert idx.dtype == np.float64 and len(idx) > 100 and np.all(np.diff(idx) > 0)
+    for k, a in arrays.items():
+        b = np.load(tmp_path / "s1" / (k + ".npy"))
+        assert np.array_equal(b, a[idx.astype(int)]) and s["arrays"][k] == list(b.shape)
