@@ -26,6 +26,9 @@ from . import units as u
 from .darray import DMat, DPars, DVec
 from .dist import shard_bounds, shard_counts
 
+_GAVE_UP = ("a launch of the resident loop gave up waiting for a walker's record (status %d): its "
+            "workgroups were not all resident")
+
 
 class DeviceState:
     """what the loop yields: host views are fetched on first access"""
@@ -228,12 +231,10 @@ class DeviceLoop:
         # two blocks of moves at most, by the per-launch kernel (sample)
         self._rl_count = 0     # launches queued so far (the library counts them the same way)
         self._rl_pending = []
-        self._verify = os.environ.get("NAIMA_AMD_VERIFY_LAUNCHES", "1") != "0"
         # copies of the current blobs as a launch WITHOUT a history found them (such a launch
         # writes the blobs of accepted moves straight into the current-blob arrays): what a
         # launch that gave up -- or ran void behind one that did -- is rolled back to
         self._cur_snaps = [None] * 4
-        self._last_snap = None
         self._nan_pending = self._forbidden_pending = 0
         _n = _lib._i(0)  # (the context's word may hold what an earlier sampler left uncounted)
         _lib._chk(_lib._lib.nh_nan_count(self.ctx.h, 1, C.byref(_n)))
@@ -258,7 +259,9 @@ class DeviceLoop:
         # and make the journal's steps again with one launch and one all-gather per half-step
         # (the reference's Pool carries on when a worker is slow, core.py:523-536; this used to be
         # an exception on every rank)
-        self._flushed = False  # (nothing has run since the last flush: see flush)
+        # what has changed the device state (initial states uploaded, steps queued), and its value
+        # at the last full flush (None: none since the last reset) -- see flush
+        self._changes, self._flushed_at = 0, None
         self._sh_snap = None
         self._sh_want = False
         self._sh_journal = []
@@ -280,7 +283,7 @@ class DeviceLoop:
             _lib._chk(_lib._lib.nh_half_step_run_counters(self.ctx.h, self._run, None, None, 1))
             self._acc_dirty, self._acc_shared = False, 0.0
         self._acc_base = 0.0
-        self._flushed = False
+        self._flushed_at = None
 
     def _eval(self, qT_buf, n):
         """run the user's model on device parameters: (total DVec, blob list)"""
@@ -602,11 +605,13 @@ class DeviceLoop:
         else:
             ctx.call("nh_copy", self.logp, total.ptr, 8 * self.N)
         if s.store_blobs and blobs:
-            self.cur_blobs, units = [], []
+            # (a later initial state keeps the current-blob arrays: captured graphs and the
+            # one-launch plan point at them)
+            old, self.cur_blobs, units = self.cur_blobs or [], [], []
             ident = ctx.array(np.arange(lo, hi, dtype=np.int32), dtype=np.int32)
-            for b in blobs:
+            for i, b in enumerate(blobs):
                 own, ptr, m, unit, trail = self._blob_dense(b)
-                cur = ctx.empty((self.N, m))
+                cur = old[i][0] if i < len(old) and old[i][1] == m else ctx.empty((self.N, m))
                 if self.sharded:
                     self._gather_rows(ptr, cur, self.N, m)
                 else:
@@ -621,6 +626,7 @@ class DeviceLoop:
             raise ValueError("Probability function returned NaN")
         self._have_state = True
         self._cur_host = None
+        self._changes += 1
 
     def host_blobs(self):
         if not self.cur_blobs:
@@ -635,20 +641,17 @@ class DeviceLoop:
     def sample(self, initial_state, iterations, store, yield_every=1):
         from .sampler import State
         s, ctx = self.s, self.ctx
-        if isinstance(initial_state, DeviceState) and initial_state._loop is self:
-            pass  # continue from the ensemble already in HBM
-        else:
+        cont = isinstance(initial_state, DeviceState) and initial_state._loop is self
+        if not cont:  # (else: continue from the ensemble already in HBM)
             st = State(initial_state)
             if st.coords.shape != (self.N, self.ndim):
                 raise ValueError("incompatible input dimensions")
             self._init_state(st.coords, st.log_prob)
-        rng, N, ns = s._rng, self.N, self.ns
+        N = self.N
         iterations = int(iterations)
         jentry = None
-        self._flushed = False
         if self.sharded and s.comm.size > 1 and not self._replaying and self._run is not False:
-            fresh = not (isinstance(initial_state, DeviceState) and initial_state._loop is self)
-            if self._sh_snap is None or fresh:  # (normally kept at the verified point itself, below)
+            if self._sh_snap is None or not cont:  # (normally kept at the verified point itself)
                 self._shared_snapshot()
             # (the steps the call has MADE, kept up to date as it goes: a caller that breaks out of
             # the generator early must not have the full count replayed -- ADVICE r5)
@@ -676,80 +679,50 @@ class DeviceLoop:
                         ctx.call("nh_copy", c0, cur, 8 * N * m)
                         block["cur0"].append(c0)
             self.hist.append(block)
-        if not (isinstance(initial_state, DeviceState) and initial_state._loop is self):
+        if not cont:
             self._sync_cur_blobs()
-        # chain history: appended on the device by nh_move_cycle when it is active for
-        # the whole call, else one pair of copies per step
-        dev_hist = self.fused and block is not None and not (
-            self.mega and self._plan["hs"] is None)  # (the launch's plan does not exist yet)
-        blob_hist_ok = not (block is not None and block["blobs"] and not (dev_hist and self.blobs_in_kernel))
+        # the launches append the chain history themselves (the nh_hist descriptor) when the
+        # call keeps one and the launch's plan exists; else one pair of copies per step ...
+        dev_hist = self.fused and block is not None and not (self.mega and self._plan["hs"] is None)
+        # ... and the blobs' histories too, in the one-launch mode
+        blob_dev_hist = dev_hist and self.blobs_in_kernel
+        # several steps per launch need whatever the call keeps to be kept by the launches
+        whole = (block is None or dev_hist) and not (block is not None and block["blobs"] and
+                                                     not blob_dev_hist)
         # the whole call as launches of the resident loop, one per block of moves: nothing of the
         # per-launch kernel's bookkeeping (history descriptor words, slice counter) is needed
-        fast = (self._resident_ok() and yield_every >= iterations and (block is None or dev_hist)
-                and blob_hist_ok)
-        def per_launch_history():
-            # (the per-launch kernel's history descriptor: where its launches append the chain)
-            words = [block["coords"].ptr, block["logp"].ptr, 0, iterations] if dev_hist \
-                else [0, 0, 0, 0]
-            if dev_hist and self.blobs_in_kernel:
-                words = words + [hb.ptr for hb in block["blobs"]]
-            words = (words + [0, 0, 0, 0])[:8]
-            ctx.call("nh_set_words", self.histd, (C.c_longlong * 8)(*words), 8)
-
-        if self.fused and not fast:
-            per_launch_history()
-        blob_dev_hist = dev_hist and self.blobs_in_kernel  # the launches append the blobs too
-        moves = s.moves(pinned=True)
+        fast = self._resident_ok() and yield_every >= iterations and whole
         it = 0
-        mv = self._mv
+        if fast:
+            it = yield from self._sample_resident(iterations, block, jentry)
+        if not fast or it < iterations:
+            yield from self._sample_per_launch(it, iterations, yield_every, block, jentry,
+                                               dev_hist, blob_dev_hist, whole)
+        self._flush_pending()
 
-        def rollback(rec):
-            """a launch of the resident loop gave up waiting for a walker's record (its workgroups
-            were not all resident: another process on the GPU, a profiler) -- `rec` is the first
-            such launch, everything queued behind it found the same status and changed nothing
-            either (k_run_epilogue leaves the ensemble, the counters and the blobs as a launch
-            that gave up found them).  The books go back to where `rec` was queued, the move
-            stream is made again up to that step (a function of the seed), and the per-launch
-            loop takes over for good: -> (it, the new move stream)"""
-            import warnings
-            from ._lib import Moves
-            void = [r for r in self._rl_pending if r["launch"] >= rec["launch"]]
-            self._rl_pending = []
-            ctx.sync()  # (the void launches behind it: nothing of theirs may still be running)
-            self.resident_reason = ("a launch of the resident loop gave up waiting for a walker's "
-                                    "record (status %d): its workgroups were not all resident"
-                                    % rec["status"])
-            warnings.warn(self.resident_reason + "; %d block(s) of moves are replayed and the run "
-                          "continues with one launch per half-step" % len(void))
-            self._run = False
-            self.resident_failed_launches += len(void)
-            self._read_counts(reset=False, set_to=rec["counts"])  # (the replay counts them again)
-            self._restore_cur_blobs(rec.get("snap"))  # (a void launch behind it may have written some)
-            s.iteration, s.steps_total = rec["iteration"], rec["steps_total"]
-            s.n_lnprob_calls, s.n_walker_evals = rec["nlc"], rec["nwe"]
-            self.resident_launches = rec["rl"]
-            if block is not None:
-                block["n"] = rec["block_n"]
-            while self._inflight:
-                ctx.call("nh_marker_wait", self._inflight.pop(0))
-            mv["have"] = mv["used"] = 0
-            mv["ahead"] = mv["prev"] = mv["last"] = None
-            old = s._moves
-            s._moves = Moves(s.seed, s.nwalkers, s.a, ksteps=32, depth=4, pinned=True)
-            if old is not None:
-                old.close()
-            left = rec["steps_total"]
-            while left > 0:  # (the steps every loop of this sampler has made so far)
-                _, got = s._moves.take(min(32, left))
-                left -= got
-            if self.fused:
-                per_launch_history()
-            return rec["it"], s._moves
-        while fast and it < iterations:
-            # up to KSTEPS steps per launch.  The moves are a function of the seed only, so the
-            # stream's next steps are already on the device (uploaded ahead, below) unless this
-            # is the first call; the generator hands its stream out in pieces that end at its
-            # own block boundaries: they land side by side in `blk` and run as ONE launch
+    def _advance(self, g, block, jentry):
+        """the books after `g` more steps of the call"""
+        s = self.s
+        s.iteration += g
+        s.steps_total += g
+        if jentry is not None:
+            jentry[0] += g
+        if block is not None:
+            block["n"] += g
+        self._changes += 1
+
+    def _sample_resident(self, iterations, block, jentry):
+        """the call as launches of the resident loop, up to KSTEPS steps each, a launch checked
+        when the one behind it is queued (_rl_settle) -> the steps made: fewer than `iterations`
+        when a launch gave up, and the per-launch loop makes the rest"""
+        ctx, mv = self.ctx, self._mv
+        moves = self.s.moves(pinned=True)
+        it = 0
+        while it < iterations:
+            # the moves are a function of the seed only, so the stream's next steps are already on
+            # the device (uploaded ahead, below) unless this is the first call; the generator hands
+            # its stream out in pieces that end at its own block boundaries: they land side by side
+            # in `blk` and run as ONE launch
             want = min(self.KSTEPS, iterations - it)
             if mv["have"] - mv["used"] < want:
                 need = want - (mv["have"] - mv["used"])
@@ -759,27 +732,17 @@ class DeviceLoop:
             if mv["ahead"] is not None:  # the launch waits for the copy stream's last upload
                 ctx.call("nh_stream_wait_marker", mv["ahead"])
                 mv["ahead"] = None
-            verify = self._verify and not self.shared
-            if verify and len(self._rl_pending) >= 2:
+            if len(self._rl_pending) >= 2:
                 # launch n + 1 is queued only once launch n - 1 is known to have ended well (launch
                 # n is running meanwhile: the device does not wait for this)
                 gave_up = self._rl_settle(keep=1)
                 if gave_up is not None:
-                    it, moves = rollback(gave_up)
-                    if jentry is not None:
-                        jentry[0] = it
-                    fast = False
-                    break
-            rec = dict(launch=self._rl_count + 1, it=it, iteration=s.iteration, steps_total=s.steps_total,
-                       block_n=block["n"] if block is not None else None, nlc=s.n_lnprob_calls,
-                       nwe=s.n_walker_evals, rl=self.resident_launches)
-            if not self._run_resident(2 * mv["used"], 2 * want, block):
-                fast = False  # (gave up: the per-launch loop below replays these steps)
-                if self.fused:
-                    per_launch_history()
-                break
-            if verify:
-                rec["snap"] = self._last_snap
+                    return self._rollback(gave_up)
+            rec = self._run_resident(2 * mv["used"], 2 * want, block)
+            if rec is None:
+                return it  # (gave up: the per-launch loop replays these steps)
+            if not self.shared:  # (a shared loop's launches are checked where all ranks are)
+                rec["it"] = it
                 self._rl_pending.append(rec)
             mv["used"] += want
             # a marker behind this launch: `blk` is a ring, and the host runs launches ahead of
@@ -794,24 +757,31 @@ class DeviceLoop:
                     mv["have"] + self.KSTEPS <= self.MOVES_CAP:
                 self._moves_append(moves, self.KSTEPS, ahead=True)
             it += want
-            if jentry is not None:
-                jentry[0] = it
-            s.iteration += want
-            s.steps_total += want
-            if block is not None:
-                block["n"] += want
+            self._advance(want, block, jentry)
             if it >= iterations and self._rl_pending:
                 # the call's last launches: known to have ended well before the state is handed out
                 gave_up = self._rl_settle(keep=0)
                 if gave_up is not None:
-                    it, moves = rollback(gave_up)
-                    if jentry is not None:
-                        jentry[0] = it
-                    fast = False
-                    break
-            yield DeviceState(self, rng)
+                    return self._rollback(gave_up)
+            yield DeviceState(self, self.s._rng)
+        return it
+
+    def _sample_per_launch(self, it, iterations, yield_every, block, jentry, dev_hist,
+                           blob_dev_hist, whole):
+        """steps it .. iterations of the call, a block of KSTEPS moves uploaded at a time, with one
+        launch per half-step, a graph of several steps, or the resident loop for a block's rest"""
+        s, ctx, mv, N, ns = self.s, self.ctx, self._mv, self.N, self.ns
+        if self.fused:
+            # (the per-launch kernel's history descriptor: where its launches append the chain)
+            words = [block["coords"].ptr, block["logp"].ptr, 0, iterations] if dev_hist \
+                else [0, 0, 0, 0]
+            if blob_dev_hist:
+                words = words + [hb.ptr for hb in block["blobs"]]
+            words = (words + [0, 0, 0, 0])[:8]
+            ctx.call("nh_set_words", self.histd, (C.c_longlong * 8)(*words), 8)
+        moves = s.moves(pinned=True)
         if it < iterations:
-            mv["prev"] = mv["last"] = None  # (the per-launch loop takes over: see _moves_append)
+            mv["prev"] = mv["last"] = None  # (see _moves_append)
         while it < iterations:
             self._flush_pending()  # (merged sharded mode) the block's last accept
             self._sync_cur_blobs()  # (launches per half-step keep every rank's blobs whole)
@@ -858,8 +828,7 @@ class DeviceLoop:
                 g = 1
                 gmax = min(self.GSTEPS, K - k) if self.mega else self.GSTEPS
                 resident = False
-                if (self._resident_ok() and yield_every >= K - k and (block is None or dev_hist)
-                        and not (block is not None and block["blobs"] and not blob_dev_hist)):
+                if self._resident_ok() and yield_every >= K - k and whole:
                     # the rest of this block of moves in ONE launch of resident workgroups
                     g = K - k
                     if k > 0 and dev_hist:
@@ -871,12 +840,11 @@ class DeviceLoop:
                             ctx.call("nh_half_step_append_blobs", self._plan["hs"]["plan"],
                                      block["n"] - 1)
                     self._flush_pending()
-                    if not self._run_resident(2 * k, 2 * g, block if dev_hist else None):
+                    if self._run_resident(2 * k, 2 * g, block if dev_hist else None) is None:
                         continue  # (gave up: _resident_ok() is false from now on)
                     resident = True
                 elif (self.step_graph is not None and self.fused and K - k >= gmax >= 2 and
-                        yield_every >= gmax and (block is None or dev_hist) and
-                        not (block is not None and block["blobs"] and not blob_dev_hist)):
+                        yield_every >= gmax and whole):
                     g = gmax
                     # one launch per half-step: the slices are baked into the graph (the
                     # proposal's chain of dependent reads is one trip shorter), so there is
@@ -887,8 +855,7 @@ class DeviceLoop:
                         self.multi_graphs[key] = self.multi_graph = self._capture_steps(k, g)
                     ctx.graph_launch(self.multi_graphs[key])
                 elif (self.split and self.graph2 is not None and self.fused and
-                        yield_every >= 2 and (block is None or dev_hist) and
-                        not (block is not None and block["blobs"])):
+                        yield_every >= 2 and whole and not (block is not None and block["blobs"])):
                     # sharded, nobody looks at the intermediate states: the accept of a
                     # half-step and the evaluation of the next are ONE graph, with the
                     # all-gather between two such graphs (two host calls per half-step
@@ -903,10 +870,6 @@ class DeviceLoop:
                     mark_pending = False
                 k += g
                 it += g
-                if jentry is not None:
-                    jentry[0] = it
-                s.iteration += g
-                s.steps_total += g
                 if block is not None:
                     kk = block["n"]
                     if not dev_hist:
@@ -916,7 +879,7 @@ class DeviceLoop:
                     if not blob_dev_hist:
                         for hb, (cur, m, _, _) in zip(block["blobs"], self.cur_blobs or []):
                             ctx.call("nh_copy", hb.ptr + 8 * kk * N * m, cur, 8 * N * m)
-                    block["n"] = kk + g
+                self._advance(g, block, jentry)
                 if yield_every < 2:
                     self._flush_pending()
                 if self.mega and dev_hist and not resident and (k >= K or yield_every <= iterations):
@@ -930,8 +893,7 @@ class DeviceLoop:
                     if blob_dev_hist:
                         ctx.call("nh_half_step_append_blobs", self._plan["hs"]["plan"],
                                  block["n"] - 1)
-                yield DeviceState(self, rng)
-        self._flush_pending()
+                yield DeviceState(self, s._rng)
 
     # ------------------------------------------------------------- the move stream on the device
     def _moves_append(self, moves, n, ahead):
@@ -1185,6 +1147,8 @@ class DeviceLoop:
                         p_[t][rej] = (p_[t - 1] if t > 0 else c0)[rej]
 
     def _run_resident(self, slice0, nslices, block):
+        """queue a launch of the resident loop -> the books as it found them (_checkpoint, with the
+        launch's number and its copy of the current blobs), or None if it was checked and gave up"""
         ctx, hs = self.ctx, self._plan["hs"]
         if self.shared:
             self._acc_dirty = True
@@ -1203,6 +1167,7 @@ class DeviceLoop:
             row0, cap = block["n"], block["coords"].shape[0]
             if block["blobs"]:
                 hb = (C.c_void_p * 4)(*([b.ptr for b in block["blobs"]] + [None] * 4)[:4])
+        books = self._checkpoint(block)
         probation = not self.shared and self._resident_trust < 2
         if probation:
             # The first launches of a loop are checked before anything builds on them: a launch
@@ -1212,33 +1177,91 @@ class DeviceLoop:
             # same block of moves is replayed by the per-launch kernel and the run carries on
             # with one launch per half-step.  (A shared ensemble: the ranks agree in
             # _create_shared_run / bench.py's rehearsal and raise together on a later time-out; a
-            # one-GPU loop's later launches are checked a launch behind: sample, _rl_settle.)
-            n0, f0 = self._read_counts(reset=False)
-        self._last_snap = None
+            # one-GPU loop's later launches are checked a launch behind: _sample_resident.)
+            books["counts"] = self._read_counts(reset=False)
         if block is None and not self.shared and self.s.store_blobs and self.cur_blobs:
-            self._last_snap = self._snapshot_cur_blobs()
+            books["snap"] = self._snapshot_cur_blobs()
         ctx.call("nh_half_step_run", hs["plan"], self._run, slice0, nslices, hc, hl, hb, row0, cap)
         self._rl_count += 1
+        books["launch"] = self._rl_count  # (the library numbers a loop's launches the same way)
         if probation:
             st = _lib._i()
             _lib._chk(_lib._lib.nh_half_step_run_status(ctx.h, self._run, C.byref(st)))
             if st.value != 0:
-                import warnings
-                self.resident_reason = ("a launch of the resident loop gave up waiting for a walker's "
-                                        "record (status %d): its workgroups were not all resident"
-                                        % st.value)
-                warnings.warn(self.resident_reason + "; the block of moves is replayed and the run "
-                              "continues with one launch per half-step")
-                self._run = False
-                self.resident_failed_launches += 1
-                self._read_counts(reset=False, set_to=(n0, f0))  # (the replay counts them again)
-                self._restore_cur_blobs(self._last_snap)  # (slices that finished before it gave up)
-                return False
+                # (nothing consumed the launch's moves: the per-launch loop takes them from `blk`)
+                self._leave_resident(_GAVE_UP % st.value, "the block of moves is replayed "
+                                     "and the run continues with one launch per half-step", 1, books)
+                return None
             self._resident_trust += 1
         self.resident_launches += 1
         self.s.n_lnprob_calls += nslices
         self.s.n_walker_evals += nslices * self.nloc
-        return True
+        return books
+
+    def _rollback(self, rec):
+        """a launch of the resident loop gave up waiting for a walker's record (its workgroups were
+        not all resident: another process on the GPU, a profiler) -- `rec` is the first such
+        launch, everything queued behind it found the same status and changed nothing either
+        (k_run_epilogue leaves the ensemble, the counters and the blobs as a launch that gave up
+        found them).  Back to the books `rec` holds, the move stream made again up to its step;
+        the per-launch loop takes over for good -> the step of the call to carry on from"""
+        void = sum(1 for r in self._rl_pending if r["launch"] >= rec["launch"])
+        self._rl_pending = []
+        self.ctx.sync()  # (the void launches behind it: nothing of theirs may still be running)
+        self._leave_resident(_GAVE_UP % rec["status"], "%d block(s) of moves are replayed "
+                             "and the run continues with one launch per half-step" % void, void, rec,
+                             rewind=True)
+        return rec["it"]
+
+    def _leave_resident(self, reason, then, failed, books, rewind=False):
+        """the resident loop given up for good: `failed` launches of it void, the books back to
+        `books` (with `rewind` the move stream too), the per-launch loop carries the run on"""
+        import warnings
+        self.resident_reason = reason
+        if self.s.comm.rank == 0:
+            warnings.warn(reason + "; " + then)
+        self._run, self.shared = False, False
+        self.resident_failed_launches += failed
+        self._restore(books)
+        if rewind:
+            self._rewind_moves(books["steps_total"])
+
+    def _checkpoint(self, block=None, counts=None):
+        """the host's books as one record for _restore (`counts`: the device's NaN / forbidden
+        counters to put back, when known here)"""
+        s = self.s
+        return dict(iteration=s.iteration, steps_total=s.steps_total, nlc=s.n_lnprob_calls,
+                    nwe=s.n_walker_evals, rl=self.resident_launches, nan_pending=self._nan_pending,
+                    forbidden_pending=self._forbidden_pending, hist_len=len(self.hist),
+                    block=block, block_n=block["n"] if block is not None else None,
+                    counts=counts, snap=None)
+
+    def _restore(self, books):
+        s = self.s
+        self._read_counts(reset=False, set_to=books["counts"])  # (the replay counts them again)
+        self._restore_cur_blobs(books["snap"])  # (what launches that gave up may have written)
+        s.iteration, s.steps_total = books["iteration"], books["steps_total"]
+        s.n_lnprob_calls, s.n_walker_evals = books["nlc"], books["nwe"]
+        self.resident_launches = books["rl"]
+        self._nan_pending, self._forbidden_pending = books["nan_pending"], books["forbidden_pending"]
+        self.hist = self.hist[:books["hist_len"]]  # (what predates the checkpoint stays)
+        if books["block"] is not None:
+            books["block"]["n"] = books["block_n"]
+
+    def _rewind_moves(self, steps):
+        """the move stream made again from the seed (a fresh generator, every upload of the old one
+        done) and its first `steps` steps skipped: the steps every loop of this sampler has made"""
+        s, mv = self.s, self._mv
+        while self._inflight:
+            self.ctx.call("nh_marker_wait", self._inflight.pop(0))
+        mv["have"] = mv["used"] = 0
+        mv["ahead"] = mv["prev"] = mv["last"] = None
+        old, s._moves = s._moves, None
+        moves = s.moves(pinned=True)
+        if old is not None:
+            old.close()
+        while steps > 0:
+            steps -= moves.take(min(self.KSTEPS, steps))[1]
 
     def _snapshot_cur_blobs(self):
         """device copies of the current blobs, in stream order ahead of the launch about to be
@@ -1274,15 +1297,11 @@ class DeviceLoop:
     def _shared_snapshot(self):
         """device copies of the ensemble (positions, log-probabilities, acceptance counts, current
         blobs) and the host's books, at a point where every rank is known to be well"""
-        ctx, s = self.ctx, self.s
+        ctx = self.ctx
         self._flush_pending()
-        snap = dict(coords=ctx.empty((self.N * self.ndim,)), logp=ctx.empty((self.N,)),
-                    nacc=ctx.empty((self.N,), dtype=np.int32), blobs=[],
-                    iteration=s.iteration, steps_total=s.steps_total, nlc=s.n_lnprob_calls,
-                    nwe=s.n_walker_evals, rl=self.resident_launches,
-                    nan_pending=self._nan_pending, forbidden_pending=self._forbidden_pending,
-                    # (chain rows of earlier calls that nobody has asked for yet: they stay)
-                    hist_len=len(self.hist))
+        # (the device's counters: drained at the kept state, the replay counts again)
+        snap = dict(self._checkpoint(counts=(0, 0)), coords=ctx.empty((self.N * self.ndim,)),
+                    logp=ctx.empty((self.N,)), nacc=ctx.empty((self.N,), dtype=np.int32), blobs=[])
         ctx.call("nh_copy", snap["coords"], self.coords, 8 * self.N * self.ndim)
         ctx.call("nh_copy", snap["logp"], self.logp, 8 * self.N)
         ctx.call("nh_copy", snap["nacc"], self.nacc, 4 * self.N)
@@ -1320,22 +1339,11 @@ class DeviceLoop:
         Every rank is here (the status was reduced over all of them): back to the kept ensemble,
         the move stream made again up to its step, and the journal's calls once more -- one launch
         and one all-gather per half-step from here on."""
-        import warnings
-        from ._lib import Moves
-        ctx, s, snap = self.ctx, self.s, self._sh_snap
-        journal = list(self._sh_journal)
+        ctx, s, snap, journal = self.ctx, self.s, self._sh_snap, self._sh_journal
         ctx.sync()
-        self.resident_reason = ("a launch of the resident loop over the shared ensemble gave up waiting "
-                                "for a record (status %d%s)" % (bad, "" if bad == mine else ", on another rank"))
-        if s.comm.rank == 0:
-            warnings.warn(self.resident_reason + "; every rank goes back %d step(s) to the last ensemble "
-                          "all of them held and carries on with one launch and one all-gather per "
-                          "half-step" % (s.steps_total - snap["steps_total"]))
-        self.resident_failed_launches += max(1, self.resident_launches - snap["rl"])
         # what the shared launches accepted up to the kept state stays counted (flush folded it)
         self._acc_base = self._acc_base + self._acc_shared
         self._acc_shared, self._acc_dirty = 0.0, False
-        self._run, self.shared = False, False
         self._cur_dirty, self._cur_host = False, None
         self._sh_snap, self._sh_journal = None, []
         ctx.call("nh_copy", self.coords, snap["coords"], 8 * self.N * self.ndim)
@@ -1343,25 +1351,12 @@ class DeviceLoop:
         ctx.call("nh_copy", self.nacc, snap["nacc"], 4 * self.N)
         for b, (cur, m, _, _) in zip(snap["blobs"], self.cur_blobs or []):
             ctx.call("nh_copy", cur, b, 8 * self.N * m)
-        self.hist = self.hist[:snap.get("hist_len", 0)]  # (what predates the kept ensemble stays)
-        s.iteration, s.steps_total = snap["iteration"], snap["steps_total"]
-        s.n_lnprob_calls, s.n_walker_evals = snap["nlc"], snap["nwe"]
-        self.resident_launches = snap["rl"]
-        self._read_counts(reset=False, set_to=(0, 0))  # (drained at the kept state; the replay counts again)
-        self._nan_pending, self._forbidden_pending = snap["nan_pending"], snap["forbidden_pending"]
-        while self._inflight:
-            ctx.call("nh_marker_wait", self._inflight.pop(0))
-        mv = self._mv
-        mv["have"] = mv["used"] = 0
-        mv["ahead"] = mv["prev"] = mv["last"] = None
-        old = s._moves
-        s._moves = Moves(s.seed, s.nwalkers, s.a, ksteps=32, depth=4, pinned=True)
-        if old is not None:
-            old.close()
-        left = snap["steps_total"]
-        while left > 0:
-            _, got = s._moves.take(min(32, left))
-            left -= got
+        self._leave_resident(
+            "a launch of the resident loop over the shared ensemble gave up waiting for a record "
+            "(status %d%s)" % (bad, "" if bad == mine else ", on another rank"),
+            "every rank goes back %d step(s) to the last ensemble all of them held and carries on "
+            "with one launch and one all-gather per half-step" % (s.steps_total - snap["steps_total"]),
+            max(1, self.resident_launches - snap["rl"]), snap, rewind=True)
         self._replaying = True
         try:
             for made, store, yield_every in journal:
@@ -1453,8 +1448,8 @@ class DeviceLoop:
         serialises workgroups); the ensemble is undefined from that launch on.  (A one-GPU
         loop's launches are checked as they are made, or a launch behind, and replayed by the
         per-launch kernel instead: _run_resident, sample -- what is left to find here is a
-        shared ensemble's, or a loop run with NAIMA_AMD_VERIFY_LAUNCHES=0.)  ``collective``: every rank is here -- the worst status
-        of all ranks decides, and all of them raise."""
+        shared ensemble's.)  ``collective``: every rank is here -- the worst status of all ranks
+        decides, and all of them raise."""
         if self.shared and not collective and self.s.comm is not None and self.s.comm.size > 1:
             # a shared loop's status is acted on where EVERY rank is (flush, reset): an exception on
             # the one rank that reads its state here would leave the others waiting in their next
@@ -1615,13 +1610,13 @@ class DeviceLoop:
 
     def flush(self):
         """bring the pending chain history and acceptance counters to the host"""
-        if self._flushed and not self.hist and not self._pending:
+        if self._flushed_at == self._changes and not self.hist and not self._pending:
             # nothing has run since the last flush: the books are on the host already.  (With
-            # several ranks a flush is collective; the ranks run the same program, so this early
-            # return is taken by all of them or none -- and a rank that reads its results AGAIN,
-            # alone, after the others have left -- rank 0 writing the run to disk, as the
-            # reference's save_run does in its one process, analysis.py:366-471 -- is not left
-            # waiting for peers that are gone.)
+            # several ranks a flush is collective; the count follows the calls, which the ranks
+            # make alike, so this early return is taken by all of them or none -- and a rank that
+            # reads its results AGAIN, alone, after the others have left -- rank 0 writing the run
+            # to disk, as the reference's save_run does in its one process, analysis.py:366-471 --
+            # is not left waiting for peers that are gone.)
             return
         self._flush_pending()
         self.check_resident(collective=True)
@@ -1663,4 +1658,4 @@ class DeviceLoop:
                     self._acc_shared += np.frombuffer(p_, dtype=np.int32)
             s.naccepted += self._acc_shared
         self.keep_verified()
-        self._flushed = True
+        self._flushed_at = self._changes

@@ -1261,3 +1261,106 @@ def test_sorted_table_trailers_are_checked_at_the_abi(na):
     st2 = ref.run_mcmc(ref.run_mcmc(pos, 8), 8)
     st, st2 = d.run_mcmc(st, 40), ref.run_mcmc(st2, 40)
     assert np.array_equal(st.coords, st2.coords)
+
+
+def test_acceptance_read_after_every_step_of_a_call_without_history(na):
+    """a caller that iterates sample(store=False) and reads the acceptance after every state: each
+    read sees the steps made since the last one (a flush with steps run since the one before is
+    not skipped), as on the host-driven loop"""
+    from naima_amd.sampler import EnsembleSampler
+    model, p0, raw, data, prior = _problem(na, "cfg1", {})
+    nw, nd = 32, p0.size
+    kw = dict(args=[data, model, prior], seed=31, naima_style=True)
+    h = EnsembleSampler(nw, nd, na.lnprob, **kw)
+    d = EnsembleSampler(nw, nd, na.lnprob, device=True, **kw)
+    pos = p0 * (1 + 0.003 * np.random.default_rng(5).standard_normal((nw, nd)))
+    n = 0
+    for _ in zip(h.sample(pos, iterations=6, store=False), d.sample(pos, iterations=6, store=False)):
+        n += 1
+        assert_allclose(d.acceptance_fraction, h.acceptance_fraction, err_msg="after step %d" % n)
+    assert n == 6 and d.iteration == h.iteration == 6
+    assert d.acceptance_fraction.sum() > 0
+
+
+def test_seeded_call_sequences_equal_the_host_loop(na):
+    """the calls users string together -- run_mcmc with and without a history, iterating sample()
+    and breaking off early, reset, the getters, a fresh initial state -- in sequences drawn from a
+    fixed seed, on the device loop (one run_mcmc crosses 32-step blocks of moves and resident
+    launches) and on the host-driven loop: after every read, the same chain, log-probabilities,
+    blobs, acceptance and iteration"""
+    from naima_amd.sampler import EnsembleSampler
+    model, p0, raw, data, prior = _problem(na, "cfg1", {})
+    nw, nd = 32, p0.size
+    kw = dict(args=[data, model, prior], seed=31, naima_style=True, store_blobs=True)
+    rng = np.random.default_rng(20261015)
+
+    def ball():
+        return p0 * (1 + 0.003 * rng.standard_normal((nw, nd)))
+
+    def compare(h, d, where):
+        assert d.iteration == h.iteration, where
+        ch, cd = h.get_chain(), d.get_chain()
+        assert cd.shape == ch.shape, where
+        assert_allclose(cd, ch, rtol=1e-8, err_msg=where)
+        assert_allclose(d.get_log_prob(), h.get_log_prob(), rtol=1e-6, err_msg=where)
+        bh, bd = h.get_blobs(), d.get_blobs()
+        assert (bh is None) == (bd is None), where
+        for x, y in zip(bd or [], bh or []):
+            x, y = np.asarray(x, dtype=float), np.asarray(y, dtype=float)
+            assert x.shape == y.shape, where
+            assert_allclose(x, y, rtol=1e-8, atol=1e-300, equal_nan=True, err_msg=where)
+        assert_allclose(d.acceptance_fraction, h.acceptance_fraction, err_msg=where)
+
+    resident = 0
+    for seq in range(24):
+        h = EnsembleSampler(nw, nd, na.lnprob, **kw)
+        d = EnsembleSampler(nw, nd, na.lnprob, device=True, **kw)
+        sh = sd = pos = ball()
+        ops = []
+        for _ in range(int(rng.integers(4, 9))):
+            op = ("run", "run", "iter", "reset", "read", "read", "fresh")[int(rng.integers(7))]
+            if op == "run":
+                ops.append((op, int(rng.integers(1, 71)), bool(rng.integers(2))))
+            elif op == "iter":
+                # to its end, or broken off where a block of 32 moves ends (a generator left in the
+                # middle of a block has taken the block's moves from the stream: the device loop's
+                # next call starts behind them, the host loop's does not)
+                k = int(rng.integers(2, 71))
+                ops.append((op, k, 32 if k > 32 and rng.integers(2) else k))
+            elif op == "read":
+                ops.append((op, ("get_chain", "get_log_prob", "get_blobs",
+                                 "acceptance_fraction")[int(rng.integers(4))]))
+            else:
+                ops.append((op,))
+        ops.append(("read", "acceptance_fraction"))
+        made = 0  # steps since the last initial state
+        for i, op in enumerate(ops):
+            where = "sequence %d, call %d of %s" % (seq, i, ops)
+            if op[0] in ("run", "iter"):
+                made += op[1]
+                if made > 120:  # (positions drift apart by rounding over hundreds of chained steps)
+                    sh = sd = pos = ball()
+                    made = op[1]
+            if op[0] == "run":
+                sh = h.run_mcmc(sh, op[1], store=op[2])
+                sd = d.run_mcmc(sd, op[1], store=op[2])
+            elif op[0] == "iter":
+                for j, (sh, sd) in enumerate(zip(h.sample(sh, op[1]), d.sample(sd, op[1])), 1):
+                    if j == op[2] < op[1]:
+                        break
+            elif op[0] == "reset":
+                h.reset()
+                d.reset()
+            elif op[0] == "fresh":
+                sh = sd = pos = ball()
+                made = 0
+            else:
+                for smp in (h, d):  # (the call the user makes first, then all of them)
+                    got = getattr(smp, op[1])
+                    if callable(got):
+                        got()
+                compare(h, d, where)
+                if sd is not pos:
+                    assert_allclose(sd.coords, sh.coords, rtol=1e-8, err_msg=where)
+        resident += d._dev.resident_launches if d._dev is not None else 0
+    assert resident > 0  # (the device samplers took the resident loop)
