@@ -391,20 +391,6 @@ int nh_scatter_rows(nh_ctx* ctx, double* dst, int ldd, const double* src, int ld
                     const int* idx, const int* accepted, int lo, int nloc, int m);
 int nh_copy(nh_ctx* ctx, void* dev_dst, const void* dev_src, long long bytes);
 
-/* side streams: independent pieces of one model evaluation (the radiative components)
- * run concurrently; under capture they become branches of the graph.  fork: side stream
- * `side` (0..3) starts after everything issued so far on the main stream and becomes
- * the current stream; wait: stream `waiter` waits for `producer`'s work so far (-1 =
- * main); join: the main stream waits for every forked side stream and becomes current
- * again (nh_sync, nh_download and nh_graph_end join implicitly). */
-int nh_stream_fork(nh_ctx* ctx, int side);
-/* as nh_stream_fork, but the side stream waits only for `marker` (nh_marker_record on the
- * main stream right after the launch whose output the branch consumes) */
-int nh_stream_fork_at(nh_ctx* ctx, int side, void* marker);
-int nh_stream_switch(nh_ctx* ctx, int side);
-int nh_stream_wait(nh_ctx* ctx, int waiter, int producer);
-int nh_stream_join(nh_ctx* ctx);
-
 /* ---- the general electron path: a particle grid PER WALKER --------------------------------
  * Eemin / Eemax as per-walker values (fit parameters; the reference takes any keyword as
  * per-call state, radiative.py:280, 430): walker w integrates over

@@ -93,11 +93,6 @@ _SIGS = {
                          _dp],
     "nh_scatter_rows": [_dp, _dp, _i, _dp, _i, _dp, _dp, _i, _i, _i],
     "nh_copy": [_dp, _dp, _dp, _ll],
-    "nh_stream_fork": [_dp, _i],
-    "nh_stream_fork_at": [_dp, _i, _dp],
-    "nh_stream_switch": [_dp, _i],
-    "nh_stream_wait": [_dp, _i, _i],
-    "nh_stream_join": [_dp],
     "nh_moves_create": [C.c_ulonglong, _i, _d, _i, _i, _i, C.POINTER(_dp)],
     "nh_moves_take": [_dp, _i, C.POINTER(_dp), C.POINTER(_i)],
     "nh_moves_destroy": [_dp],
@@ -277,13 +272,10 @@ class Moves:
 
 class DeviceArray:
     """A float64 (or int32) array in HBM owned by a Context's pool."""
-    __slots__ = ("ctx", "ptr", "shape", "dtype", "nbytes", "_cap", "stream", "anchor",
-                 "graph_owned", "pending", "__weakref__")
+    __slots__ = ("ctx", "ptr", "shape", "dtype", "nbytes", "_cap", "graph_owned", "pending", "__weakref__")
 
     def __init__(self, ctx, ptr, shape, dtype, cap, nbytes=None):
         self.ctx, self.ptr, self.shape, self.dtype, self._cap = ctx, ptr, tuple(shape), dtype, cap
-        self.stream = ctx.cur_stream  # the stream whose work produces this buffer
-        self.anchor = None
         # allocated while a hipGraph was being captured: the graph keeps using the address
         # on every replay, so the buffer never returns to the general pool
         self.graph_owned = bool(ctx.capturing)
@@ -300,7 +292,6 @@ class DeviceArray:
     def get(self):
         if self.ctx.capturing:
             raise RuntimeError("device->host download while a hipGraph is being captured")
-        self.ctx.join()
         out = np.empty(self.shape, dtype=self.dtype)
         if out.nbytes:
             _chk(_lib.nh_download(self.ctx.h, out.ctypes.data, self.ptr, out.nbytes))
@@ -349,19 +340,9 @@ class Context:
         self._deferred = []
         self._pinned = set()
         self._pinned_ptrs = set()
-        self._anchors = []
-        self._nanchor = 0
-        self.side_small = os.environ.get("NAIMA_AMD_SIDE_SMALL", "0") != "0"
         self._tables = {}
         self._big_tables = {}
         self.capturing = False
-        # side streams (nh_stream_fork/join): -1 = main
-        self.cur_stream = -1
-        self.multistream = os.environ.get("NAIMA_AMD_MULTISTREAM", "0") != "0"
-        self._next_side = 0
-        self._forked = False
-        self._limbo = []
-        self._waited = set()
         # particle grids recently asked of each distribution kind: a fresh distribution
         # evaluates all of them in one launch (nh_particle_weights_multi)
         self._wgrids = {}
@@ -404,10 +385,6 @@ class Context:
                 self._cap_pool.setdefault(cap, []).append(ptr)
             else:
                 self._retained.append((ptr, cap))  # a captured graph still writes here
-        elif self._forked:
-            # side streams are in flight: the buffer may still be read or written by a
-            # stream other than the one that will reuse it -> park it until the join
-            self._limbo.append((ptr, cap))
         else:
             self._pool.setdefault(cap, []).append(ptr)
 
@@ -849,7 +826,6 @@ class Context:
             if tiles > 8 or nG < 2:
                 continue
             Kh, dKh = np.empty((nG, nK)), np.empty((nG, nK))
-            self.join()
             _chk(_lib.nh_download(self.h, Kh.ctypes.data, Kt, Kh.nbytes))
             _chk(_lib.nh_download(self.h, dKh.ctypes.data, dKt, dKh.nbytes))
             perm, row0 = sorted_columns(Kh)
@@ -871,55 +847,6 @@ class Context:
         if keep:
             _chk(_lib.nh_half_step_run_tables(self.h, hs["plan"], run, ptrs, 4))
             hs.setdefault("sorted", []).append(keep)  # (alive as long as the plan)
-
-    # -- side streams ---------------------------------------------------------
-    def branch(self):
-        """context manager: run the enclosed launches on the next side stream (after
-        everything issued so far on the main stream).  No-op when already inside a
-        branch or when multistream is off."""
-        return _Branch(self)
-
-    def anchor(self):
-        """a marker recorded now on the main stream (ring of 16): ``branch_at`` hangs a
-        side stream off this point"""
-        if self.cur_stream != -1:
-            return None
-        if not self._anchors:
-            self._anchors = [self.marker() for _ in range(16)]
-        m = self._anchors[self._nanchor % 16]
-        self._nanchor += 1
-        _chk(_lib.nh_marker_record(self.h, m))
-        return m
-
-    def branch_at(self, anchor):
-        """context manager: the enclosed launches go to a side stream that waits only
-        for ``anchor`` -- small reductions (We, Wp) then run beside the emission kernels
-        issued before them.  No-op without an anchor or inside another branch."""
-        return _Branch(self, anchor=anchor)
-
-    def need(self, *objs):
-        """make the current stream wait for the streams that produced ``objs``"""
-        if not self._forked:
-            return
-        for o in objs:
-            st = getattr(o, "stream", None)
-            if st is None or st == self.cur_stream or st == -1:
-                continue  # main-stream producers are ordered by the fork itself
-            key = (self.cur_stream, st)
-            if key not in self._waited:
-                _chk(_lib.nh_stream_wait(self.h, self.cur_stream, st))
-                self._waited.add(key)
-
-    def join(self):
-        """the main stream waits for every side stream and becomes current again"""
-        if self._forked:
-            _chk(_lib.nh_stream_join(self.h))
-            self._forked = False
-            self.cur_stream = -1
-            self._waited.clear()
-            for ptr, cap in self._limbo:
-                self._pool.setdefault(cap, []).append(ptr)
-            self._limbo = []
 
     def array(self, host, dtype=np.float64):
         host = np.ascontiguousarray(host, dtype=dtype)
@@ -1015,7 +942,6 @@ class Context:
         self.capturing = True
 
     def graph_end(self):
-        self.join()
         self.capturing = False
         for cap, ptrs in self._cap_pool.items():  # scratch of the captured launches
             self._retained.extend((p, cap) for p in ptrs)
@@ -1061,7 +987,6 @@ class Context:
         return m
 
     def sync(self):
-        self.join()
         _chk(_lib.nh_sync(self.h))
 
     def info(self):
@@ -1122,39 +1047,6 @@ class Context:
             self._tables.clear()
             _lib.nh_destroy(self.h)
             self.h = None
-
-
-class _Branch:
-    def __init__(self, ctx, anchor=None):
-        self.ctx, self.active, self.anchor = ctx, False, anchor
-
-    def __enter__(self):
-        c = self.ctx
-        if self.anchor is not None:
-            if c.cur_stream == -1 and c.side_small:
-                side = c._next_side
-                c._next_side = (side + 1) % 4
-                _chk(_lib.nh_stream_fork_at(c.h, side, self.anchor))
-                c.cur_stream = side
-                c._forked = True
-                self.active = True
-            return self
-        # (not while a step graph is being captured: hipStreamEndCapture died on cfg4's graph
-        # with forked side streams -- ROCm 7.2 -- and the fork never paid inside a graph)
-        if c.multistream and c.cur_stream == -1 and not getattr(c, "capturing", False):
-            side = c._next_side
-            c._next_side = (side + 1) % 4
-            _chk(_lib.nh_stream_fork(c.h, side))
-            c.cur_stream = side
-            c._forked = True
-            self.active = True
-        return self
-
-    def __exit__(self, *exc):
-        if self.active:
-            _chk(_lib.nh_stream_switch(self.ctx.h, -1))
-            self.ctx.cur_stream = -1
-        return False
 
 
 _default = {}

@@ -152,7 +152,6 @@ def lnprobmodel(model, data, lp=None, blobs=()):
         N, nE = m.shape
         if nE != dd.n:
             raise ValueError("model has %d energies, data table has %d" % (nE, dd.n))
-        ctx.join()  # the emission components ran on side streams
         hook = ctx._accept_hook
         if hook is not None and (hook["N"] != N or hook["used"]):
             hook = None

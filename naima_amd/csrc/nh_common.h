@@ -36,15 +36,9 @@
 
 struct nh_prof_rec { hipEvent_t a, b; int kid; };
 
-#define NH_NSIDE 4
-
 struct nh_ctx {
   int device;
-  hipStream_t stream;        // the CURRENT stream: every launch goes here
-  hipStream_t main_stream;   // uploads, downloads, sync, graph capture origin
-  hipStream_t side[NH_NSIDE];
-  hipEvent_t ev_fork, ev_side[NH_NSIDE];
-  bool side_used[NH_NSIDE];
+  hipStream_t stream;  // every launch, upload, download and sync; the graph capture origin
   hipEvent_t t0, t1;
   bool profiling;
   std::vector<nh_prof_rec> recs;
@@ -68,12 +62,12 @@ struct nh_ctx {
 // then run first and have its words zeroed under it afterwards (seen with three and more
 // processes on one GPU: a plan's `done` counter reset in the middle of a block of moves).
 static inline hipError_t nh_fill_now(nh_ctx* c, void* p, int byte, size_t n) {
-  hipError_t e = hipMemsetAsync(p, byte, n, c->main_stream);
-  return e == hipSuccess ? hipStreamSynchronize(c->main_stream) : e;
+  hipError_t e = hipMemsetAsync(p, byte, n, c->stream);
+  return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
 }
 static inline hipError_t nh_put_now(nh_ctx* c, void* dst, const void* src, size_t n) {
-  hipError_t e = hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, c->main_stream);
-  return e == hipSuccess ? hipStreamSynchronize(c->main_stream) : e;
+  hipError_t e = hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, c->stream);
+  return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
 }
 
 // device scratch of at least `bytes`; contents are only valid within one entry point

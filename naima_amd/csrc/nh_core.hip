@@ -49,14 +49,7 @@ extern "C" int nh_create(int device, nh_ctx** out) {
   c->clk = nullptr;
   memset(c->acc_ms, 0, sizeof(c->acc_ms));
   memset(c->acc_n, 0, sizeof(c->acc_n));
-  NH_CHECK_HIP(hipStreamCreateWithFlags(&c->main_stream, hipStreamNonBlocking));
-  c->stream = c->main_stream;
-  for (int i = 0; i < NH_NSIDE; ++i) {
-    NH_CHECK_HIP(hipStreamCreateWithFlags(&c->side[i], hipStreamNonBlocking));
-    NH_CHECK_HIP(hipEventCreateWithFlags(&c->ev_side[i], hipEventDisableTiming));
-    c->side_used[i] = false;
-  }
-  NH_CHECK_HIP(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+  NH_CHECK_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   NH_CHECK_HIP(hipEventCreate(&c->t0));
   NH_CHECK_HIP(hipEventCreate(&c->t1));
   NH_CHECK_HIP(hipMalloc(&c->nan_word, sizeof(int)));
@@ -104,16 +97,10 @@ extern "C" int nh_nan_count(nh_ctx* c, int reset, int* count) {
 extern "C" int nh_destroy(nh_ctx* c) {
   if (!c) return NH_OK;
   (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->main_stream);
+  (void)hipStreamSynchronize(c->stream);
   if (c->nan_word) (void)hipFree(c->nan_word);
   if (c->clk) (void)hipFree(c->clk);
   nh_comm_destroy(c);
-  for (int i = 0; i < NH_NSIDE; ++i) {
-    (void)hipStreamSynchronize(c->side[i]);
-    (void)hipStreamDestroy(c->side[i]);
-    (void)hipEventDestroy(c->ev_side[i]);
-  }
-  (void)hipEventDestroy(c->ev_fork);
   if (c->copy_stream) {
     (void)hipStreamSynchronize(c->copy_stream);
     (void)hipStreamDestroy(c->copy_stream);
@@ -123,7 +110,7 @@ extern "C" int nh_destroy(nh_ctx* c) {
   for (auto& e : c->pool) (void)hipEventDestroy(e);
   (void)hipEventDestroy(c->t0);
   (void)hipEventDestroy(c->t1);
-  (void)hipStreamDestroy(c->main_stream);
+  (void)hipStreamDestroy(c->stream);
   delete c;
   return NH_OK;
 }
@@ -131,11 +118,11 @@ extern "C" int nh_destroy(nh_ctx* c) {
 int nh_scratch(nh_ctx* c, size_t bytes, void** out) {
   if (bytes > c->scratch_bytes) {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(c->main_stream, &st);
+    (void)hipStreamIsCapturing(c->stream, &st);
     if (st != hipStreamCaptureStatusNone)
       return nh_set_error(NH_ENOMEM, "scratch must grow to %zu B during graph capture: run the "
                           "same call once eagerly first", bytes);
-    NH_CHECK_HIP(hipStreamSynchronize(c->main_stream));
+    NH_CHECK_HIP(hipStreamSynchronize(c->stream));
     if (c->scratch) NH_CHECK_HIP(hipFree(c->scratch));
     size_t want = bytes + bytes / 4;
     hipError_t e = hipMalloc(&c->scratch, want);
@@ -236,10 +223,8 @@ extern "C" int nh_stream_wait_marker(nh_ctx* c, void* marker) {
 
 extern "C" int nh_download(nh_ctx* c, void* dst, const void* src, long long bytes) {
   NH_REQUIRE(c && dst && src && bytes >= 0, "bad argument");
-  int rc = nh_stream_join(c);
-  if (rc) return rc;
-  NH_CHECK_HIP(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, c->main_stream));
-  NH_CHECK_HIP(hipStreamSynchronize(c->main_stream));
+  NH_CHECK_HIP(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
+  NH_CHECK_HIP(hipStreamSynchronize(c->stream));
   return NH_OK;
 }
 
@@ -251,65 +236,7 @@ extern "C" int nh_memset(nh_ctx* c, void* p, int byte, long long bytes) {
 
 extern "C" int nh_sync(nh_ctx* c) {
   NH_REQUIRE(c, "ctx is NULL");
-  int rc = nh_stream_join(c);
-  if (rc) return rc;
-  NH_CHECK_HIP(hipStreamSynchronize(c->main_stream));
-  return NH_OK;
-}
-
-// ---- fork / join over side streams (independent emission components of one model
-// evaluation run concurrently; under graph capture these become graph branches) ----
-extern "C" int nh_stream_fork(nh_ctx* c, int side) {
-  NH_REQUIRE(c && side >= 0 && side < NH_NSIDE, "bad side stream");
-  // the side stream starts after everything issued so far on the main stream
-  NH_CHECK_HIP(hipEventRecord(c->ev_fork, c->main_stream));
-  NH_CHECK_HIP(hipStreamWaitEvent(c->side[side], c->ev_fork, 0));
-  c->side_used[side] = true;
-  c->stream = c->side[side];
-  return NH_OK;
-}
-
-// the side stream starts after a marker recorded earlier on the main stream (the launch
-// that produced its inputs) instead of after everything issued so far: under capture the
-// branch hangs off that node only and runs beside whatever followed it
-extern "C" int nh_stream_fork_at(nh_ctx* c, int side, void* marker) {
-  NH_REQUIRE(c && side >= 0 && side < NH_NSIDE && marker, "bad argument");
-  NH_CHECK_HIP(hipStreamWaitEvent(c->side[side], reinterpret_cast<hipEvent_t>(marker), 0));
-  c->side_used[side] = true;
-  c->stream = c->side[side];
-  return NH_OK;
-}
-
-extern "C" int nh_stream_switch(nh_ctx* c, int side) {
-  NH_REQUIRE(c && side >= -1 && side < NH_NSIDE, "bad side stream");
-  c->stream = side < 0 ? c->main_stream : c->side[side];
-  return NH_OK;
-}
-
-extern "C" int nh_stream_wait(nh_ctx* c, int waiter, int producer) {
-  NH_REQUIRE(c && waiter >= -1 && waiter < NH_NSIDE && producer >= -1 && producer < NH_NSIDE,
-             "bad stream index");
-  if (waiter == producer) return NH_OK;
-  hipStream_t ws = waiter < 0 ? c->main_stream : c->side[waiter];
-  if (producer < 0) {
-    NH_CHECK_HIP(hipEventRecord(c->ev_fork, c->main_stream));
-    NH_CHECK_HIP(hipStreamWaitEvent(ws, c->ev_fork, 0));
-  } else {
-    NH_CHECK_HIP(hipEventRecord(c->ev_side[producer], c->side[producer]));
-    NH_CHECK_HIP(hipStreamWaitEvent(ws, c->ev_side[producer], 0));
-  }
-  return NH_OK;
-}
-
-extern "C" int nh_stream_join(nh_ctx* c) {
-  NH_REQUIRE(c, "ctx is NULL");
-  for (int i = 0; i < NH_NSIDE; ++i) {
-    if (!c->side_used[i]) continue;
-    NH_CHECK_HIP(hipEventRecord(c->ev_side[i], c->side[i]));
-    NH_CHECK_HIP(hipStreamWaitEvent(c->main_stream, c->ev_side[i], 0));
-    c->side_used[i] = false;
-  }
-  c->stream = c->main_stream;
+  NH_CHECK_HIP(hipStreamSynchronize(c->stream));
   return NH_OK;
 }
 

@@ -855,15 +855,6 @@ __global__ __launch_bounds__(1024) void k_half_step(const int* __restrict__ done
       if (it >= total) break;
       bool is_tab;
       int ix;
-#if HS_ORDER == 1
-      is_tab = it < nT;
-      ix = is_tab ? it : it - nT;
-      (void)both;
-#elif HS_ORDER == 2
-      is_tab = it >= nS;
-      ix = is_tab ? it - nS : it;
-      (void)both;
-#else
       if (it < F) {
         is_tab = true;
         ix = it;
@@ -874,7 +865,6 @@ __global__ __launch_bounds__(1024) void k_half_step(const int* __restrict__ done
         is_tab = nT - F > nS;
         ix = is_tab ? it - nS : it - nT;
       }
-#endif
 #ifdef HS_SKIP_TAB
       if (is_tab) { part_t[ix * 64 + lane] = 0.0; continue; }
 #endif
@@ -1499,31 +1489,17 @@ static int hs_create(nh_ctx* c, const nh_hs_desc* d, nh_halfstep_plan** out, int
     }
     const int free_waves = (threads / 64 - d->nmoms) * split;
     int per_tile = free_waves / tiles > 1 ? free_waves / tiles : 1;
-    per_tile *= nh_env_int("NH_HS_TAB_ROUNDS", 1);  // (tuning experiments: that many rounds of shorter items)
     seg = (maxseg + per_tile - 1) / per_tile;
     if (seg < 8) seg = 8;
   }
-  // NH_HS_GRADE=1: the last third of a table's segments in chunks of half the length
-  const bool grade = nh_env_int("NH_HS_GRADE", 0) != 0 && d->syn.grid >= 0;
-  auto chunking = [&](int nseg, int sg, int& nfull, int& seg2) {
-    nfull = (nseg + sg - 1) / sg;
-    seg2 = sg;
-    if (grade && sg >= 8) {
-      nfull = (2 * nseg / 3) / sg;
-      seg2 = sg / 2;
-    }
-    const int rest = nseg - nfull * sg;
-    return nfull + (rest > 0 ? (rest + seg2 - 1) / seg2 : 0);
-  };
+  auto chunking = [&](int nseg) { return (nseg + seg - 1) / seg; };
   for (;;) {
     int nT = 0;
     for (int t = 0; t < d->ntab; ++t) {
       const int tiles = (d->tab[t].nK + 63) / 64;
-      const int nseg = d->grids[d->tab[t].grid].nG - 1;
-      int nf, s2;
-      nT += tiles * chunking(nseg, seg, nf, s2);
+      nT += tiles * chunking(d->grids[d->tab[t].grid].nG - 1);
     }
-    if (nT <= (split > 1 ? 160 : (grade ? 128 : 96))) break;
+    if (nT <= (split > 1 ? 160 : 96)) break;
     seg *= 2;
   }
   C.seg = seg;
@@ -1544,10 +1520,9 @@ static int hs_create(nh_ctx* c, const nh_hs_desc* d, nh_halfstep_plan** out, int
       while (o.nKp / 2 >= tb.nK && o.nKp > 1) o.nKp /= 2;
       o.sub = 64 / o.nKp;
     }
-    int nfull = 0, seg2 = 0;
-    const int nchunks = chunking(nG - 1, seg, nfull, seg2);
-    NH_REQUIRE(nchunks < 256 && nfull < 256 && seg2 < 32768, "table cut into too many chunks");
-    o.chunks = nchunks | (nfull << 8) | (seg2 << 16);
+    const int nchunks = chunking(nG - 1);
+    NH_REQUIRE(nchunks < 256 && seg < 32768, "table cut into too many chunks");
+    o.chunks = nchunks | (nchunks << 8) | (seg << 16);  // (chunks | chunks of length seg | seg)
     o.item0 = nT;
     nT += o.tiles * nchunks;
     o.spec_off = nspec;

@@ -11,17 +11,14 @@
 #ifndef HS_SYN_NODES
 #define HS_SYN_NODES 10  // synchrotron nodes per thread and work item (besides the start node)
 #endif
-#ifndef HS_ORDER
-#define HS_ORDER 0  // work items: 0 = tables and synchrotron alternate, 1 = tables first, 2 = synchrotron first
-#endif
 
 struct hs_tab {
   const double* KD; const double* scale; double* out;  // KD: interleaved {K, dlnK}, [nG][nK][2]
   int grid, nK, ldo, nonneg, spec_off, tiles, item0, chunks;
   int sub, nKp;  // nK <= 32: sub = 64 / nKp sub-ranges of an item share a wave (nKp = 32, 16, ...)
   // `chunks` packs three numbers: chunks | nfull << 8 | seg2 << 16.  Chunks [0, nfull) hold `seg`
-  // segments each, the rest seg2 (<= seg): the items pulled last decide how far apart the waves
-  // reach the barrier, so they are the short ones.  (Packed into the existing word: a wider
+  // segments each, the rest seg2 (<= seg).  hs_create sets nfull = chunks and seg2 = seg: every
+  // chunk holds `seg` segments, the last one what is left.  (Packed into the existing word: a wider
   // struct made the compiler copy the whole by-value descriptor to scratch in k_half_step.)
 };
 #define HS_CHUNKS(pk) ((pk) & 0xff)

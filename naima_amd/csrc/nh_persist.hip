@@ -101,10 +101,7 @@ struct hs_run {
   // the loop's own copies of the plan's tables with their columns sorted (nh_hs.h; NULL: the
   // plan's table as it is)
   const double* kds[HS_MAX_TAB];
-  // order: 2 = synchrotron items (twice as long as table items) first, then the tables -- the
-  // items pulled last decide how far apart the waves reach the barrier (cfg3: 18.9 -> 18.6 us of
-  // items + wait); 0 = the two kinds alternate as in k_half_step
-  int spin_limit, order;
+  int spin_limit;
   // synchrotron nodes per thread and work item.  The plan's 10 suit a launch per half-step and
   // workgroups that share a walker; one resident workgroup per walker runs fastest on items
   // three times that long (cfg3, us per 40 half-steps: 1 015 at 10, 981 at 16, 975 at 24, 959
@@ -151,7 +148,6 @@ struct hs_run {
   int o_rs;   // LDS: this workgroup's nodes per grid and its units (rowsplit)
   int nxmax;  // doubles a workgroup hands over at most (spectrum + single-row reductions)
   int sum_cols;  // columns of all the tables together (the sum phase's loop bound)
-  int dbg_skip;  // -DNH_LAB builds only: NH_RUN_DEBUG_SKIP (experiments: instruction counts by kind): 1 no synchrotron items, 2 no table items
   // ---- an ensemble shared by several GPUs (nrank > 1; see "The ensemble across GPUs" below):
   // `ring` is this launch's ring in THIS rank's memory, peer[p] the same ring in rank p's
   // (peer[rank] == ring); a mover stores its walker's record into every one of them
@@ -1410,8 +1406,7 @@ __global__ __launch_bounds__(RT > 0 ? 512 : 1024) void k_half_step_run(const hs_
       // ---- C. work items: table reductions and synchrotron nodes, pulled from one counter -----
       {
         const int nT = D.nT;
-        const int F0 = min(nT, nwv);
-        const int both = 2 * min(nT - F0, nS), total = nT + nS;
+        const int total = nT + nS;
         double* part_t = sm + H.o_part_t;
         double* part_s = sm + H.o_part_s;
         bool rt_first = true;
@@ -1457,27 +1452,11 @@ __global__ __launch_bounds__(RT > 0 ? 512 : 1024) void k_half_step_run(const hs_
             if (item >= total) continue;
           }
           if (item >= total) break;
-          bool is_tab;
-          int ix;
-          if (R.order == 2) {
-            is_tab = item >= nS;
-            ix = is_tab ? item - nS : item;
-          } else if (item < F0) {
-            is_tab = true;
-            ix = item;
-          } else if (item - F0 < both) {
-            is_tab = ((item - F0) & 1) != 0;
-            ix = is_tab ? F0 + ((item - F0) >> 1) : (item - F0) >> 1;
-          } else {
-            is_tab = nT - F0 > nS;
-            ix = is_tab ? item - nS : item - nT;
-          }
-#ifdef NH_LAB  // (build.sh -DNH_LAB: instruction counts by kind of work item; every result is wrong)
-          if (R.dbg_skip && (is_tab ? (R.dbg_skip & 2) : (R.dbg_skip & 1))) {
-            if (is_tab) part_t[((K > 1 && R.tcompact) ? pulled : ix) * 64 + lane] = 0.0;
-            continue;
-          }
-#endif
+          // synchrotron items (twice as long as table items) first, then the tables: the items
+          // pulled last decide how far apart the waves reach the barrier (cfg3: 18.9 -> 18.6 us of
+          // items + wait against the two kinds alternating as in k_half_step)
+          const bool is_tab = item >= nS;
+          const int ix = is_tab ? item - nS : item;
           if (is_tab && RT == 0) {  // (the descriptor table is part of every such instance's layout)
             typedef int hsi_i4 __attribute__((ext_vector_type(4)));
             const int* ttab = reinterpret_cast<const int*>(sm + R.o_it);
@@ -2121,7 +2100,6 @@ static int hs_run_create(nh_ctx* c, nh_halfstep_plan* P, int rank, int nrank, nh
   }
   // ---- the table grids' 1 / lx in LDS, and the weights' units (below)
   for (int g = 0; g < NH_MAX_GRIDS; ++g) R.o_il[g] = -1;
-  R.order = nh_env_int("NH_RUN_ORDER", 2);
   R.rebalance = nh_env_int("NH_RUN_REBALANCE", H.syn_grid < 0 ? 1 : 0);
   const bool units_tab = grids_in_lds && nh_env_int("NH_RUN_UT", 1) != 0;
   // (the plan chose two workgroups per walker for a table-only model with one table: they halve
@@ -2138,7 +2116,7 @@ static int hs_run_create(nh_ctx* c, nh_halfstep_plan* P, int rank, int nrank, nh
   // summing it blindly measured faster than deciding per chunk whose it is -- cfg5 / 256 10.9
   // against 10.3 M walker-steps/s, cfg3 / 256 7.12 against 6.94; cfg3 / 128, four per walker: 3.95
   // against 4.07 the other way, and its log-domain synchrotron table fits LDS again)
-  R.tcompact = (P->split >= nh_env_int("NH_RUN_TCOMPACT_MIN", 4) && (R.rowsplit || R.order == 2)) ? 1 : 0;
+  R.tcompact = P->split >= nh_env_int("NH_RUN_TCOMPACT_MIN", 4) ? 1 : 0;
   int hole_lo = 0, hole_hi = 0;
   if (R.tcompact) {
     int nsmax = 0;  // synchrotron items of a slice at most
@@ -2298,15 +2276,7 @@ static int hs_run_create(nh_ctx* c, nh_halfstep_plan* P, int rank, int nrank, nh
   // walker: 20.8 at 10, 20.8 at 16, 20.0 at 24; cfg2 / 256: 17.7 at 10 and at 16, 18.3 at 24)
   if (R.syn2 && P->split >= 2 && R.syn_nodes < 16) R.syn_nodes = 16;
   R.syn_nodes = nh_env_int("NH_RUN_SYN_NODES", R.syn_nodes);
-#ifdef NH_LAB
-  R.dbg_skip = nh_env_int("NH_RUN_DEBUG_SKIP", 0);
-#else
-  R.dbg_skip = 0;  // (the product build has no switch that drops work: -DNH_LAB, scripts/lab/r4_count.sh)
-#endif
   R.pipeline = nh_env_int("NH_RUN_PIPELINE", 1);
-  if (R.dbg_skip != 0)
-    fprintf(stderr, "libnaima_hip: NH_RUN_DEBUG_SKIP=%d -- work items are DROPPED from the likelihood "
-                    "(instruction-count experiments): every result of this loop is wrong\n", R.dbg_skip);
   if (nh_env_int("NH_RUN_FAIL_AT", 0) > 0)
     fprintf(stderr, "libnaima_hip: NH_RUN_FAIL_AT=%d -- that launch of the resident loop is made to time "
                     "out (fault injection of the tests)\n", nh_env_int("NH_RUN_FAIL_AT", 0));

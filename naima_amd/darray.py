@@ -152,14 +152,12 @@ class DVec:
         """a contiguous device vector holding the values (one tiny launch unless plain)"""
         if self.is_plain():
             return self
-        self.ctx.need(self.owner)
         out = self.ctx.empty((self.n,))
         cols = (nh_lazy * 1)(self.lazy())
         self.ctx.call("nh_pack_rows", cols, 1, self.n, out, 1)
         return DVec(self.ctx, out, out.ptr, self.n)
 
     def get(self):
-        self.ctx.join()
         d = self.dense()
         host = np.empty(self.n)
         _lib._chk(_lib._lib.nh_download(self.ctx.h, host.ctypes.data, d.ptr, host.nbytes))
@@ -204,7 +202,6 @@ class DVec:
             keep = (self.owner, dev)
         if reverse:
             x, y = y, x
-        self.ctx.need(*keep)
         out = self.ctx.empty((self.n,))
         self.ctx.call("nh_ew_binary", OPS[op], C.byref(x), C.byref(y), self.n, out)
         del keep
@@ -420,7 +417,6 @@ class DMat:
         import ctypes as C
         self.ctx.flush(*[t[0] for t in self.terms])
         N, m = self.shape
-        self.ctx.need(*[t[0] for t in self.terms])
         out = self.ctx.empty((N, m))
         cf = self.ctx.const(self.colfac) if self.colfac is not None else None
         lz = rf.lazy()
@@ -435,7 +431,6 @@ class DMat:
         if len(self.terms) == 1 and self.colfac is None and self.terms[0][3] == 1.0 \
                 and self.terms[0][2] == m:
             return self
-        self.ctx.need(*[t[0] for t in self.terms])
         out = self.ctx.empty((N, m))
         cf = self.ctx.const(self.colfac) if self.colfac is not None else None
         self.ctx.call("nh_lincomb", self.comps(), len(self.terms), cf, None, N, m, out, m)
@@ -446,7 +441,6 @@ class DMat:
         return d.terms[0][0], d.terms[0][1]
 
     def get(self):
-        self.ctx.join()
         d = self.dense()
         host = np.empty(self.shape)
         _lib._chk(_lib._lib.nh_download(self.ctx.h, host.ctypes.data, d.terms[0][1], host.nbytes))

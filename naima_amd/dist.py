@@ -316,7 +316,6 @@ class HostComm:
     def allgather_device(self, ctx, send_ptr, recv, n):
         from . import _lib
         host = np.empty(n)
-        ctx.join()
         _lib._chk(_lib._lib.nh_download(ctx.h, host.ctypes.data, send_ptr, host.nbytes))
         recv.set(self.allgather(host))
 

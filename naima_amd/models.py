@@ -98,7 +98,6 @@ class _ParticleDistribution:
         key = (N, None if amplitude_to is None else amplitude_to.name)
         hit = cache.get(key)
         if hit is not None:
-            ctx.need(hit)  # packed on another side stream of this evaluation
             return hit
         cols = (nh_lazy * NH_PD_NPAR)()
         for j in range(NH_PD_NPAR):
@@ -131,7 +130,6 @@ class _ParticleDistribution:
                 dev = ctx.array(np.broadcast_to(np.asarray(v, dtype=float), (N,)))
                 cols[slot] = nh_lazy(dev.ptr, 1, 1.0, 1.0, 0.0, 0, 0)
                 keep.append(dev)
-        ctx.need(*[getattr(k, "owner", k) for k in keep])
         out = ctx.pack_rows(cols, NH_PD_NPAR, N)
         cache[key] = out
         return out

@@ -253,15 +253,9 @@ class BaseRadiative:
                                      [reg[k][1:3][::-1] + reg[k][3:5] + (k[2], k[3]) for k in todo])
             for k, wl in zip(todo, bufs):
                 cache[k] = wl
-            if self.on_device and ctx.side_small:
-                # We/Wp reductions hang a side stream off this launch (ctx.branch_at)
-                mark = ctx.anchor()
-                for k in todo:
-                    cache[k][0].anchor = mark
             hit = cache[key]
         else:
             reg[key] = (ctx._weval, xd, ed, ctx.grid_ln(ed, e_eV), lx)
-        ctx.need(hit[0])
         return ctx, N, hit[0], hit[1], xd, lx
 
     def _weights_table(self, pd, xg, e_eV, unit_scale):
@@ -305,21 +299,9 @@ class BaseRadiative:
         return ctx, N, hit[0], hit[1], xd, lx
 
     # -- public ---------------------------------------------------------------
-    def _spectrum_branch(self, photon_energy):
-        """``_spectrum`` on its own side stream when the values stay on the device:
-        the emission components of a model evaluation are independent of each
-        other, so their launch sequences run concurrently (graph branches)"""
-        if self.on_device:
-            ctx = get_context()
-            self._prefork(ctx)
-            with ctx.branch():
-                return self._spectrum(photon_energy)
-        return self._spectrum(photon_energy)
-
-    def _prefork(self, ctx):
-        """launch what several components share (the packed parameter rows) on the
-        MAIN stream before forking, so that a side stream never has to wait for
-        another side stream's whole queue"""
+    def _launch_shared_inputs(self, ctx):
+        """launch what several components share (the packed parameter rows) ahead of
+        the spectrum of a device evaluation"""
         pd = self.particle_distribution
         if hasattr(pd, "device_rows"):
             pd.device_rows(ctx, self.batch_size, amplitude_to=_PER_EV)
@@ -329,7 +311,9 @@ class BaseRadiative:
         differential luminosity (radiative.py:88-111)."""
         if self._needs_walker_loop():
             return self._loop_walkers("flux", photon_energy, distance=distance)
-        spec = self._spectrum_branch(photon_energy)
+        if self.on_device:
+            self._launch_shared_inputs(get_context())
+        spec = self._spectrum(photon_energy)
         if not _dist_is_zero(distance):
             distance = validate_scalar("distance", distance, physical_type="length")
             spec = spec / (4 * np.pi * distance.to("cm") ** 2)
@@ -528,19 +512,6 @@ class BaseElectron(BaseRadiative):
         return n if self.is_batched else n[0]
 
     def _We_on(self, gam):
-        ctx = get_context()
-        if self.on_device and ctx.multistream:
-            self._prefork(ctx)
-            with ctx.branch():
-                return self._We_on_impl(gam)
-        if self.on_device:
-            # the weights on the main stream, the small reduction beside what follows them
-            w = self._electron_weights(gam)[2]
-            with ctx.branch_at(getattr(w, "anchor", None)):
-                return self._We_on_impl(gam)
-        return self._We_on_impl(gam)
-
-    def _We_on_impl(self, gam):
         ctx, N, w, lw, xd, lx, gam = self._electron_weights(gam)
         K = gam * MEC2_ERG  # u = x*y = (gam mec2)(gam nelec)
         Kt, dlnKt = ctx.const(K), ctx.const(_dlog(K))
@@ -643,8 +614,8 @@ class Synchrotron(BaseElectron):
     def _own_device_values(self):
         return (self.B,)
 
-    def _prefork(self, ctx):
-        super()._prefork(ctx)
+    def _launch_shared_inputs(self, ctx):
+        super()._launch_shared_inputs(ctx)
         Bv = self.B.to("G").value
         if isinstance(Bv, DVec) and self.__dict__.get("_B_dense") is None \
                 and not self._B_in_rows(Bv):
@@ -1259,18 +1230,6 @@ class BaseProton(BaseRadiative):
         return J if self.is_batched else J[0]
 
     def _Wp_on(self, Ep):
-        ctx = get_context()
-        if self.on_device and ctx.multistream:
-            self._prefork(ctx)
-            with ctx.branch():
-                return self._Wp_on_impl(Ep)
-        if self.on_device:
-            w = self._proton_weights(Ep)[2]
-            with ctx.branch_at(getattr(w, "anchor", None)):
-                return self._Wp_on_impl(Ep)
-        return self._Wp_on_impl(Ep)
-
-    def _Wp_on_impl(self, Ep):
         ctx, N, w, lw, xd, lx, Ep = self._proton_weights(Ep)
         Kt, dlnKt = ctx.const(Ep), ctx.const(_dlog(Ep))
         out = ctx.moment(w, lw, N, Ep.size, lx, Kt, dlnKt)

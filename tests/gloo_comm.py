@@ -37,6 +37,5 @@ class GlooComm:
     def allgather_device(self, ctx, send_ptr, recv, n):
         from naima_amd import _lib
         host = np.empty(n)
-        ctx.join()
         _lib._chk(_lib._lib.nh_download(ctx.h, host.ctypes.data, send_ptr, host.nbytes))
         recv.set(self.allgather(host))
