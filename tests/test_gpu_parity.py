@@ -230,6 +230,21 @@ def test_lnprobmodel_and_priors(na, golden):
     assert_allclose(na.log_uniform_prior(2.0, 1.0, 3.0), U["prior_logu"][0])
 
 
+def test_lnprobmodel_confidence_level_indexed_by_violations(na, golden):
+    """lnprob.npz: asymmetric errors, five upper limits, a distinct cl per point, models violating
+    0 .. 4 of them -- the likelihood kernel against the reference, batched and one row at a time"""
+    u = na.u
+    z = golden("lnprob")
+    fu = u.Unit("1/(cm2 s TeV)")
+    d = dict(energy=z["energy_TeV"] * u.TeV, flux=z["flux"] * fu,
+             flux_error_lo=z["flux_error_lo"] * fu, flux_error_hi=z["flux_error_hi"] * fu,
+             ul=z["ul"], cl=z["cl"])
+    models = z["models"] * fu
+    assert_allclose(na.lnprobmodel(models, d), z["lnprobmodel"], rtol=1e-12)
+    for i in (1, 4):
+        assert_allclose(na.lnprobmodel(models[i], d), z["lnprobmodel"][i], rtol=1e-12)
+
+
 def _data_from_npz(na, z, prefix="data_"):
     from naima_amd.datatable import make_data
     return make_data({k: z[prefix + k] for k in ("energy", "energy_unit", "flux", "flux_error_lo",

@@ -150,6 +150,20 @@ def test_lnprobmodel_and_priors(golden):
     assert O.uniform_prior(1.0, 0.0, 2.0) == 0.0 and O.uniform_prior(3.0, 0.0, 2.0) == -np.inf
 
 
+def test_lnprobmodel_confidence_level_indexed_by_violations(golden):
+    """lnprob.npz (gen_golden_lnprob.py): asymmetric errors, five upper limits, a distinct cl per
+    point and models violating 0 .. 4 of them -- the reference's cl[nviol] (core.py:89-92) pinned
+    to a value; cl[nviol - 1], or lo / hi swapped, would miss it by far more than the tolerance"""
+    z = golden("lnprob")
+    d = dict(flux=z["flux"], flux_error_lo=z["flux_error_lo"], flux_error_hi=z["flux_error_hi"],
+             ul=z["ul"], cl=z["cl"])
+    assert not np.array_equal(d["flux_error_lo"], d["flux_error_hi"])
+    assert sorted(set(z["nviol"].tolist())) == [0, 1, 2, 3, 4]
+    for m, k, ref in zip(z["models"], z["nviol"], z["lnprobmodel"]):
+        assert int(np.sum(m[z["ul"]] > z["flux"][z["ul"]])) == k
+        assert_allclose(O.lnprobmodel(m, d), ref, rtol=1e-13)
+
+
 @pytest.mark.parametrize("name", ["cfg1", "cfg2", "cfg3", "cfg4", "cfg5"])
 def test_workloads(golden, name):
     z = golden(name)
