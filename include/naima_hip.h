@@ -751,6 +751,19 @@ int nh_comm_info(nh_ctx* ctx, int* nranks, int* rank, int* device);
 /* recv[r*count .. (r+1)*count) = send of rank r (device buffers, float64 count) */
 int nh_comm_allgather(nh_ctx* ctx, const double* send, double* recv, long long count);
 
+/* ---- posterior bands: exact per-column order statistics (plot.py:438-501) -------------------
+ * out[r][c] = np.sort(x[0:M, c])[ranks[r]] for c < ncol, r < R: the confidence bands of naima's
+ * _calc_CI (np.sort(model[:, i])[nf] per energy i) over the samples of a chain's blobs or of model
+ * evaluations at drawn parameters.  x is a row-major DEVICE matrix [M][ld] (samples x energies,
+ * the layout of stored blobs and of a dense model output), ranks a HOST array of R <= 16 ranks in
+ * [0, M), out a device [R][ncol].  Exact (an MSD radix select on order-preserving 64-bit keys,
+ * integer atomics only); NaNs rank after +inf as in NumPy, -0.0 and +0.0 as equals.  Stream-ordered
+ * on the context's stream, no host synchronisation; library scratch of 8*M*ncol bytes + a little.
+ * NH_EINVAL: M == 0, M >= 2^31, ncol > ld, R outside [1, 16] or a rank outside [0, M). */
+#define NH_SELECT_MAX_RANKS 16
+int nh_column_select(nh_ctx* ctx, const double* x, long long M, int ncol, long long ld,
+                     const int* ranks /*host*/, int R, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@ import numpy as np
 from . import units as u
 from .datatable import DataTable
 
-__all__ = ["save_run", "read_run", "save_results_table", "find_ML"]
+__all__ = ["save_run", "read_run", "save_results_table", "find_ML", "save_diagnostic_plots"]
 
 
 def _unit_string(unit):
@@ -210,8 +210,10 @@ def _table_from(table, meta_lines):
     return data
 
 
-def read_run(filename):
-    """Read a run saved by ``save_run`` (either container)."""
+def read_run(filename, modelfn=None):
+    """Read a run saved by ``save_run`` (either container).  ``modelfn``, the run's model
+    function, is attached to the result as ``modelfn`` (analysis.py:497-530) so that the plots
+    can recompute the model on an ``e_range`` grid."""
     if filename.endswith((".h5", ".hdf5")):
         import h5py
         with h5py.File(filename, "r") as f:
@@ -243,8 +245,10 @@ def read_run(filename):
         i += 1
     run_info = {k: v for k, v in attrs.items()
                 if not k.startswith("label") and k != "acceptance_fraction"}
-    return _Result(chain, log_prob, blobs, units, data, labels, run_info,
-                   attrs.get("acceptance_fraction"))
+    res = _Result(chain, log_prob, blobs, units, data, labels, run_info,
+                  attrs.get("acceptance_fraction"))
+    res.modelfn = modelfn
+    return res
 
 
 def find_ML(sampler):
@@ -255,6 +259,69 @@ def find_ML(sampler):
     chain = np.asarray(sampler.get_chain())
     idx = np.unravel_index(np.argmax(lp), lp.shape)
     return float(lp[idx]), chain[idx]
+
+
+def save_diagnostic_plots(outname, sampler, modelidxs=None, pdf=False, sed=True, blob_labels=None,
+                          last_step=False, dpi=100):
+    """Diagnostic figures of a run (analysis.py:29-162 of the reference): the chain and posterior
+    of every parameter (``<outname>_chain_<label>.png``, log prefixes stripped), the corner plot
+    when the corner package is installed (``<outname>_corner.png``) and every model blob
+    (``<outname>_model<i>.png``: a spectrum with 100 sample models, the ML model, data and
+    residuals; a scalar as its distribution).  ``pdf=True``: all of them as the pages of
+    ``<outname>_plots.pdf`` instead.  Collective on a sampler that spans several ranks."""
+    import warnings
+
+    from matplotlib import pyplot as plt
+
+    from .plot import plot_blob, plot_chain, plot_corner
+    old_interactive = plt.rcParams["interactive"]
+    plt.rcParams["interactive"] = False
+    outpdf = None
+    if pdf:
+        from matplotlib.backends.backend_pdf import PdfPages
+        plt.rc("pdf", fonttype=42)
+        outpdf = PdfPages("{0}_plots.pdf".format(outname))
+
+    def save(f, png):
+        if outpdf is not None:
+            f.savefig(outpdf, format="pdf", dpi=dpi)
+        else:
+            f.savefig(png, dpi=dpi)
+        f.clf()
+        plt.close(f)
+
+    try:
+        for par, label in enumerate(sampler.labels):
+            try:
+                f = plot_chain(sampler, par, last_step=last_step)
+                if "log(" in label or "log10(" in label:
+                    label = label.split("(")[-1].split(")")[0]
+                save(f, "{0}_chain_{1}.png".format(outname, label))
+            except Exception as e:
+                warnings.warn("plot_chain failed for parameter {0} ({1}): {2}".format(label, par, e))
+        f = plot_corner(sampler)
+        if f is not None:
+            save(f, "{0}_corner.png".format(outname))
+        if modelidxs is None:
+            modelidxs = list(range(len(sampler.get_blobs() or [])))
+        sed = [sed] * len(modelidxs) if isinstance(sed, bool) else list(sed)
+        if blob_labels is None:
+            blob_labels = []
+        elif isinstance(blob_labels, str):
+            blob_labels = [blob_labels]
+        blob_labels = list(blob_labels) + ["Model output {0}".format(i)
+                                           for i in modelidxs[len(blob_labels):]]
+        for modelidx, plot_sed, label in zip(modelidxs, sed, blob_labels):
+            try:
+                f = plot_blob(sampler, blobidx=modelidx, label=label, sed=plot_sed, n_samples=100,
+                              last_step=last_step)
+                save(f, "{0}_model{1}.png".format(outname, modelidx))
+            except Exception as e:
+                warnings.warn("plot_blob failed for {0}: {1}".format(label, e))
+    finally:
+        if outpdf is not None:
+            outpdf.close()
+        plt.rcParams["interactive"] = old_interactive
 
 
 def save_results_table(outname, sampler, convert_log=True, last_step=False, include_blobs=True,
