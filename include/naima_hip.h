@@ -764,6 +764,27 @@ int nh_comm_allgather(nh_ctx* ctx, const double* send, double* recv, long long c
 int nh_column_select(nh_ctx* ctx, const double* x, long long M, int ncol, long long ld,
                      const int* ranks /*host*/, int R, double* out);
 
+/* ---- integrated autocorrelation time (emcee.autocorr.integrated_time) ----------------------
+ * The walker-averaged normalised autocorrelation function of one dimension of a chain, emcee's
+ * function_1d of every walker's series averaged over the walkers; the window search and the
+ * tolerance check stay on the host.  Deterministic (no floating-point atomics: the order of every
+ * sum is fixed by the shapes), 64-bit indices, stream-ordered on the context's stream, no host
+ * synchronisation; library scratch of a few MiB at most.
+ * nh_autocorr_prep: x is a row-major DEVICE matrix [n_t][n_w*n_d] (get_chain's layout: column
+ *   w*n_d + d is walker w's series of dimension d).  Writes the centred series of dimension d,
+ *   z[w][t] = x[t][w*n_d+d] - mean_t, into the device matrix z [n_w][n_t] (contiguous in t) and
+ *   s2[w] = sum_t z[w][t]^2 into the device array s2 [n_w].  A series whose values are all equal
+ *   gets z = 0 and s2 = 0 exactly; a non-finite value makes its s2 non-finite.
+ *   NH_EINVAL: n_t, n_w or n_d not positive, d outside [0, n_d).
+ * nh_autocorr_lags: f[k] = (1/n_w) sum_w (sum_{t < n_t-tau} z[w][t] z[w][t+tau]) / s2[w] for
+ *   tau = lag0 + k, k < nlags, from nh_autocorr_prep's z and s2 (every s2[w] positive and finite:
+ *   the host leaves a dimension with a zero or non-finite one out, as NaN); f is a device [nlags].
+ *   NH_EINVAL: n_t, n_w or nlags not positive, lags outside [0, n_t). */
+int nh_autocorr_prep(nh_ctx* ctx, const double* x, long long n_t, int n_w, int n_d, int d,
+                     double* z, double* s2);
+int nh_autocorr_lags(nh_ctx* ctx, const double* z, const double* s2, long long n_t, int n_w,
+                     long long lag0, int nlags, double* f);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,6 +151,8 @@ _SIGS = {
     "nh_set_words": [_dp, _dp, _dp, _i],
     "nh_half_step_append_blobs": [_dp, _dp, _ll],
     "nh_column_select": [_dp, _dp, _ll, _i, _ll, C.POINTER(_i), _i, _dp],
+    "nh_autocorr_prep": [_dp, _dp, _ll, _i, _i, _i, _dp, _dp],
+    "nh_autocorr_lags": [_dp, _dp, _dp, _ll, _i, _ll, _i, _dp],
 }
 EXPORTS = tuple(_SIGS) + ("nh_last_error", "nh_version", "nh_ssc_table_bytes")
 

@@ -1,0 +1,169 @@
+"""emcee's ``emcee.autocorr`` surface: the integrated autocorrelation time of a chain, with the
+autocorrelation function computed on the GPU.
+
+Per dimension the device returns the walker-averaged normalised autocorrelation function
+(``nh_autocorr_prep`` / ``nh_autocorr_lags``: emcee's ``function_1d`` of every walker's series,
+averaged over the walkers; direct lag sums, which equal the zero-padded FFT's linear correlation).
+The host takes emcee's cumulative sum and window search on it.  Lags are computed in blocks, 256
+and then doubling, only until a dimension's window is certain; a dimension with a constant walker
+or a non-finite value is NaN (emcee's 0/0) without any lag work.
+
+Importing this module creates no GPU context; argument errors come before any device work.
+"""
+import logging
+
+import numpy as np
+
+__all__ = ["function_1d", "integrated_time", "AutocorrError", "auto_window"]
+
+logger = logging.getLogger("naima_amd.autocorr")
+
+_FIRST_BLOCK = 256
+
+
+class AutocorrError(Exception):
+    """Raised when the chain is too short to give a reliable autocorrelation time; ``.tau``
+    holds the estimate anyway."""
+
+    def __init__(self, tau, *args, **kwargs):
+        self.tau = tau
+        super(AutocorrError, self).__init__(*args, **kwargs)
+
+
+def auto_window(taus, c):
+    """emcee's window: the first lag ``m`` with ``m >= c * taus[m]`` (Sokal 1989)"""
+    m = np.arange(len(taus)) < c * taus
+    if np.any(m):
+        return np.argmin(m)
+    return len(taus) - 1
+
+
+def _device_chain(x):
+    """(ctx, device [n_t][n_w*n_d] copy of the host chain x [n_t][n_w][n_d])"""
+    from . import _lib
+    ctx = _lib.get_context()
+    n_t, n_w, n_d = x.shape
+    return ctx, ctx.array(np.ascontiguousarray(x, dtype=np.float64).reshape(n_t, n_w * n_d))
+
+
+def _prep(ctx, dx, shape, d):
+    """centre dimension d's series on the device: (z, s2, ok); ok is False when a walker's series
+    is constant or holds a non-finite value (the dimension is NaN then)"""
+    n_t, n_w, n_d = shape
+    z, s2 = ctx.empty((n_w, n_t)), ctx.empty((n_w,))
+    ctx.call("nh_autocorr_prep", dx, n_t, n_w, n_d, d, z, s2)
+    v = s2.get()
+    return z, s2, bool(np.all(np.isfinite(v) & (v > 0)))
+
+
+def _lags(ctx, z, s2, n_t, n_w, lag0, nlags):
+    f = ctx.empty((nlags,))
+    ctx.call("nh_autocorr_lags", z, s2, n_t, n_w, lag0, nlags, f)
+    return f.get()
+
+
+def _window_done(taus, c):
+    """the window is certain from the lags so far: some lag m > 0 has m >= c * taus[m] while
+    lag 0 has 0 < c * taus[0] (then auto_window returns the first such m whatever comes later)"""
+    m = np.arange(len(taus)) < c * taus
+    return bool(m[0]) and not bool(np.all(m))
+
+
+def _dimension(ctx, dx, shape, d, c):
+    """(tau, window, f) of dimension d; f holds the lags computed, NaN-filled for a NaN dimension"""
+    n_t, n_w, _ = shape
+    z, s2, ok = _prep(ctx, dx, shape, d)
+    if not ok:
+        return np.nan, n_t - 1, np.full(1, np.nan)
+    f = np.empty(0)
+    block = _FIRST_BLOCK
+    while True:
+        nl = min(block, n_t - f.size)
+        f = np.concatenate([f, _lags(ctx, z, s2, n_t, n_w, f.size, nl)])
+        taus = 2.0 * np.cumsum(f) - 1.0
+        if f.size == n_t or _window_done(taus, c):
+            w = auto_window(taus, c)
+            return taus[w], w, f
+        block *= 2
+
+
+def _as3d(x, has_walkers):
+    x = np.atleast_1d(x)
+    if len(x.shape) == 1:
+        x = x[:, np.newaxis, np.newaxis]
+    if len(x.shape) == 2:
+        if not has_walkers:
+            x = x[:, np.newaxis, :]
+        else:
+            x = x[:, :, np.newaxis]
+    if len(x.shape) != 3:
+        raise ValueError("invalid dimensions")
+    if x.shape[0] == 0:
+        raise ValueError("the chain has no steps")
+    if x.shape[1] == 0 or x.shape[2] == 0:
+        raise ValueError("the chain has no walkers or no parameters")
+    return x
+
+
+def _integrated(x, c=5, has_walkers=True):
+    """(tau [n_d], windows [n_d], [f of each dimension], n_t) without the tolerance check"""
+    x = _as3d(x, has_walkers)
+    ctx, dx = _device_chain(x)
+    out = [_dimension(ctx, dx, x.shape, d, c) for d in range(x.shape[2])]
+    tau = np.array([o[0] for o in out], dtype=float)
+    windows = np.array([o[1] for o in out], dtype=int)
+    return tau, windows, [o[2] for o in out], x.shape[0]
+
+
+def function_1d(x):
+    """The normalised autocorrelation function of one series, every lag (emcee's
+    ``function_1d``); NaN throughout for a constant or non-finite series."""
+    x = np.atleast_1d(x)
+    if len(x.shape) != 1:
+        raise ValueError("invalid dimensions for 1D autocorrelation function")
+    n_t = x.shape[0]
+    if n_t == 0:
+        raise ValueError("the series is empty")
+    x3 = x[:, np.newaxis, np.newaxis]
+    ctx, dx = _device_chain(x3)
+    z, s2, ok = _prep(ctx, dx, x3.shape, 0)
+    if not ok:
+        return np.full(n_t, np.nan)
+    return _lags(ctx, z, s2, n_t, 1, 0, n_t)
+
+
+def integrated_time(x, c=5, tol=50, quiet=False, has_walkers=True):
+    """Estimate the integrated autocorrelation time of a time series (emcee 3's
+    ``emcee.autocorr.integrated_time``).
+
+    Args:
+        x: the series, ``(n_t, n_walkers, n_dim)`` (``get_chain()``); a 1-D array is one series,
+            a 2-D one ``(n_t, n_walkers)``, or ``(n_t, n_dim)`` with ``has_walkers=False``.
+        c (float): the step size for the window search (default 5).
+        tol (float): the minimum number of autocorrelation times needed to trust the estimate
+            (default 50).
+        quiet (bool): log a warning instead of raising ``AutocorrError`` when the chain is too
+            short.
+        has_walkers (bool): whether the second axis of a 2-D ``x`` is the walkers.
+
+    Returns:
+        float array ``[n_dim]``: the autocorrelation time of each parameter; NaN for a parameter
+        with a constant walker or a non-finite value.
+
+    Raises:
+        AutocorrError: if the chain is shorter than ``tol`` times the autocorrelation time of a
+            parameter (and ``quiet`` is False).
+    """
+    tau_est, _, _, n_t = _integrated(x, c, has_walkers)
+    flag = tol * tau_est > n_t
+    if np.any(flag):
+        msg = (
+            "The chain is shorter than {0} times the integrated "
+            "autocorrelation time for {1} parameter(s). Use this estimate "
+            "with caution and run a longer chain!\n"
+        ).format(tol, np.sum(flag))
+        msg += "N/{0} = {1:.0f};\ntau: {2}".format(tol, n_t / tol, tau_est)
+        if not quiet:
+            raise AutocorrError(tau_est, msg)
+        logger.warning(msg)
+    return tau_est

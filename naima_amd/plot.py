@@ -362,14 +362,16 @@ def _posterior_hist(ax, dist, label, title):
     return tuple(q)
 
 
-def _chain_text(sampler, label, dist, shape, last_step):
-    """the summary printed beside a chain plot: run size, acceptance, and the posterior's
-    median with 16/84 % errors (de-logged too for a log10( ) / log( ) label).  No
-    autocorrelation time: emcee's estimator is not available here, and naima leaves that line
-    out whenever it cannot give one."""
+def _chain_text(sampler, label, dist, shape, last_step, tau=None):
+    """the summary printed beside a chain plot: run size, the parameter's integrated
+    autocorrelation time ``tau`` (left out when None: naima leaves it out for a chain too short to
+    estimate it), acceptance, and the posterior's median with 16/84 % errors (de-logged too for a
+    log10( ) / log( ) label)."""
     q16, q50, q84 = np.percentile(dist, [16, 50, 84])
-    lines = ["Walkers: %d" % shape[0], "Steps in chain: %d" % shape[1],
-             "Mean acceptance fraction: %.3f" % np.mean(sampler.acceptance_fraction),
+    lines = ["Walkers: %d" % shape[0], "Steps in chain: %d" % shape[1]]
+    if tau is not None:
+        lines.append("Autocorrelation time: %.1f" % tau)
+    lines += ["Mean acceptance fraction: %.3f" % np.mean(sampler.acceptance_fraction),
              "Distribution properties for the %s:" % ("last ensemble" if last_step
                                                       else "whole chain"),
              "    $-$ median: $%s$, std: $%s$" % (_tex_number(q50), _tex_number(np.std(dist))),
@@ -387,7 +389,13 @@ def _chain_text(sampler, label, dist, shape, last_step):
 def _plot_chain_func(sampler, p, last_step=False):
     """one parameter: walker traces (top left), posterior (right), summary (bottom left)"""
     import matplotlib.pyplot as plt
-    traces = np.asarray(sampler.get_chain())[:, :, p].T  # (walker, step)
+    from .autocorr import AutocorrError, integrated_time
+    chain = np.asarray(sampler.get_chain())
+    traces = chain[:, :, p].T  # (walker, step)
+    try:  # (plot.py:202-209: on the chain, so that read_run results get the line too)
+        tau = integrated_time(chain)[p]
+    except AutocorrError:  # too short a chain for a meaningful estimate
+        tau = None
     label = sampler.labels[p]
     dist = traces[:, -1] if last_step else traces.ravel()
     fig = plt.figure()
@@ -402,7 +410,7 @@ def _plot_chain_func(sampler, p, last_step=False):
                    color=color_cycle[0] if hi else "0.1", rasterized=not hi)
     ax_tr.set(xlabel="step number", ylabel=label, title="Walker traces")
     _posterior_hist(ax_post, dist, label, "posterior distribution")
-    fig.text(0.05, 0.45, _chain_text(sampler, label, dist, traces.shape, last_step),
+    fig.text(0.05, 0.45, _chain_text(sampler, label, dist, traces.shape, last_step, tau),
              ha="left", va="top")
     return fig
 

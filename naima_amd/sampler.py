@@ -152,6 +152,17 @@ class EnsembleSampler:
             out.append(a.reshape((-1,) + a.shape[2:]) if flat else a)
         return out
 
+    def get_autocorr_time(self, discard=0, thin=1, **kwargs):
+        """emcee's estimate of the integrated autocorrelation time of each parameter:
+        ``thin * integrated_time(self.get_chain(discard=discard, thin=thin), **kwargs)``, the
+        autocorrelation function computed on the GPU (naima_amd.autocorr).  ``kwargs`` are
+        integrated_time's (``c``, ``tol``, ``quiet``); a chain shorter than ``tol`` times the
+        estimate raises ``autocorr.AutocorrError`` unless ``quiet=True``.  With several ranks this
+        is a COLLECTIVE call, as ``get_chain`` is: every rank makes it, or none does."""
+        from .autocorr import integrated_time
+        x = self.get_chain(discard=discard, thin=thin)
+        return thin * integrated_time(x, **kwargs)
+
     # legacy emcee-2 names that naima's analysis code touches
     @property
     def chain(self):
