@@ -785,6 +785,30 @@ int nh_autocorr_prep(nh_ctx* ctx, const double* x, long long n_t, int n_w, int n
 int nh_autocorr_lags(nh_ctx* ctx, const double* z, const double* s2, long long n_t, int n_w,
                      long long lag0, int nlags, double* f);
 
+/* ---- EBL absorption with a per-walker redshift (models.py:470-552) ------------------------
+ * The reference picks the nearest of the tabulated redshifts zl = arange(0.01, 4, 0.01)
+ * (models.py:520-528, no interpolation in z), clips log tau at 150 (models.py:529-531) and
+ * interpolates log10(tau) in log10(E) with interp1d(kind="cubic") (models.py:445-466).  At fixed energies
+ * the transmission is therefore a walker-independent table Tab[ncol+1][nE]: row 0 is z < 0.01
+ * (models.py:532-536), row c+1 is column c.  Deterministic, no atomics, no scratch.
+ * nh_ebl_table: knots[nt] and coef[nt-4][ncol] (DEVICE) are the cubic B-spline of every column
+ *   (scipy make_interp_spline, k = 3); x[nE] = log10(E/eV) and code[nE] (DEVICE) the host's
+ *   per-energy decisions: code & 3 = NH_EBL_ONE below 1 GeV (transmission 1), NH_EBL_HIGH
+ *   above 100 TeV (transmission t_hi = exp(-log10(6000))), models.py:542-552;
+ *   code & NH_EBL_OUTSIDE: outside the table (interp1d's fill value -inf).  Writes
+ *   P[r][k] = 10**S_r(x_k) (TableModel.__call__) and T[r][k] = exp(-log10(P[r][k])) or the
+ *   branch value (transmission); either may be NULL, not both.
+ * nh_ebl_apply: out[w*ldo+k] = Tab[row(z_w)][k] * colfac[k] * sum_j comps[j] (ncomp 0..8; no
+ *   terms: the row itself; colfac may be NULL), z a lazy per-walker redshift, zl[nzl] (DEVICE)
+ *   the tabulated redshifts, nrows = nzl + 1.  row(z) = 0 for 0 <= z < 0.01, else
+ *   1 + argmin_i |zl[i] - z| (first index on a tie); z < 0, NaN or +-inf gives a NaN row. */
+enum { NH_EBL_ONE = 1, NH_EBL_HIGH = 2, NH_EBL_OUTSIDE = 4 };
+int nh_ebl_table(nh_ctx* ctx, const double* knots, int nt, const double* coef, int ncol,
+                 const double* x, const int* code, int nE, double t_hi, double* T, double* P);
+int nh_ebl_apply(nh_ctx* ctx, const double* tab, int ldt, int nrows, const double* zl, int nzl,
+                 const nh_lazy* z /*host*/, const nh_comp* comps /*host*/, int ncomp,
+                 const double* colfac, int N, int m, double* out, int ldo);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ if os.environ.get("NAIMA_AMD_LIB"):  # (experiments: a variant of the library bu
     LIB_PATH = os.path.abspath(os.environ["NAIMA_AMD_LIB"])
 
 NH_PD_NPAR = 8
+NH_EBL_ONE, NH_EBL_HIGH, NH_EBL_OUTSIDE = 1, 2, 4  # nh_ebl_table's per-energy codes
 NH_K_NAMES = ("particle_weights", "integrate_tables", "synchrotron", "tables", "lnprob",
               "ic_seed_walkers", "glue", "integrate_rows", "half_step")
 PD_KIND = {"PowerLaw": 0, "ExponentialCutoffPowerLaw": 1, "BrokenPowerLaw": 2,
@@ -153,6 +154,8 @@ _SIGS = {
     "nh_column_select": [_dp, _dp, _ll, _i, _ll, C.POINTER(_i), _i, _dp],
     "nh_autocorr_prep": [_dp, _dp, _ll, _i, _i, _i, _dp, _dp],
     "nh_autocorr_lags": [_dp, _dp, _dp, _ll, _i, _ll, _i, _dp],
+    "nh_ebl_table": [_dp, _dp, _i, _dp, _i, _dp, _dp, _i, _d, _dp, _dp],
+    "nh_ebl_apply": [_dp, _dp, _i, _i, _dp, _i, _dp, _dp, _i, _dp, _i, _i, _dp, _i],
 }
 EXPORTS = tuple(_SIGS) + ("nh_last_error", "nh_version", "nh_ssc_table_bytes")
 

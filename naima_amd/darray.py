@@ -365,6 +365,8 @@ class DMat:
             return NotImplemented
         if _is_number(o):
             return self._scaled(float(o))
+        if isinstance(o, DEbl):  # per-walker, per-energy factor (EBL absorption at a free z)
+            return o.apply(self)
         if isinstance(o, DVec):  # per-walker factor (a target density that is a fit parameter)
             if o.n != self.shape[0]:
                 raise ValueError("factor has %d walkers, matrix has %d" % (o.n, self.shape[0]))
@@ -453,6 +455,62 @@ class DMat:
         return self.get()[k]
 
 
+class DEbl:
+    """lazy (N, nE) EBL factor: row row(z_w) of a walker-independent table Tab[400][nE]
+    (nh_ebl_table, cached per set of energies) for a lazy per-walker redshift z.  Times a
+    ``DMat`` it is one ``nh_ebl_apply`` launch that also forms the matrix's linear combination;
+    ``.get()`` gathers the rows themselves."""
+    __array_priority__ = 30000
+    __array_ufunc__ = None
+    ndim = 2
+
+    def __init__(self, ctx, tab, zl, z, nE):
+        self.ctx, self.tab, self.zl, self.z = ctx, tab, zl, z
+        self.shape = (z.n, int(nE))
+
+    @property
+    def size(self):
+        return self.shape[0] * self.shape[1]
+
+    def __len__(self):
+        return self.shape[0]
+
+    def apply(self, m=None):
+        """DMat of Tab[row(z_w)][k] * (m[w][k], or 1 without m): one nh_ebl_apply launch"""
+        N, nE = self.shape
+        comps, ncomp, cf = None, 0, None
+        if m is not None:
+            if m.shape != self.shape:
+                raise ValueError("EBL factor of shape %r times a device matrix of shape %r"
+                                 % (self.shape, m.shape))
+            self.ctx.flush(*[t[0] for t in m.terms])
+            comps, ncomp = m.comps(), len(m.terms)
+            cf = self.ctx.const(m.colfac) if m.colfac is not None else None
+        out = self.ctx.empty((N, nE))
+        lz = self.z.lazy()
+        self.ctx.call("nh_ebl_apply", self.tab, nE, self.zl.shape[0] + 1, self.zl,
+                      self.zl.shape[0], C.byref(lz), comps, ncomp, cf, N, nE, out, nE)
+        return DMat.from_buffer(self.ctx, out, N, nE)
+
+    def __mul__(self, o):
+        if _defer(o):
+            return NotImplemented
+        if isinstance(o, DMat):
+            return self.apply(o)
+        return self.apply() * o  # numbers, per-energy factors, per-walker DVec
+
+    __rmul__ = __mul__
+
+    def get(self):
+        return self.apply().get()
+
+    def __array__(self, dtype=None, copy=None):
+        return self.get()
+
+    def __getitem__(self, k):
+        return self.get()[k]
+
+
 class LazyPrior:
     """sum of prior terms on device scalars, evaluated by nh_priors"""
     __array_priority__ = 30000
@@ -512,4 +570,4 @@ class LazyPrior:
 
 
 def is_device(x):
-    return isinstance(x, (DVec, DMat, DPars, LazyPrior))
+    return isinstance(x, (DVec, DMat, DPars, LazyPrior, DEbl))

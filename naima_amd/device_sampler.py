@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from . import units as u
-from .darray import DMat, DPars, DVec
+from .darray import DEbl, DMat, DPars, DVec
 from .dist import shard_bounds, shard_counts
 
 _GAVE_UP = ("a launch of the resident loop gave up waiting for a walker's record (status %d): its "
@@ -310,6 +310,8 @@ class DeviceLoop:
         unit = None
         if isinstance(b, u.Quantity):
             b, unit = b.value, b.unit
+        if isinstance(b, DEbl):  # (a transmission blob: its rows gathered, one launch)
+            b = b.apply()
         if isinstance(b, DMat):
             own, ptr = b.buffer()
             return own, ptr, b.shape[1], unit, (b.shape[1],)

@@ -311,16 +311,103 @@ class TableModel:
         return u.Quantity(a * interpy, self.unit)
 
 
+_EBL_FILE = ("data", "tau_dominguez11.npz")
+_ebl_cache = {}
+
+
+def _ebl_spline():
+    """the Dominguez table as the scalar path interpolates it, every tabulated redshift at
+    once: (log10 E/eV of the table, the tabulated redshifts, knots, coefficients [n][399]).
+    make_interp_spline of all the columns is what interp1d(kind="cubic") evaluates column by
+    column (the same coefficients, bit for bit); built once per process."""
+    hit = _ebl_cache.get("spline")
+    if hit is None:
+        import os
+
+        from scipy.interpolate import make_interp_spline
+
+        from .validator import validate_array
+        tab = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), *_EBL_FILE))
+        energy = validate_array("energy", tab["energy_TeV"] * u.TeV, domain="positive",
+                                physical_type="energy")
+        loge = np.log10(energy.to("eV").value)
+        v = np.array(tab["table"], dtype=float)
+        v[v > 150.0] = 150.0
+        with np.errstate(divide="ignore"):
+            logy = np.log10((10 ** v * u.dimensionless_unscaled).value)
+        spl = make_interp_spline(loge, logy, k=3)
+        hit = (loge, np.arange(0.01, 4, 0.01), np.ascontiguousarray(spl.t),
+               np.ascontiguousarray(spl.c))
+        _ebl_cache["spline"] = hit
+    return hit
+
+
+def _ebl_codes(e):
+    """per energy: log10(E/eV) and the scalar path's decisions, made with its own unit
+    conversions (nh_ebl_table's codes: below 1 GeV, above 100 TeV, outside the table)"""
+    from ._lib import NH_EBL_HIGH, NH_EBL_ONE, NH_EBL_OUTSIDE
+    ev = np.atleast_1d(e.to("eV").value).astype(float).ravel()
+    e_GeV = np.atleast_1d(e.to("GeV").value).ravel()
+    e_TeV = np.atleast_1d(e.to("TeV").value).ravel()
+    loge = _ebl_spline()[0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        x = np.log10(ev)
+    code = np.where(e_GeV < 1.0, NH_EBL_ONE, np.where(e_TeV > 100.0, NH_EBL_HIGH, 0))
+    code = code | np.where((x < loge[0]) | (x > loge[-1]), NH_EBL_OUTSIDE, 0)
+    return x, code.astype(np.int32)
+
+
+def _ebl_table(ctx, x, code, kind):
+    """(Tab[400][nE], ...) of one kind -- "transmission" or "call" (10**S) -- at these
+    energies: one nh_ebl_table launch, cached like the emission tables (and pinned with them
+    for captured graphs).  The entry keeps the arrays its key and nh_ebl_apply point at."""
+    from . import _lib
+    xd, cd = ctx.const(x), ctx.const(code, dtype=np.int32)
+
+    def build():
+        _, zl, t, c = _ebl_spline()
+        td, cfd = ctx.const(t), ctx.const(c)
+        out = ctx.empty((c.shape[1] + 1, x.size))
+        T, P = (out.ptr, None) if kind == "transmission" else (None, out.ptr)
+        # (a table build, not a step-loop launch: called directly, never recorded in a plan)
+        _lib._chk(_lib._lib.nh_ebl_table(ctx.h, td.ptr, t.size, cfd.ptr, c.shape[1], xd.ptr,
+                                         cd.ptr, x.size, float(np.exp(-np.log10(6000.0))), T, P))
+        return out, ctx.const(zl), xd, cd
+
+    return ctx.table(("ebl", kind, xd.ptr, cd.ptr), build)
+
+
+def _per_walker(redshift):
+    from .darray import DVec
+    v = redshift.value if isinstance(redshift, u.Quantity) else redshift
+    return isinstance(v, DVec) or (getattr(v, "__array_priority__", 0) != 30000
+                                   and np.ndim(v) == 1)
+
+
 class EblAbsorptionModel(TableModel):
     """Opacity of the extragalactic background light (Dominguez et al. 2011) at a given
     redshift as a TableModel; ``transmission(e)`` is the factor to multiply a flux with
     (models.py:470-552).  No interpolation in redshift: the closest tabulated z
-    (step 0.01) is used, as in the reference."""
+    (step 0.01) is used, as in the reference.
+
+    ``redshift`` may also be one value per walker: a 1-D host array, or a device parameter
+    (``pars[5]`` or ``pars[5] * u.dimensionless_unscaled`` in a model on the device loop).
+    ``transmission(e)`` and ``__call__(e)`` then have shape (N, n_e) and come from the GPU:
+    a walker-independent table of every tabulated redshift at these energies (built once,
+    cached) and one gathered row per walker (nh_ebl_table / nh_ebl_apply).  On the host they
+    are an ndarray and a Quantity; on the device a lazy factor (``darray.DEbl``) that
+    multiplies a device flux.  A walker whose redshift is negative, NaN or infinite gets a
+    NaN row instead of the scalar's ValueError: a prior that excludes z < 0 gives it -inf,
+    and without one the sampler's ``nan_policy`` applies (-0.0 is valid, as in the
+    reference)."""
 
     def __init__(self, redshift, ebl_absorption_model="Dominguez"):
         import os
 
         from .validator import validate_scalar
+        if _per_walker(redshift):
+            self._init_batch(redshift, ebl_absorption_model)
+            return
         if not isinstance(redshift, u.Quantity):
             redshift = redshift * u.dimensionless_unscaled
         self.redshift = validate_scalar("redshift", redshift, domain="positive",
@@ -343,7 +430,49 @@ class EblAbsorptionModel(TableModel):
             taus = 10 ** np.zeros(len(tab["energy_TeV"])) * u.dimensionless_unscaled
         super().__init__(energy, taus)
 
+    def _init_batch(self, redshift, ebl_absorption_model):
+        from .darray import DVec
+        from .validator import validate_physical_type
+        if not isinstance(redshift, u.Quantity):
+            redshift = u.Quantity(redshift, u.dimensionless_unscaled)
+        validate_physical_type("redshift", redshift, physical_type="dimensionless")
+        z = redshift.to(u.dimensionless_unscaled).value
+        if not isinstance(z, DVec):
+            z = np.asarray(z, dtype=float)
+        self.redshift = u.Quantity(z, u.dimensionless_unscaled)
+        self.model = ebl_absorption_model
+        if self.model != "Dominguez":
+            raise ValueError('Model should be one of: ["Dominguez"]')
+        self.amplitude = 1
+        self.unit = u.dimensionless_unscaled
+
+    @property
+    def _batch(self):
+        return "_interplogy" not in self.__dict__
+
+    def _factor(self, e, kind):
+        """the per-walker factor at energies e: a DEbl over the walkers' redshifts"""
+        from ._lib import get_context
+        from .darray import DEbl, DVec
+        x, code = _ebl_codes(_validate_ene(e))
+        ctx = get_context()
+        tab, zl, _, _ = _ebl_table(ctx, x, code, kind)
+        z = self.redshift.value
+        if not isinstance(z, DVec):
+            zd = ctx.array(z)
+            z = DVec(ctx, zd, zd.ptr, z.size)
+        return DEbl(ctx, tab, zl, z, x.size)
+
+    def __call__(self, e):
+        if not self._batch:
+            return super().__call__(e)
+        f = self._factor(e, "call")
+        return u.Quantity(f if self.redshift.on_device else f.get(), self.unit)
+
     def transmission(self, e):
+        if self._batch:
+            f = self._factor(e, "transmission")
+            return f if self.redshift.on_device else f.get()
         e = _validate_ene(e)
         ev = np.atleast_1d(e.to("eV").value).astype(float)
         e_GeV = np.atleast_1d(e.to("GeV").value)
