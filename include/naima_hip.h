@@ -286,6 +286,24 @@ typedef struct { const double* ptr; long long ld; double scale; } nh_comp;
 int nh_lincomb(nh_ctx* ctx, const nh_comp* comps /*host*/, int ncomp, const double* colfac,
                const nh_lazy* rowfac /*host*/, int N, int m, double* out, int ldo);
 
+/* ---- utils.py:285-355 trapz_loglog of a lazy matrix: a band-integrated flux or luminosity
+ * per walker, trapz_loglog(spectrum * E, E) (docs/radiative.rst "luminosity by setting distance
+ * to 0", tests/test_models.py's known-answer luminosities), without writing the matrix.
+ *   y[w][k] = rowfac[w] * colfac[k] * sum_j comps[j]     (as nh_lincomb forms it)
+ *   out[w*ldo] = trapz_loglog(y[w][0:n], x[0:n])  for w < N
+ * with nh_trapz_loglog's segment term and edge rules (a zero node or x1 == x2 -> 0,
+ * |b+1| <= 1e-10 or NaN b -> log branch, n == 1 -> 0) and its order of summation: the result
+ * is what nh_trapz_loglog gives for nh_lincomb's output, and the same bits at every call.
+ * colfac, rowfac may be NULL; comps[j].ld >= n. */
+int nh_trapz_loglog_comps(nh_ctx* ctx, const nh_comp* comps /*host*/, int ncomp,
+                          const double* colfac, const nh_lazy* rowfac /*host*/, const double* x,
+                          int N, int n, double* out, int ldo);
+/* the same with intervals=True (utils.py:350-351): out[w*ldo + i] = the term of segment
+ * (x_i, x_{i+1}), i < n-1; n >= 2, ldo >= n-1 */
+int nh_trapz_loglog_comps_intervals(nh_ctx* ctx, const nh_comp* comps /*host*/, int ncomp,
+                                    const double* colfac, const nh_lazy* rowfac /*host*/,
+                                    const double* x, int N, int n, double* out, int ldo);
+
 /* priors of core.py:34-58 on lazy scalars; lp[w] = sum of the terms */
 enum { NH_PRIOR_UNIFORM = 0, NH_PRIOR_NORMAL = 1, NH_PRIOR_LOGUNIFORM = 2, NH_PRIOR_VALUE = 3 };
 typedef struct { nh_lazy x; double p0, p1; int kind; int pad; } nh_prior;

@@ -76,6 +76,8 @@ _SIGS = {
     "nh_pack_rows": [_dp, _dp, _i, _i, _dp, _i],
     "nh_ew_binary": [_dp, _i, _dp, _dp, _i, _dp],
     "nh_lincomb": [_dp, _dp, _i, _dp, _dp, _i, _i, _dp, _i],
+    "nh_trapz_loglog_comps": [_dp, _dp, _i, _dp, _dp, _dp, _i, _i, _dp, _i],
+    "nh_trapz_loglog_comps_intervals": [_dp, _dp, _i, _dp, _dp, _dp, _i, _i, _dp, _i],
     "nh_priors": [_dp, _dp, _i, _i, _dp],
     "nh_integrate_tables_nsplit": [_i, _i, _i],
     "nh_lnprob": [_dp, _dp, _i, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _i, _dp, _dp],

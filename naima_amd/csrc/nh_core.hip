@@ -384,6 +384,111 @@ extern "C" int nh_trapz_loglog(nh_ctx* c, const double* y, const double* x, int 
 }
 
 // ---------------------------------------------------------------------------
+// trapz_loglog of a LAZY matrix (a band-integrated flux or luminosity per walker):
+//   y[w][k] = rowfac[w] * colfac[k] * sum_j scale_j * comp_j[w*ld_j + k]
+// formed as k_lincomb forms it and integrated as k_trapz_loglog integrates it (the same
+// segment term, the same per-lane order of the sum), without the matrix ever being written.
+// One wave per walker, four walkers per workgroup.  What does not depend on the walker -- x1,
+// x2 and the two logarithms of x2/x1 -- is computed once per workgroup for a tile of 256
+// segments into LDS.  Every node is loaded once: a lane keeps node base+lane, gets its right-hand
+// neighbour's by __shfl_down, and lane 63 takes lane 0 of the 64 nodes loaded for the next pass.
+// ---------------------------------------------------------------------------
+#define NH_BAND_TILE 256
+
+template <bool INTERVALS>
+__global__ __launch_bounds__(256) void k_trapz_loglog_comps(
+    nh_comps P, const double* __restrict__ colfac, nh_lazy rowfac, const double* __restrict__ x,
+    int N, int n, double* __restrict__ out, int ldo) {
+  __shared__ double sx1[NH_BAND_TILE], sx2[NH_BAND_TILE], sl10[NH_BAND_TILE], sln[NH_BAND_TILE];
+  const int lane = threadIdx.x & 63;
+  const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const bool live = w < N;  // (wave-uniform; a wave without a walker still takes the barriers)
+  const double rf = live ? nh_lazy_eval(rowfac, w) : 0.0;
+  auto node = [&](int k) -> double {
+    if (!live || k >= n) return 0.0;
+    double s = 0.0;
+    for (int j = 0; j < P.n; ++j) s += P.c[j].scale * P.c[j].ptr[(long long)w * P.c[j].ld + k];
+    if (colfac) s *= colfac[k];
+    s *= rf;
+    return s;
+  };
+  double cur = node(lane), acc = 0.0;
+  for (int t0 = 0; t0 < n - 1; t0 += NH_BAND_TILE) {
+    if (t0 > 0) __syncthreads();  // (the previous tile has been read)
+    const int st = t0 + (int)threadIdx.x;
+    if (st < n - 1) {
+      const double x1 = x[st], x2 = x[st + 1];
+      sx1[threadIdx.x] = x1;
+      sx2[threadIdx.x] = x2;
+      sl10[threadIdx.x] = log10(x2 / x1);
+      sln[threadIdx.x] = log(x2 / x1);
+    }
+    __syncthreads();
+    for (int p = 0; p < NH_BAND_TILE / 64 && t0 + 64 * p < n - 1; ++p) {
+      const int q = 64 * p + lane, s = t0 + q;
+      const double nxt = node(s + 64);
+      const double dn = __shfl_down(cur, 1, 64), n0 = __shfl(nxt, 0, 64);
+      const double y1 = cur, y2 = lane == 63 ? n0 : dn;
+      cur = nxt;
+      if (live && s < n - 1) {
+        const double x1 = sx1[q], x2 = sx2[q];
+        const double b = log10(y2 / y1) / sl10[q];
+        const double tp = (y1 * (x2 * pow(x2 / x1, b) - x1)) / (b + 1.0);
+        const double tl = x1 * y1 * sln[q];
+        double t = (fabs(b + 1.0) > 1e-10) ? tp : tl;  // NaN b -> log branch
+        if (y1 == 0.0 || y2 == 0.0 || x1 == x2) t = 0.0;
+        if (INTERVALS) out[(long long)w * ldo + s] = t;
+        else acc += t;
+      }
+    }
+  }
+  if (INTERVALS || !live) return;
+  acc = wave_sum(acc);
+  if (lane == 0) out[(long long)w * ldo] = acc;
+}
+
+static int launch_trapz_comps(nh_ctx* c, const nh_comp* comps, int ncomp, const double* colfac,
+                              const nh_lazy* rowfac, const double* x, int N, int n, double* out,
+                              int ldo, bool intervals) {
+  if (N == 0) return NH_OK;
+  nh_comps P;
+  P.n = ncomp;
+  for (int j = 0; j < ncomp; ++j) P.c[j] = comps[j];
+  nh_lazy rf = {nullptr, 0, 1.0, 0.0, 0.0, NH_TF_ID, 0};  // constant 1
+  if (rowfac) rf = *rowfac;
+  nh_prof_scope ps(c, NH_K_INTEGRATE);
+  if (intervals)
+    hipLaunchKernelGGL(k_trapz_loglog_comps<true>, dim3((N + 3) / 4), dim3(256), 0, c->stream, P,
+                       colfac, rf, x, N, n, out, ldo);
+  else
+    hipLaunchKernelGGL(k_trapz_loglog_comps<false>, dim3((N + 3) / 4), dim3(256), 0, c->stream, P,
+                       colfac, rf, x, N, n, out, ldo);
+  NH_CHECK_HIP(hipGetLastError());
+  return NH_OK;
+}
+
+extern "C" int nh_trapz_loglog_comps(nh_ctx* c, const nh_comp* comps, int ncomp,
+                                     const double* colfac, const nh_lazy* rowfac, const double* x,
+                                     int N, int n, double* out, int ldo) {
+  NH_REQUIRE(c && comps && x && out && ncomp >= 1 && ncomp <= NH_MAX_COMP && N >= 0 && n >= 1 &&
+                 ldo >= 1, "bad argument");
+  for (int j = 0; j < ncomp; ++j)
+    NH_REQUIRE(comps[j].ptr && comps[j].ld >= n, "a component is narrower than n");
+  return launch_trapz_comps(c, comps, ncomp, colfac, rowfac, x, N, n, out, ldo, false);
+}
+
+extern "C" int nh_trapz_loglog_comps_intervals(nh_ctx* c, const nh_comp* comps, int ncomp,
+                                               const double* colfac, const nh_lazy* rowfac,
+                                               const double* x, int N, int n, double* out,
+                                               int ldo) {
+  NH_REQUIRE(c && comps && x && out && ncomp >= 1 && ncomp <= NH_MAX_COMP && N >= 0 && n >= 2 &&
+                 ldo >= n - 1, "bad argument");
+  for (int j = 0; j < ncomp; ++j)
+    NH_REQUIRE(comps[j].ptr && comps[j].ld >= n, "a component is narrower than n");
+  return launch_trapz_comps(c, comps, ncomp, colfac, rowfac, x, N, n, out, ldo, true);
+}
+
+// ---------------------------------------------------------------------------
 // rows 2,3: per-walker particle spectrum on a grid -> weights w = xg*n and the
 // log-ratios dlw[i] = ln|w[i+1]/w[i]| assembled analytically per segment
 // ---------------------------------------------------------------------------

@@ -112,7 +112,9 @@ class EnsembleSampler:
             self._dev.reset()
         self.iteration = 0
         self._chain, self._logp, self._blobs = [], [], None
-        self.blob_units = None
+        # (blob_units stays: the units are the model function's, not the chain's, and the run
+        # that follows a burn-in starts from a state with log-probabilities and never
+        # evaluates the initial ensemble again -- run_sampler's results keep their units)
         self.naccepted = np.zeros(self.nwalkers)
         if getattr(self, "_dev", None) is not None:
             # several ranks: the ensemble all of them were found well at is kept NOW, behind the
