@@ -590,6 +590,9 @@ int nh_half_step_syn_form(const nh_halfstep_plan* plan, int* form);
  * compute_log_prob; reference call site core.py:128); a launch rejects the proposal -- NaN
  * compares false -- and counts.  The one-launch kernels count per plan (below). */
 int nh_nan_count(nh_ctx* ctx, int reset, int* count);
+/* ... and the proposals the same accepts found forbidden by the prior (their log-probability is
+ * the prior's -inf), counted the same way. */
+int nh_forbidden_count(nh_ctx* ctx, int reset, int* count);
 /* The device span clock: what the step loop's launches -- the kernels that replace emcee's
  * EnsembleSampler.sample loop around core.py:97-121 (reference call sites core.py:128, 450-457)
  * -- have spent ON the device since the last reset, measured on those launches themselves: the

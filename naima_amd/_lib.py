@@ -117,6 +117,7 @@ _SIGS = {
     "nh_half_step_syn_form": [_dp, C.POINTER(_i)],
     "nh_half_step_destroy": [_dp, _dp],
     "nh_nan_count": [_dp, _i, C.POINTER(_i)],
+    "nh_forbidden_count": [_dp, _i, C.POINTER(_i)],
     "nh_clock_read": [_dp, _i, C.POINTER(C.c_longlong)],
     "nh_half_step_span": [_dp, _i, _i],
     "nh_half_step_nan_count": [_dp, _dp, _i, C.POINTER(_i)],

@@ -50,7 +50,9 @@ struct nh_ctx {
   void* scratch;   // library-owned device scratch (grown outside graph capture)
   size_t scratch_bytes;
   hipStream_t copy_stream;  // uploads that run AHEAD of the main stream (nh_upload_ahead), or NULL
-  int* nan_word;  // device: NaN log-probabilities met by the accepts of the separate kernels (nh_nan_count)
+  // device: { NaN log-probabilities, proposals forbidden by the prior } met by the accepts of the
+  // separate kernels (nh_nan_count, nh_forbidden_count)
+  int* nan_word;
   // device: the span clock (nh_clock_read) -- { wall_clock64 at the open span's start | ticks of
   // all closed spans | closed spans | (int) blocks of a closing launch that are through }
   long long* clk;

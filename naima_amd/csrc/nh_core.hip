@@ -52,8 +52,8 @@ extern "C" int nh_create(int device, nh_ctx** out) {
   NH_CHECK_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   NH_CHECK_HIP(hipEventCreate(&c->t0));
   NH_CHECK_HIP(hipEventCreate(&c->t1));
-  NH_CHECK_HIP(hipMalloc(&c->nan_word, sizeof(int)));
-  NH_CHECK_HIP(nh_fill_now(c, c->nan_word, 0, sizeof(int)));
+  NH_CHECK_HIP(hipMalloc(&c->nan_word, 2 * sizeof(int)));  // { NaN, forbidden by the prior }
+  NH_CHECK_HIP(nh_fill_now(c, c->nan_word, 0, 2 * sizeof(int)));
   NH_CHECK_HIP(hipMalloc(&c->clk, 8 * sizeof(long long)));
   NH_CHECK_HIP(nh_fill_now(c, c->clk, 0, 8 * sizeof(long long)));
   *out = c;
@@ -91,6 +91,18 @@ extern "C" int nh_nan_count(nh_ctx* c, int reset, int* count) {
   if (rc) return rc;
   NH_CHECK_HIP(hipMemcpy(count, c->nan_word, sizeof(int), hipMemcpyDeviceToHost));
   if (reset && *count) NH_CHECK_HIP(nh_fill_now(c, c->nan_word, 0, sizeof(int)));
+  return NH_OK;
+}
+
+// ... and the proposals the same accepts found forbidden by the prior (a log-probability of -inf),
+// so that EnsembleSampler.prior_forbidden_proposals counts the same whichever kernels made the
+// half-step (the one-launch kernels count per plan: nh_half_step_counts)
+extern "C" int nh_forbidden_count(nh_ctx* c, int reset, int* count) {
+  NH_REQUIRE(c && count, "bad argument");
+  int rc = nh_sync(c);
+  if (rc) return rc;
+  NH_CHECK_HIP(hipMemcpy(count, c->nan_word + 1, sizeof(int), hipMemcpyDeviceToHost));
+  if (reset && *count) NH_CHECK_HIP(nh_fill_now(c, c->nan_word + 1, 0, sizeof(int)));
   return NH_OK;
 }
 
@@ -531,7 +543,7 @@ __global__ __launch_bounds__(256) void k_particle_weights_multi(
   __shared__ double lg[3];
   if (threadIdx.x < 3) {
     const double v = threadIdx.x == 0 ? p.e0 : (threadIdx.x == 1 ? p.ec : p.eb);
-    lg[threadIdx.x] = v > 0.0 ? log(v) : 0.0;
+    lg[threadIdx.x] = v > 0.0 ? log(v) : pd_ln_default(kind, threadIdx.x);
   }
   __syncthreads();
   const int j = blockIdx.y * 256 + threadIdx.x;
@@ -686,7 +698,8 @@ __global__ __launch_bounds__(1024) void k_step_front(front_args A) {
       if (A.pk[q].out == A.params) {
         row[col] = v;
         // ln e_0, ln e_cutoff, ln e_break by the threads that hold those columns
-        if (col == 1 || col == 3 || col == 5) lg[col >> 1] = v > 0.0 ? log(v) : 0.0;
+        if (col == 1 || col == 3 || col == 5)
+          lg[col >> 1] = v > 0.0 ? log(v) : pd_ln_default(A.kind, col >> 1);
       }
     }
   }

@@ -194,6 +194,8 @@ __global__ void k_move_accept(double* __restrict__ coords, double* __restrict__ 
     accepted[j] = acc ? 1 : 0;
     if (sel) sel[j] = me;  // the slice's active walkers, for the blob scatter that follows
     if (newlp[j] != newlp[j]) atomicAdd(nan_count, 1);  // (emcee raises here: nh_nan_count)
+    // (a forbidden walker's log-probability is its prior's -inf, nh_lnprob.h: nh_forbidden_count)
+    if (newlp[j] == -INFINITY) atomicAdd(nan_count + 1, 1);
   }
   __syncthreads();
   if (advance && threadIdx.x == 0) cursor[0] += 1;
@@ -251,6 +253,7 @@ __global__ void k_move_accept_rows(double* __restrict__ coords, double* __restri
     accepted[j] = acc ? 1 : 0;
     if (sel) sel[j] = me;
     if (r[0] != r[0]) atomicAdd(nan_count, 1);  // (emcee raises here: nh_nan_count)
+    if (r[0] == -INFINITY) atomicAdd(nan_count + 1, 1);  // (nh_forbidden_count)
   }
 }
 

@@ -334,7 +334,7 @@ __global__ __launch_bounds__(1024) void k_half_step(const int* __restrict__ done
       ui[sl] = i;
       if (i < nG) {  // (clamped neighbour indices: nothing is selected before all loads are out)
         const int i1 = min(i + 1, nG - 1), il = min(i, nG - 2);
-        if (F.broken) {  // (E itself is only compared with the break energy)
+        if (F.broken & 1) {  // (E itself is only compared with the break energy)
           nE_[sl] = pe[i];
           nE2_[sl] = pe[i1];
         }
@@ -424,7 +424,8 @@ __global__ __launch_bounds__(1024) void k_half_step(const int* __restrict__ done
           // (a power of ten of a proposed coordinate: hs_ln_pow10, as the resident loop has it)
           const bool p10 = pkd >= 0 && pkz.tf == NH_TF_POW10;
           const double lv = log(fabs(p10 ? pkz.a : v));
-          lg[col >> 1] = v > 0.0 ? (p10 ? hs_ln_pow10(lv, pkz.b, pkz.c, qk) : lv) : 0.0;
+          lg[col >> 1] = v > 0.0 ? (p10 ? hs_ln_pow10(lv, pkz.b, pkz.c, qk) : lv)
+                                 : pd_ln_default_flags(F.broken, col >> 1);
         }
       }
     }
@@ -1693,7 +1694,8 @@ static int hs_create(nh_ctx* c, const nh_hs_desc* d, nh_halfstep_plan** out, int
     F.npk8 = d->npacks * NH_MAX_LAZY; F.ngrids = H.ngrids; F.nloc = H.nloc;
     F.qT = H.qT; F.factors = H.factors;
     F.syn_c = P->syn_c; F.syn_nG = H.syn_grid >= 0 ? H.nG[H.syn_grid] : 0;
-    F.broken = (d->kind == NH_PD_BROKENPL || d->kind == NH_PD_ECBPL) ? 1 : 0;
+    F.broken = ((d->kind == NH_PD_BROKENPL || d->kind == NH_PD_ECBPL) ? 1 : 0) |
+               ((d->kind == NH_PD_ECPL || d->kind == NH_PD_ECBPL) ? 2 : 0);
     F.ppk = -1;
     for (int q = 0; q < d->npacks; ++q)
       if (packs_host[q].out == d->params) F.ppk = q;

@@ -99,7 +99,9 @@ struct hs_first {
   double* qT; double* factors;
   const double* syn_c;  // [3][syn_nG]: 1/gamma^2 | its cube root | 1/g2^2 - 1/g1^2 (or NULL)
   int syn_nG;
-  int broken;  // the particle distribution has a break energy (the only use of the grids' E)
+  // bit 0: the particle distribution has a break energy (the only use of the grids' E); bit 1: it
+  // has a cut-off energy (with bit 0: which energy slots it USES, pd_ln_default_flags)
+  int broken;
 };
 
 struct hs_hot {

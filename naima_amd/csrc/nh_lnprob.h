@@ -18,7 +18,9 @@ struct nh_lnprob_args {
   nh_prior_pack pri;
   double* model_out; double* lnl;
   nh_accept mv;
-  int* nan_count;  // the context's counter of NaN log-probabilities met by an accept (or NULL)
+  // the context's counters { NaN log-probabilities, proposals forbidden by the prior } met by an
+  // accept (or NULL)
+  int* nan_count;
 };
 
 __device__ __forceinline__ double nh_wave_sum(double v) {
@@ -112,6 +114,7 @@ __device__ __forceinline__ void nh_lnprob_wave(const nh_lnprob_args& A, int wi, 
       if (mv.sel) mv.sel[g] = me;
       // emcee raises "Probability function returned NaN" here; a launch cannot, it counts
       if (acc != acc && A.nan_count) atomicAdd(A.nan_count, 1);
+      if (has_prior && isinf(prior) && A.nan_count) atomicAdd(A.nan_count + 1, 1);  // (forbidden)
     }
   }
 }
@@ -222,6 +225,7 @@ __device__ __forceinline__ void nh_lnprob64_finish(const nh_lnprob_args& A, cons
       mv.accepted[g] = ok ? 1 : 0;
       if (mv.sel) mv.sel[g] = P.me;
       if (acc != acc && A.nan_count) atomicAdd(A.nan_count, 1);
+      if (has_prior && isinf(P.prior) && A.nan_count) atomicAdd(A.nan_count + 1, 1);  // (forbidden)
     }
   }
 }

@@ -165,6 +165,22 @@ __device__ __forceinline__ bool pd_has_break(int kind) {
   return kind == NH_PD_BROKENPL || kind == NH_PD_ECBPL;
 }
 
+// What the batched weights kernels put in place of ln e for an energy that has no logarithm
+// (c = 0: e_0, 1: e_cutoff, 2: e_break).  A slot the kind does not use holds a constant 0 and
+// must not disturb anything: 0.  An energy the kind USES that is zero, negative or NaN makes the
+// walker's spectrum NaN, as pd_node's log(E / e) does and as the reference's E / e under a
+// non-integer power does -- not the spectrum of e = 1 eV.
+__device__ __forceinline__ double pd_ln_default(int kind, int c) {
+  const bool used = c == 0 || (c == 1 ? pd_has_cutoff(kind) : pd_has_break(kind));
+  return used ? __builtin_nan("") : 0.0;
+}
+// the same from the half-step descriptors' flags (hs_first.broken: bit 0 the kind has a break
+// energy, bit 1 a cut-off)
+__device__ __forceinline__ double pd_ln_default_flags(int flags, int c) {
+  const bool used = c == 0 || (flags & (c == 1 ? 2 : 1)) != 0;
+  return used ? __builtin_nan("") : 0.0;
+}
+
 // the same from energies (three logarithms per node)
 __device__ __forceinline__ void pd_node(int kind, const pd_par& p, double E, double E2,
                                         double lr, double& n, double& dsh) {

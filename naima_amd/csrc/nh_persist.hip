@@ -505,7 +505,7 @@ __global__ __launch_bounds__(RT > 0 ? 512 : 1024) void k_half_step_run(const hs_
   const int ns = H.ns, ndim = H.ndim, N = R.N;
   const int K = gridDim.y, part = blockIdx.y;
   const bool has_syn = SYN && H.syn_grid >= 0;
-  const bool broken = H.F.broken != 0;
+  const bool broken = (H.F.broken & 1) != 0;
   const int GRn = 2 * (ndim + 1);  // granules of a record that carry data (<= 32)
   const bool lik_wave = wv == (nwv > 1 ? 1 : 0);
   const int npk8 = H.F.npk8;
@@ -2096,7 +2096,7 @@ static int hs_run_create(nh_ctx* c, nh_halfstep_plan* P, int rank, int nrank, nh
     R.o_gx[g] = off; off += H.nG[g];
     R.o_lne[g] = off; off += H.nG[g];
     R.o_ge[g] = off;
-    if (H.F.broken) off += H.nG[g];
+    if (H.F.broken & 1) off += H.nG[g];
   }
   // ---- the table grids' 1 / lx in LDS, and the weights' units (below)
   for (int g = 0; g < NH_MAX_GRIDS; ++g) R.o_il[g] = -1;

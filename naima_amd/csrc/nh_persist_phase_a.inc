@@ -26,6 +26,9 @@
       // descriptor three dependent LDS trips)
       double pk_a = 0.0, pk_b = 0.0, pk_c = 0.0, pk_lna = 0.0;
       int pk_tf = 0, pk_nc = 0, pkd = -1;
+      // (what stands in for ln e when this lane's column is an energy without a logarithm: 0 for a
+      // slot the kind leaves unused, NaN for one it uses -- pd_ln_default; walker-independent too)
+      const double pk_ln0 = pd_ln_default_flags(H.F.broken, (lane % NH_MAX_LAZY) >> 1);
       if (lane < npk8) {
         const double* o = sm + R.o_pk + lane * HS_RUN_PKW;
         pk_a = o[0]; pk_b = o[1]; pk_c = o[2];
@@ -144,7 +147,7 @@
                 qs[HS_O_LNA] = lv;
                 qs[HS_O_LNA + 1] = val < 0.0 ? -1.0 : 1.0;
               } else {
-                lg[col >> 1] = val > 0.0 ? lv : 0.0;
+                lg[col >> 1] = val > 0.0 ? lv : pk_ln0;
               }
             }
           }

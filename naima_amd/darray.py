@@ -208,14 +208,14 @@ class DVec:
         return DVec(self.ctx, out, out.ptr, self.n)
 
     def __mul__(self, o):
-        if _defer(o):
+        if _defer(o) or isinstance(o, (DMat, DEbl)):  # (a matrix takes the per-walker factor)
             return NotImplemented
         return self._scale(float(o)) if _is_number(o) else self._binary("mul", o)
 
     __rmul__ = __mul__
 
     def __truediv__(self, o):
-        if _defer(o):
+        if _defer(o) or isinstance(o, (DMat, DEbl)):
             return NotImplemented
         return self._scale(1.0 / float(o)) if _is_number(o) else self._binary("div", o)
 
@@ -384,6 +384,10 @@ class DMat:
             return NotImplemented
         if _is_number(o):
             return self._scaled(1.0 / float(o))
+        if isinstance(o, DVec):  # per-walker divisor: the reciprocal stays lazy, a row factor
+            return self.__mul__(1.0 / o)
+        if isinstance(o, (DMat, DEbl)):
+            return NotImplemented
         return self.__mul__(1.0 / np.asarray(o, dtype=float))
 
     def __neg__(self):

@@ -238,6 +238,7 @@ class DeviceLoop:
         self._nan_pending = self._forbidden_pending = 0
         _n = _lib._i(0)  # (the context's word may hold what an earlier sampler left uncounted)
         _lib._chk(_lib._lib.nh_nan_count(self.ctx.h, 1, C.byref(_n)))
+        _lib._chk(_lib._lib.nh_forbidden_count(self.ctx.h, 1, C.byref(_n)))
         self.resident_launches = 0
         # ... and over an ensemble shared by several GPUs (nh_half_step_run_create_shared: movers
         # store their walkers' records into every rank's ring; no collective per half-step).
@@ -1386,24 +1387,26 @@ class DeviceLoop:
         return None
 
     def _read_counts(self, reset, set_to=None):
-        """(NaN log-probabilities, proposals forbidden by the prior) the one-launch kernels have
-        counted on the device since the last reset"""
+        """(NaN log-probabilities, proposals forbidden by the prior) the kernels have counted on
+        the device since the last reset"""
         hs = self._plan["hs"] if self._plan else None
-        extra = 0
+        extra = extra_f = 0
         if set_to is None:
             # launches of the separate kernels (cfg4; the first half-steps of any run): their
-            # accepts count into the context's word
+            # accepts count into the context's words
             n = _lib._i(0)
             _lib._chk(_lib._lib.nh_nan_count(self.ctx.h, 1 if reset else 0, C.byref(n)))
             extra = n.value
+            _lib._chk(_lib._lib.nh_forbidden_count(self.ctx.h, 1 if reset else 0, C.byref(n)))
+            extra_f = n.value
         if hs is None or hs.get("plan") is None:
-            return extra, 0
+            return extra, extra_f
         n, f = _lib._i(0), _lib._i(0)
         if set_to is not None:
             n, f = _lib._i(-set_to[0] - 1), _lib._i(-set_to[1] - 1)
         _lib._chk(_lib._lib.nh_half_step_counts(self.ctx.h, hs["plan"], 1 if reset else 0,
                                                 C.byref(n), C.byref(f)))
-        return n.value + (extra if reset else 0), f.value
+        return n.value + (extra if reset else 0), f.value + (extra_f if reset else 0)
 
     def check_nan(self, collective=False):
         """NaN log-probabilities the launches met since the last look (one-launch plans count

@@ -56,10 +56,11 @@ MODES = {"resident": {}, "per-launch": {"NAIMA_AMD_RESIDENT": "0"},
 
 
 def run_loop(na, monkeypatch, model, prior, raw, pos, mode="resident", env=None, steps=(3, 4),
-             seed=5):
+             seed=5, nan_policy="raise"):
     """``steps[0]`` then ``steps[1]`` steps of the device loop in ``mode`` (resident: the default
     environment; per-launch: NAIMA_AMD_RESIDENT=0; separate: NAIMA_AMD_MEGA=0) ->
-    dict(chain, lp, blobs (as arrays), units, info, launches)"""
+    dict(chain, lp, blobs (as arrays), units, info, launches, reason, mega, fused, and the
+    sampler's nan_proposals and prior_forbidden_proposals)"""
     from naima_amd.datatable import make_data
     from naima_amd.sampler import EnsembleSampler
     for k in ("NAIMA_AMD_RESIDENT", "NAIMA_AMD_MEGA", "NH_RUN_RT"):
@@ -68,7 +69,7 @@ def run_loop(na, monkeypatch, model, prior, raw, pos, mode="resident", env=None,
         monkeypatch.setenv(k, v)
     nw, nd = pos.shape
     s = EnsembleSampler(nw, nd, na.lnprob, args=[make_data(raw), model, prior], seed=seed,
-                        naima_style=True, store_blobs=True, device=True)
+                        naima_style=True, store_blobs=True, device=True, nan_policy=nan_policy)
     st = s.run_mcmc(pos, steps[0])
     s.run_mcmc(st, steps[1])
     dev = s._dev
@@ -79,7 +80,8 @@ def run_loop(na, monkeypatch, model, prior, raw, pos, mode="resident", env=None,
                 blobs=[np.asarray(b, dtype=float) for b in s.get_blobs()],
                 units=list(s.blob_units or []), info=getattr(dev, "resident_info", None),
                 launches=dev.resident_launches, reason=getattr(dev, "resident_reason", None),
-                mega=dev.mega)
+                mega=dev.mega, fused=dev.fused, nan=s.nan_proposals,
+                forbidden=s.prior_forbidden_proposals)
 
 
 def sample_pairs(nsteps, nw, extra=5, seed=0):
