@@ -830,6 +830,20 @@ int nh_ebl_apply(nh_ctx* ctx, const double* tab, int ldt, int nrows, const doubl
                  const nh_lazy* z /*host*/, const nh_comp* comps /*host*/, int ncomp,
                  const double* colfac, int N, int m, double* out, int ldo);
 
+/* ---- thinning a chain history on the device (emcee's thin_by) -------------------------------
+ * For every segment (row-major DEVICE matrices of doubles, `width` columns each):
+ *   dst row (dst_row0 + k) := src row (first + k*stride),  k < nrows.
+ * One launch for all segments: the chain, the log-probability and every blob history of a chunk
+ * of steps.  A plain copy (16-byte accesses where a segment's width is even and both its bases
+ * are 16-byte aligned, else 8-byte ones), stream-ordered on the context's stream, no host
+ * synchronisation, no scratch.  Rows are copied in parallel, so the bytes read and the bytes
+ * written must not overlap (an in-place compaction would race).  nrows == 0: nothing is launched.
+ * NH_EINVAL: nsegs outside [1, 8], stride < 1, first, nrows or dst_row0 negative, a null or
+ *   misaligned segment, a width < 1, source and destination rows that overlap. */
+typedef struct { const double* src; double* dst; long long width; } nh_thin_seg;
+int nh_hist_thin(nh_ctx* ctx, const nh_thin_seg* segs /*host*/, int nsegs /* <= 8 */,
+                 long long first, long long stride, long long nrows, long long dst_row0);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,6 +157,7 @@ _SIGS = {
     "nh_column_select": [_dp, _dp, _ll, _i, _ll, C.POINTER(_i), _i, _dp],
     "nh_autocorr_prep": [_dp, _dp, _ll, _i, _i, _i, _dp, _dp],
     "nh_autocorr_lags": [_dp, _dp, _dp, _ll, _i, _ll, _i, _dp],
+    "nh_hist_thin": [_dp, _dp, _i, _ll, _ll, _ll, _ll],
     "nh_ebl_table": [_dp, _dp, _i, _dp, _i, _dp, _dp, _i, _d, _dp, _dp],
     "nh_ebl_apply": [_dp, _dp, _i, _i, _dp, _i, _dp, _dp, _i, _dp, _i, _i, _dp, _i],
 }
@@ -231,6 +232,11 @@ def load():
     lib.nh_ssc_table_bytes.argtypes = [_i, _i, _i]
     _lib = lib
     return lib
+
+
+class nh_thin_seg(C.Structure):
+    """one matrix pair of nh_hist_thin (include/naima_hip.h)"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("width", C.c_longlong)]
 
 
 def _chk(rc):

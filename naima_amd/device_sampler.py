@@ -267,6 +267,9 @@ class DeviceLoop:
         self._sh_want = False
         self._sh_journal = []
         self._replaying = False
+        # what the last call with thin_by > 1 did (_sample_thinned): thin_by, where the rows were
+        # thinned, the staging block's rows and bytes, the internal calls as (steps, rows written)
+        self.thin_info = None
         self._finalizer = weakref.finalize(self, _release_loop, self.ctx, self._res)
 
     # ------------------------------------------------------------------ pieces
@@ -641,7 +644,11 @@ class DeviceLoop:
         return out
 
     # ------------------------------------------------------------------- loop
-    def sample(self, initial_state, iterations, store, yield_every=1):
+    def sample(self, initial_state, iterations, store, yield_every=1, thin_by=1):
+        """``iterations`` stored rows of ``thin_by`` ensemble steps each (emcee's thin_by).  The
+        launches write every step's row, as the blob bookkeeping of the step kernels needs; with
+        thin_by > 1 they write them into a staging block that is reused, and every thin_by-th row
+        is copied to the compact block that is kept (_sample_thinned)."""
         from .sampler import State
         s, ctx = self.s, self.ctx
         cont = isinstance(initial_state, DeviceState) and initial_state._loop is self
@@ -650,40 +657,134 @@ class DeviceLoop:
             if st.coords.shape != (self.N, self.ndim):
                 raise ValueError("incompatible input dimensions")
             self._init_state(st.coords, st.log_prob)
-        N = self.N
-        iterations = int(iterations)
+        iterations, thin_by = int(iterations), int(thin_by)
+        # several ranks: merging the ranks' rows (_merge_shared_block) needs every step's row and
+        # flags on the host, so the block stays full-rate and flush slices it after the merge
+        host_thin = thin_by > 1 and self.sharded
         jentry = None
         if self.sharded and s.comm.size > 1 and not self._replaying and self._run is not False:
             if self._sh_snap is None or not cont:  # (normally kept at the verified point itself)
                 self._shared_snapshot()
             # (the steps the call has MADE, kept up to date as it goes: a caller that breaks out of
             # the generator early must not have the full count replayed -- ADVICE r5)
-            jentry = [0, bool(store), yield_every]
+            jentry = [0, bool(store), yield_every, thin_by]
             self._sh_journal.append(jentry)
         block = None
-        if store and iterations > 0:
-            block = dict(n=0, coords=ctx.empty((iterations, N * self.ndim)),
-                         logp=ctx.empty((iterations, N)),
-                         blobs=[ctx.empty((iterations, N * m)) for _, m, _, _ in
-                                (self.cur_blobs or [])] if s.store_blobs else [])
-            if self.sharded and self.s.comm.size > 1:
-                # a shared ensemble's launches: who moved (and accepted) what, per row; the
-                # blobs as they stood before the first row (rows of rejected moves are filled
-                # from the row before when the ranks' histories are merged)
-                self._sync_cur_blobs()
-                block["own"] = ctx.empty((iterations, N), dtype=np.int32)
-                block["shared_rows"] = []  # [row0, row1) of every shared launch
-                block["cur0"] = []
-                if block["blobs"] and self._cur_host is not None:
-                    block["cur0"] = self._cur_host  # (host copies the last merge left: no launch)
-                elif block["blobs"]:
-                    for cur, m, _, _ in self.cur_blobs or []:
-                        c0 = ctx.empty((N, m))
-                        ctx.call("nh_copy", c0, cur, 8 * N * m)
-                        block["cur0"].append(c0)
+        if store and iterations > 0 and (thin_by == 1 or host_thin):
+            block = self._new_block(iterations * thin_by, shared=self.sharded and s.comm.size > 1)
+            if host_thin:
+                block["thin_by"] = thin_by
             self.hist.append(block)
         if not cont:
             self._sync_cur_blobs()
+        if thin_by == 1:
+            yield from self._steps(iterations, yield_every, block, jentry)
+        else:
+            yield from self._sample_thinned(iterations, thin_by, store, yield_every, block, jentry)
+
+    def _new_block(self, rows, shared=False):
+        """a history block of `rows` rows in HBM: coords, log-prob and every kept blob; `shared`:
+        with what the merge of several ranks' rows needs"""
+        s, ctx, N = self.s, self.ctx, self.N
+        block = dict(n=0, coords=ctx.empty((rows, N * self.ndim)),
+                     logp=ctx.empty((rows, N)),
+                     blobs=[ctx.empty((rows, N * m)) for _, m, _, _ in
+                            (self.cur_blobs or [])] if s.store_blobs else [])
+        if shared:
+            # a shared ensemble's launches: who moved (and accepted) what, per row; the
+            # blobs as they stood before the first row (rows of rejected moves are filled
+            # from the row before when the ranks' histories are merged)
+            self._sync_cur_blobs()
+            block["own"] = ctx.empty((rows, N), dtype=np.int32)
+            block["shared_rows"] = []  # [row0, row1) of every shared launch
+            block["cur0"] = []
+            if block["blobs"] and self._cur_host is not None:
+                block["cur0"] = self._cur_host  # (host copies the last merge left: no launch)
+            elif block["blobs"]:
+                for cur, m, _, _ in self.cur_blobs or []:
+                    c0 = ctx.empty((N, m))
+                    ctx.call("nh_copy", c0, cur, 8 * N * m)
+                    block["cur0"].append(c0)
+        return block
+
+    def _sample_thinned(self, rows, t, store, yield_every, block, jentry):
+        """`rows` stored rows of `t` steps each.  One GPU, history kept: the steps run as internal
+        calls of c*t steps that write a staging block of c*t rows through the usual paths; once
+        a call's launches are known to have ended well (what _steps ends with), ONE launch copies
+        staging rows t-1, 2t-1, ... to the next c rows of the compact block that flush downloads
+        (nh_hist_thin, stream-ordered, no synchronisation of its own).  c: as many rows as keep
+        the staging block's allocation within NAIMA_AMD_THIN_STAGE_MB (default 512).  If not even
+        t rows fit, a stored row is t-1 steps without a history and one step with it, and the
+        staging block holds one row.  `block` (several ranks): the full-rate block, thinned on
+        the host by flush.  thin_info says what was done."""
+        s, ctx, N = self.s, self.ctx, self.N
+        group = rows if yield_every >= rows else max(1, int(yield_every))
+        info = dict(thin_by=t, where="host" if block is not None else "none", stage_rows=0,
+                    stage_bytes=0, stage_alloc_bytes=0, calls=[])
+        self.thin_info = info
+        compact = stage = None
+        split = False
+        if store and rows > 0 and block is None:
+            widths = [N * self.ndim, N]
+            if s.store_blobs:
+                widths += [N * m for _, m, _, _ in (self.cur_blobs or [])]
+            budget = int(float(os.environ.get("NAIMA_AMD_THIN_STAGE_MB", "512")) * (1 << 20))
+
+            def alloc(r):  # (what the context's pool sets aside for r rows)
+                return sum(ctx._bucket(8 * r * w) for w in widths)
+
+            lo, hi = 0, group  # the largest c in [1, group] whose c*t rows stay in the budget
+            while lo < hi:
+                mid = (lo + hi + 1) // 2
+                lo, hi = (mid, hi) if alloc(mid * t) <= budget else (lo, mid - 1)
+            split = lo == 0
+            group = max(1, lo)
+            srows = 1 if split else group * t
+            compact = self._new_block(rows)
+            self.hist.append(compact)
+            stage = self._new_block(srows)
+            info.update(where="device", stage_rows=srows, stage_bytes=8 * srows * sum(widths),
+                        stage_alloc_bytes=alloc(srows))
+
+        def call(steps, blk):
+            if blk is stage and stage is not None:
+                stage["n"] = 0
+            for _ in self._steps(steps, 1 << 30, blk, jentry):
+                pass
+            info["calls"].append((steps, steps if blk is not None else 0))
+
+        done = 0
+        while done < rows:
+            c = min(group, rows - done)
+            if stage is None:
+                call(c * t, block)
+            elif split:
+                call(t - 1, None)
+                call(1, stage)
+                self._compact(stage, compact, 0, 1, 1)
+            else:
+                call(c * t, stage)
+                self._compact(stage, compact, t - 1, t, c)
+            s.iteration -= c * t - c  # (stored rows; _advance has counted the steps)
+            done += c
+            yield DeviceState(self, s._rng)
+
+    def _compact(self, stage, compact, first, stride, nrows):
+        """rows first, first + stride, ... of the staging block -> the compact block's next nrows
+        rows: one launch for the chain, the log-probability and (up to six) blob histories"""
+        pairs = [(stage["coords"], compact["coords"]), (stage["logp"], compact["logp"])] + \
+            list(zip(stage["blobs"], compact["blobs"]))
+        for i in range(0, len(pairs), 8):
+            part = pairs[i:i + 8]
+            segs = (_lib.nh_thin_seg * len(part))(*[
+                _lib.nh_thin_seg(a.ptr, b.ptr, a.shape[1]) for a, b in part])
+            self.ctx.call("nh_hist_thin", segs, len(part), first, stride, nrows, compact["n"])
+        compact["n"] += nrows
+        self._changes += 1
+
+    def _steps(self, iterations, yield_every, block, jentry):
+        """`iterations` ensemble steps from the ensemble in HBM, their rows appended to `block`
+        (None: no history) from its row block["n"] on"""
         # the launches append the chain history themselves (the nh_hist descriptor) when the
         # call keeps one and the launch's plan exists; else one pair of copies per step ...
         dev_hist = self.fused and block is not None and not (self.mega and self._plan["hs"] is None)
@@ -776,7 +877,8 @@ class DeviceLoop:
         s, ctx, mv, N, ns = self.s, self.ctx, self._mv, self.N, self.ns
         if self.fused:
             # (the per-launch kernel's history descriptor: where its launches append the chain)
-            words = [block["coords"].ptr, block["logp"].ptr, 0, iterations] if dev_hist \
+            words = [block["coords"].ptr, block["logp"].ptr, 0, block["coords"].shape[0]] \
+                if dev_hist \
                 else [0, 0, 0, 0]
             if blob_dev_hist:
                 words = words + [hb.ptr for hb in block["blobs"]]
@@ -1362,11 +1464,14 @@ class DeviceLoop:
             max(1, self.resident_launches - snap["rl"]), snap, rewind=True)
         self._replaying = True
         try:
-            for made, store, yield_every in journal:
-                if made <= 0:
-                    continue
-                for _ in self.sample(DeviceState(self, s._rng), made, store, yield_every=1 << 30):
-                    pass
+            for made, store, yield_every, tb in journal:
+                # (`made` counts steps: the same rows are stored again, every tb-th; steps past
+                # the last stored row of a call that was left early are made without a history)
+                for n, keep, by in ((made // tb, store, tb), (made % tb, False, 1)):
+                    if n > 0:
+                        for _ in self.sample(DeviceState(self, s._rng), n, keep,
+                                             yield_every=1 << 30, thin_by=by):
+                            pass
             self._flush_pending()
             ctx.sync()
         finally:
@@ -1639,6 +1744,12 @@ class DeviceLoop:
                    for hb, (cur, m, _, trail) in zip(block["blobs"], self.cur_blobs or [])]
             if self.shared and block.get("own") is not None:
                 self._merge_shared_block(block, n, c, l, per)
+            tb = block.get("thin_by", 1)
+            if tb > 1:  # (several ranks: a thinned call's rows, full-rate up to here)
+                c, l, per = c[tb - 1::tb], l[tb - 1::tb], [a[tb - 1::tb] for a in per]
+                n = c.shape[0]
+                if n == 0:
+                    continue
             s._chain.extend(list(c))
             s._logp.extend(list(l))
             if block["blobs"]:

@@ -395,7 +395,9 @@ def _plot_chain_func(sampler, p, last_step=False):
     chain = np.asarray(sampler.get_chain())
     traces = chain[:, :, p].T  # (walker, step)
     try:  # (plot.py:202-209: on the chain, so that read_run results get the line too)
-        tau = integrated_time(chain)[p]
+        # in ensemble steps: a run thinned as it was made (run_sampler(thin_by=)) stores a row
+        # every thin_by steps
+        tau = integrated_time(chain)[p] * getattr(sampler, "run_info", {}).get("thin_by", 1)
     except AutocorrError:  # too short a chain for a meaningful estimate
         tau = None
     label = sampler.labels[p]

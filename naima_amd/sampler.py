@@ -111,6 +111,7 @@ class EnsembleSampler:
         if getattr(self, "_dev", None) is not None:
             self._dev.reset()
         self.iteration = 0
+        self._steps_at_reset = self.steps_total
         self._chain, self._logp, self._blobs = [], [], None
         # (blob_units stays: the units are the model function's, not the chain's, and the run
         # that follows a burn-in starts from a state with log-probabilities and never
@@ -124,9 +125,18 @@ class EnsembleSampler:
             self._dev.keep_verified()
 
     @property
+    def steps_since_reset(self):
+        """ensemble steps made since ``reset()`` (``iteration`` counts the rows STORED since then:
+        with ``thin_by`` = t it grows by one every t steps)"""
+        return self.steps_total - self._steps_at_reset
+
+    @property
     def acceptance_fraction(self):
+        """moves accepted per walker, divided by the steps MADE since ``reset()``.  (emcee divides
+        by the backend's ``iteration``, the count of stored rows, and so over-reports a thinned
+        run's acceptance fraction by a factor of ``thin_by``.)"""
         self._flush()
-        return self.naccepted / max(1, self.iteration)
+        return self.naccepted / max(1, self.steps_since_reset)
 
     def _flush(self):
         if self._dev is not None:
@@ -223,15 +233,25 @@ class EnsembleSampler:
         return arrs, units
 
     # ------------------------------------------------------------------ sample
-    def sample(self, initial_state, iterations=1, store=True, log_prob0=None, yield_every=1):
+    def sample(self, initial_state, iterations=1, store=True, log_prob0=None, yield_every=1,
+               thin_by=1):
         """emcee's generator: one State per ensemble step.  ``yield_every`` > 1 (what
         ``run_mcmc`` asks for) lets the device loop replay several steps as one hipGraph
-        and yield only after each such group."""
+        and yield only after each such group.
+
+        ``thin_by`` = t (emcee 3): the call makes ``iterations * t`` steps and stores -- and
+        yields -- the state after every t-th of them; ``iteration`` counts the stored rows,
+        ``steps_total`` the steps made, and ``yield_every`` counts stored rows.  The device loop
+        thins on the GPU (DeviceLoop.sample): the full-rate history never leaves HBM."""
+        thin_by = int(thin_by)
+        if thin_by <= 0:
+            raise ValueError("Invalid thinning argument")
         if self.device:
             if self._dev is None and self._device_ok is None:
                 self._device_ok = self._probe_device(initial_state)
             if self._device_ok is not False:
-                yield from self._sample_device(initial_state, iterations, store, yield_every)
+                yield from self._sample_device(initial_state, iterations, store, yield_every,
+                                               thin_by)
                 return
             # the model shapes a grid / table per walker (Eemin, a seed temperature ... as
             # fit parameters): the general path needs the values on the host
@@ -258,7 +278,7 @@ class EnsembleSampler:
                 self._cur_blobs = []
         logp = logp.copy()
         moves = self.moves()
-        for _ in range(int(iterations)):
+        for step in range(1, int(iterations) * thin_by + 1):
             addr, got = moves.take(1)
             Sm, Pm, Zm, Lm = moves.view(addr, got)
             for split in range(2):
@@ -277,8 +297,10 @@ class EnsembleSampler:
                     new, _ = self._blob_arrays(blobs, hi - lo)
                     for cur, nb in zip(self._cur_blobs, new):
                         cur[acc_idx] = self._gather_rows(nb, len(S))[accepted]
-            self.iteration += 1
             self.steps_total += 1
+            if step % thin_by:
+                continue
+            self.iteration += 1
             if store:
                 self._chain.append(coords.copy())
                 self._logp.append(logp.copy())
@@ -329,11 +351,11 @@ class EnsembleSampler:
             return False
         return True
 
-    def _sample_device(self, initial_state, iterations, store, yield_every=1):
+    def _sample_device(self, initial_state, iterations, store, yield_every=1, thin_by=1):
         from .device_sampler import DeviceLoop
         if self._dev is None:
             self._dev = DeviceLoop(self)
-        yield from self._dev.sample(initial_state, iterations, store, yield_every)
+        yield from self._dev.sample(initial_state, iterations, store, yield_every, thin_by)
 
     def _gather_rows(self, rows, n):
         """this rank's block of an n-row array -> all n rows, on every rank"""
@@ -346,10 +368,11 @@ class EnsembleSampler:
         allp = self.comm.allgather(pad).reshape((size, max(counts)) + rows.shape[1:])
         return np.concatenate([allp[r, :c] for r, c in enumerate(counts)], axis=0)
 
-    def run_mcmc(self, initial_state, nsteps, **kw):
+    def run_mcmc(self, initial_state, nsteps, thin_by=1, **kw):
+        """``nsteps`` stored rows, ``nsteps * thin_by`` ensemble steps (see ``sample``)"""
         state = None
         kw.setdefault("yield_every", 1 << 30)  # nobody looks at the intermediate states
-        for state in self.sample(initial_state, iterations=nsteps, **kw):
+        for state in self.sample(initial_state, iterations=nsteps, thin_by=thin_by, **kw):
             pass
         return state
 
@@ -357,17 +380,18 @@ class EnsembleSampler:
 # --------------------------------------------------------------------------
 # naima's entry points (core.py:220-538)
 # --------------------------------------------------------------------------
-def _run_mcmc(sampler, pos, nrun, verbose=True):
+def _run_mcmc(sampler, pos, nrun, verbose=True, thin_by=1):
     """core.py:127-160: the run with a progress printout every 5 %.  The steps between two
     printouts are one ``run_mcmc`` call, so the device loop replays whole groups of steps
-    and the ensemble is only brought to the host for the printouts."""
+    and the ensemble is only brought to the host for the printouts.  With ``thin_by`` the
+    run -- and its printout -- go by stored rows, ``thin_by`` steps each."""
     state = pos
     nrun = int(nrun)
     edges = sorted(set(int(round(x)) for x in np.linspace(0, nrun, 21)))
     for a, b in zip(edges[:-1], edges[1:]):
         if verbose and sampler.comm.rank == 0 and a > 0:
             _print_progress(sampler, state, a, nrun)
-        state = sampler.run_mcmc(state, b - a, store=True)
+        state = sampler.run_mcmc(state, b - a, store=True, thin_by=thin_by)
     return sampler, state
 
 
@@ -500,19 +524,27 @@ def get_sampler(data_table=None, p0=None, model=None, prior=None, nwalkers=500, 
     return sampler, state
 
 
-def run_sampler(nrun=100, sampler=None, pos=None, verbose=True, **kwargs):
-    """Run an MCMC sampler (core.py:496-538)."""
+def run_sampler(nrun=100, sampler=None, pos=None, verbose=True, thin_by=1, **kwargs):
+    """Run an MCMC sampler (core.py:496-538).  ``thin_by`` = t (emcee's): ``nrun`` is the number
+    of STORED rows, each t ensemble steps after the one before; ``run_info["thin_by"]`` records
+    it.  The burn-in of ``get_sampler`` is not thinned."""
+    thin_by = int(thin_by)
+    if thin_by <= 0:
+        raise ValueError("Invalid thinning argument")
     if sampler is None or pos is None:
         sampler, pos = get_sampler(verbose=verbose, **kwargs)
     sampler.run_info["n_run"] = nrun
+    sampler.run_info["thin_by"] = thin_by
     if verbose and sampler.comm.rank == 0:
-        print("\nWalker burn in finished, running {0} steps...".format(nrun))
+        print("\nWalker burn in finished, running {0} steps...".format(nrun) if thin_by == 1 else
+              "\nWalker burn in finished, running {0} steps, keeping every {1}th..."
+              .format(nrun * thin_by, thin_by))
     sampler.reset()
     t0 = time.time()
     if isinstance(pos, State):
         pos = State(pos.coords)
     elif not hasattr(pos, "_loop"):  # (a DeviceState continues from the ensemble in HBM)
         pos = State(pos)
-    sampler, pos = _run_mcmc(sampler, pos, nrun, verbose)
+    sampler, pos = _run_mcmc(sampler, pos, nrun, verbose, thin_by)
     sampler.run_info["wall_s"] = time.time() - t0
     return sampler, pos
