@@ -16,15 +16,19 @@ pieces (grids, emission tables, data columns) are evaluated during a warm-up pas
 land in the context's caches, and are therefore not part of the graph.  After
 capture no Python model code runs inside the loop.
 """
+import collections
 import ctypes as C
 import os
+import warnings
+import weakref
 
 import numpy as np
 
-from . import _lib
+from . import _lib, shared_merge
 from . import units as u
 from .darray import DEbl, DMat, DPars, DVec
 from .dist import shard_bounds, shard_counts
+from .move_ring import MoveRing
 
 _GAVE_UP = ("a launch of the resident loop gave up waiting for a walker's record (status %d): its "
             "workgroups were not all resident")
@@ -40,20 +44,14 @@ class DeviceState:
     @property
     def coords(self):
         if self._c is None:
-            self._loop._flush_pending()
-            self._loop._settle_before_read()  # (one GPU: the friendlier message, ahead of the status)
-            self._loop.check_resident()
-            self._loop.check_nan()
+            self._loop._before_read()
             self._c = self._loop.coords.get().reshape(self._loop.N, self._loop.ndim)
         return self._c
 
     @property
     def log_prob(self):
         if self._l is None:
-            self._loop._flush_pending()
-            self._loop._settle_before_read()
-            self._loop.check_resident()
-            self._loop.check_nan()
+            self._loop._before_read()
             self._l = self._loop.logp.get()
         return self._l
 
@@ -83,16 +81,12 @@ def _release_loop(ctx, res):
             _lib._lib.nh_half_step_run_destroy(ctx.h, r)
         res["runs"] = []
         for plan in res["plans"]:
-            hs = plan.get("hs") if plan else None
-            if hs is not None and hs.get("plan") is not None:
-                _lib._lib.nh_half_step_destroy(ctx.h, hs["plan"])
-                hs["plan"] = None
-                plan["hs"] = None
-            st = plan.get("stage") if plan else None
-            if st is not None and st.get("plan") is not None:
-                _lib._lib.nh_half_step_destroy(ctx.h, st["plan"])
-                st["plan"] = None
-                plan["stage"] = None
+            for key in ("hs", "stage") if plan else ():
+                hs = plan.get(key)
+                if hs is not None and hs.get("plan") is not None:
+                    _lib._lib.nh_half_step_destroy(ctx.h, hs["plan"])
+                    hs["plan"] = None
+                    plan[key] = None
     except Exception:
         pass
     res["graphs"], res["plans"] = [], []
@@ -118,7 +112,6 @@ class DeviceLoop:
             # for their share of its CUs -- or their resident launches cannot all be resident
             # together and the first shared launch gives up.  Who shares a device is read off the
             # ranks' PCI bus ids (collective: every rank, always); NAIMA_AMD_CU_SHARE overrides.
-            import collections
             ids = [p_.decode() for p_ in comm.group.allgather_bytes(self.ctx.pci_bus_id().encode())]
             share = max(collections.Counter(ids).values())
             if share > 1 and not os.environ.get("NAIMA_AMD_CU_SHARE"):
@@ -146,24 +139,13 @@ class DeviceLoop:
         ctx = self.ctx
         self.coords = ctx.empty((self.N * self.ndim,))
         self.logp = ctx.empty((self.N,))
-        # the random numbers of up to KSTEPS ensemble steps travel as ONE block; a device
-        # cursor selects the current half-step's slice (advanced by the accept kernel)
-        self.KSTEPS = 32
         # ensemble steps per hipGraph launch when the host has nothing to do
         self.GSTEPS = max(1, int(os.environ.get("NAIMA_AMD_GSTEPS", "8")))
         self.multi_graph = None
-        # one spare slice: the fused move kernel proposes the half-step AFTER the one it
-        # accepts, so the last one of a block reads (and discards) slice 2*KSTEPS
-        # (room for MOVES_CAP steps: the resident loop keeps the move stream's next steps on the
-        # device ahead of time -- uploaded on a copy stream while the current launch runs)
-        self.MOVES_CAP = 4 * self.KSTEPS
-        self.blk = ctx.empty((2 * self.MOVES_CAP + 1, 3 * self.ns))
-        ctx.call("nh_memset", self.blk, 0, self.blk.nbytes)
-        # steps on the device / consumed / last ahead marker / markers behind the last two launches
-        self._mv = dict(have=0, used=0, ahead=None, prev=None, last=None)
-        self._launch_marks = [ctx.marker() for _ in range(3)]
-        self._nlaunch = 0
-        self._blk_tmp = None
+        # the move stream on the device; a device cursor selects the current half-step's slice
+        # of `blk` (advanced by the accept kernel)
+        self.ring = MoveRing(ctx, self.ns)
+        self.blk = self.ring.blk
         # nh_step_front mode: set after a recording evaluation when the model's parameter
         # packs read the proposal buffer and it asks for ONE particle-weights launch
         self.fused = False
@@ -203,9 +185,6 @@ class DeviceLoop:
         self.graph21 = None
         self._pending = False
         self.step_graph = None
-        self._markers = [ctx.marker() for _ in range(4)]
-        self._inflight = []
-        self._nmark = 0
         self.accepted = ctx.empty((self.ns,), dtype=np.int32)
         self.nacc = ctx.empty((self.N,), dtype=np.int32)
         ctx.call("nh_memset", self.nacc, 0, self.nacc.nbytes)
@@ -216,7 +195,6 @@ class DeviceLoop:
         self.warm = 0
         self._have_state = False
         # what this loop owns on the device besides pooled buffers: released when it goes
-        import weakref
         self._res = dict(graphs=[], plans=[], runs=[])
         # the resident loop (nh_half_step_run: a whole block of moves per launch, walkers handed
         # from half-step to half-step by per-walker records): None = not tried yet, False = this
@@ -236,9 +214,7 @@ class DeviceLoop:
         # launch that gave up -- or ran void behind one that did -- is rolled back to
         self._cur_snaps = [None] * 4
         self._nan_pending = self._forbidden_pending = 0
-        _n = _lib._i(0)  # (the context's word may hold what an earlier sampler left uncounted)
-        _lib._chk(_lib._lib.nh_nan_count(self.ctx.h, 1, C.byref(_n)))
-        _lib._chk(_lib._lib.nh_forbidden_count(self.ctx.h, 1, C.byref(_n)))
+        self._read_counts(reset=True)  # (the context's words may hold what an earlier sampler left)
         self.resident_launches = 0
         # ... and over an ensemble shared by several GPUs (nh_half_step_run_create_shared: movers
         # store their walkers' records into every rank's ring; no collective per half-step).
@@ -276,11 +252,7 @@ class DeviceLoop:
     def reset(self):
         """forget the chain and the acceptance counts (the sampler clears its host copies): the
         history still on the device is dropped, not downloaded"""
-        self._flush_pending()
-        self.check_resident(collective=True)
-        self.check_nan(collective=True)
-        self.ctx.check_general()
-        self._sync_cur_blobs()
+        self._meet()
         self.hist = []
         self.ctx.call("nh_memset", self.nacc, 0, self.nacc.nbytes)
         if self.shared:
@@ -288,6 +260,14 @@ class DeviceLoop:
             self._acc_dirty, self._acc_shared = False, 0.0
         self._acc_base = 0.0
         self._flushed_at = None
+
+    def _meet(self):
+        """where every rank is (flush, reset): what only all of them together can find or mend"""
+        self._flush_pending()
+        self.check_resident(collective=True)
+        self.check_nan(collective=True)
+        self.ctx.check_general()  # (a per-walker grid longer than the general kernel's LDS)
+        self._sync_cur_blobs()
 
     def _eval(self, qT_buf, n):
         """run the user's model on device parameters: (total DVec, blob list)"""
@@ -375,31 +355,23 @@ class DeviceLoop:
     def _part_accept(self):
         ctx = self.ctx
         if self.fused and self.sharded and self.blobs_in_kernel and self.send_width:
-            import ctypes as C
             nb = len(self.cur_blobs)
             cur = (C.c_void_p * nb)(*[c_.ptr for c_, _, _, _ in self.cur_blobs])
             mm = (C.c_int * nb)(*[m for _, m, _, _ in self.cur_blobs])
             ctx.call("nh_move_accept_rows", self.coords, self.logp, self.blk, self.cursor,
                      self.recv_rows, self.send_width, self.ns, self.ndim, self.accepted, self.nacc,
                      self.sel, 0, nb, cur, mm)
-        elif self.fused:
-            if not (self._hook and self._hook["used"] and self._hook["mv"] is not None):
-                # sharded (the accept waits for the all-gather), or a foreign likelihood
-                ctx.call("nh_move_accept", self.coords, self.logp, self.blk, self.cursor,
-                         self._newlp_ptr, self.ns, self.ndim, self.accepted, self.nacc,
-                         self.sel, 0)
-        else:
+        elif not (self.fused and self._hook and self._hook["used"] and self._hook["mv"] is not None):
+            # not accepted by the likelihood's own launch: the separate kernels (which also advance
+            # the cursor: 1), sharded (the accept waits for the all-gather), a foreign likelihood
             ctx.call("nh_move_accept", self.coords, self.logp, self.blk, self.cursor,
-                     self._newlp_ptr, self.ns, self.ndim, self.accepted, self.nacc, self.sel, 1)
+                     self._newlp_ptr, self.ns, self.ndim, self.accepted, self.nacc, self.sel,
+                     0 if self.fused else 1)
         if self.s.store_blobs and self.cur_blobs and not self.blobs_in_kernel:
-            if self.sharded:
-                for ab, (cur, m, _, _) in zip(self.all_blobs, self.cur_blobs):
-                    ctx.call("nh_scatter_rows", cur, m, ab, m, self.sel, self.accepted, 0,
-                             self.ns, m)
-            else:
-                for nb, (cur, m, _, _) in zip(self.new_blobs, self.cur_blobs):
-                    ctx.call("nh_scatter_rows", cur, m, nb, m, self.sel, self.accepted, self.lo,
-                             self.nloc, m)
+            src, lo, n = (self.all_blobs, 0, self.ns) if self.sharded else \
+                (self.new_blobs, self.lo, self.nloc)
+            for b, (cur, m, _, _) in zip(src, self.cur_blobs):
+                ctx.call("nh_scatter_rows", cur, m, b, m, self.sel, self.accepted, lo, n, m)
         if self.fused and not self.mega:
             self._front()
 
@@ -414,7 +386,6 @@ class DeviceLoop:
         """a half-step launched piece by piece while the model's parameter packs, weights
         launch and single-row reductions are recorded; if nh_step_front can produce them
         the loop switches to it"""
-        import ctypes as C
         from .darray import nh_accept, nh_grid, nh_lazy, nh_moment, nh_pack
         ctx = self.ctx
         plan = ctx.plan_begin()
@@ -658,8 +629,8 @@ class DeviceLoop:
                 raise ValueError("incompatible input dimensions")
             self._init_state(st.coords, st.log_prob)
         iterations, thin_by = int(iterations), int(thin_by)
-        # several ranks: merging the ranks' rows (_merge_shared_block) needs every step's row and
-        # flags on the host, so the block stays full-rate and flush slices it after the merge
+        # several ranks: merging the ranks' rows (shared_merge.merge_history_rows) needs every step's
+        # row and flags on the host, so the block stays full-rate and flush slices it after the merge
         host_thin = thin_by > 1 and self.sharded
         jentry = None
         if self.sharded and s.comm.size > 1 and not self._replaying and self._run is not False:
@@ -819,47 +790,27 @@ class DeviceLoop:
         """the call as launches of the resident loop, up to KSTEPS steps each, a launch checked
         when the one behind it is queued (_rl_settle) -> the steps made: fewer than `iterations`
         when a launch gave up, and the per-launch loop makes the rest"""
-        ctx, mv = self.ctx, self._mv
+        ring = self.ring
         moves = self.s.moves(pinned=True)
         it = 0
         while it < iterations:
             # the moves are a function of the seed only, so the stream's next steps are already on
-            # the device (uploaded ahead, below) unless this is the first call; the generator hands
-            # its stream out in pieces that end at its own block boundaries: they land side by side
-            # in `blk` and run as ONE launch
-            want = min(self.KSTEPS, iterations - it)
-            if mv["have"] - mv["used"] < want:
-                need = want - (mv["have"] - mv["used"])
-                if mv["have"] + need > self.MOVES_CAP:
-                    self._moves_to_front()
-                self._moves_append(moves, need, ahead=False)
-            if mv["ahead"] is not None:  # the launch waits for the copy stream's last upload
-                ctx.call("nh_stream_wait_marker", mv["ahead"])
-                mv["ahead"] = None
+            # the device (uploaded ahead by `launched`) unless this is the first call
+            want = min(ring.KSTEPS, iterations - it)
+            slice0 = ring.reserve(moves, want)
             if len(self._rl_pending) >= 2:
                 # launch n + 1 is queued only once launch n - 1 is known to have ended well (launch
                 # n is running meanwhile: the device does not wait for this)
                 gave_up = self._rl_settle(keep=1)
                 if gave_up is not None:
                     return self._rollback(gave_up)
-            rec = self._run_resident(2 * mv["used"], 2 * want, block)
+            rec = self._run_resident(slice0, 2 * want, block)
             if rec is None:
                 return it  # (gave up: the per-launch loop replays these steps)
             if not self.shared:  # (a shared loop's launches are checked where all ranks are)
                 rec["it"] = it
                 self._rl_pending.append(rec)
-            mv["used"] += want
-            # a marker behind this launch: `blk` is a ring, and the host runs launches ahead of
-            # the device -- an upload on the copy stream may overlap THIS launch (whose steps lie
-            # below `have`), but must wait for every earlier one, which may still be reading the
-            # very bytes it is about to overwrite once the ring has wrapped
-            mv["prev"] = mv["last"]
-            mv["last"] = self._launch_marks[self._nlaunch % 3]
-            self._nlaunch += 1
-            ctx.call("nh_marker_record", mv["last"])
-            if mv["have"] - mv["used"] < self.KSTEPS and \
-                    mv["have"] + self.KSTEPS <= self.MOVES_CAP:
-                self._moves_append(moves, self.KSTEPS, ahead=True)
+            ring.launched(moves, want)
             it += want
             self._advance(want, block, jentry)
             if it >= iterations and self._rl_pending:
@@ -874,40 +825,25 @@ class DeviceLoop:
                            blob_dev_hist, whole):
         """steps it .. iterations of the call, a block of KSTEPS moves uploaded at a time, with one
         launch per half-step, a graph of several steps, or the resident loop for a block's rest"""
-        s, ctx, mv, N, ns = self.s, self.ctx, self._mv, self.N, self.ns
+        s, ctx, ring, N = self.s, self.ctx, self.ring, self.N
         if self.fused:
             # (the per-launch kernel's history descriptor: where its launches append the chain)
             words = [block["coords"].ptr, block["logp"].ptr, 0, block["coords"].shape[0]] \
-                if dev_hist \
-                else [0, 0, 0, 0]
+                if dev_hist else [0, 0, 0, 0]
             if blob_dev_hist:
                 words = words + [hb.ptr for hb in block["blobs"]]
             words = (words + [0, 0, 0, 0])[:8]
             ctx.call("nh_set_words", self.histd, (C.c_longlong * 8)(*words), 8)
         moves = s.moves(pinned=True)
         if it < iterations:
-            mv["prev"] = mv["last"] = None  # (see _moves_append)
+            ring.forget_launches()
         while it < iterations:
             self._flush_pending()  # (merged sharded mode) the block's last accept
             self._sync_cur_blobs()  # (launches per half-step keep every rank's blobs whole)
             self._cur_host = None
             # ---- ship the moves of the next K steps: ONE asynchronous upload from the
             # generator's page-locked ring (filled ahead by its worker thread) ----------
-            # nh_moves_take's contract: only the copy of the MOST RECENT take may still be
-            # queued when the next one is taken (the generator hands a used-up block back
-            # one block late, so that copy's source is still intact); every earlier upload
-            # has to be complete -- wait on the marker recorded after it
-            while len(self._inflight) >= 2:
-                ctx.call("nh_marker_wait", self._inflight.pop(0))
-            if mv["have"] > mv["used"]:
-                # steps of the move stream the resident loop uploaded ahead and did not use: they
-                # come first (to the front of `blk`, where this loop expects its block)
-                K = min(mv["have"] - mv["used"], self.KSTEPS, iterations - it)
-                self._moves_to_front(K)
-            else:
-                mv["have"] = mv["used"] = 0
-                addr, K = moves.take(min(self.KSTEPS, iterations - it))
-                ctx.call("nh_upload", self.blk, addr, 8 * 2 * K * 3 * ns)
+            K = ring.next_block(moves, iterations - it)
             if self.fused:
                 if self.mega and self._plan["hs"] is not None:
                     # (the one-launch kernel writes the cursor itself, every launch)
@@ -921,10 +857,8 @@ class DeviceLoop:
                         self._front()  # slice 0 of the new block
             else:
                 ctx.call("nh_memset", self.cursor, 0, 4)
-            mark = self._markers[self._nmark % len(self._markers)]
-            self._nmark += 1
-            mark_pending = True  # recorded behind the block's first launch: the host gets
-            self._inflight.append(mark)  # that one out first (any later point is as good)
+            # (recorded behind the block's first launch: the host gets that one out first)
+            mark, mark_pending = ring.block_mark(), True
             k = 0
             while k < K:
                 self._pos["slice"], self._pos["steps"] = 2 * k, (block["n"] - k) if dev_hist else 0
@@ -939,11 +873,7 @@ class DeviceLoop:
                     if k > 0 and dev_hist:
                         # the per-launch kernel leaves the history row of a closed step to the
                         # NEXT launch of the block: there is none, the resident loop takes over
-                        ctx.call("nh_hist_append", self.coords, self.logp, N, self.ndim,
-                                 self.histd, block["n"] - 1)
-                        if blob_dev_hist:
-                            ctx.call("nh_half_step_append_blobs", self._plan["hs"]["plan"],
-                                     block["n"] - 1)
+                        self._append_closed_row(block, blob_dev_hist)
                     self._flush_pending()
                     if self._run_resident(2 * k, 2 * g, block if dev_hist else None) is None:
                         continue  # (gave up: _resident_ok() is false from now on)
@@ -993,62 +923,16 @@ class DeviceLoop:
                     # a block, and whoever is handed this state may read the chain (nobody
                     # does between the graphs of one run_mcmc call: yield_every > iterations)
                     self._flush_pending()
-                    ctx.call("nh_hist_append", self.coords, self.logp, N, self.ndim, self.histd,
-                             block["n"] - 1)
-                    if blob_dev_hist:
-                        ctx.call("nh_half_step_append_blobs", self._plan["hs"]["plan"],
-                                 block["n"] - 1)
+                    self._append_closed_row(block, blob_dev_hist)
                 yield DeviceState(self, s._rng)
 
-    # ------------------------------------------------------------- the move stream on the device
-    def _moves_append(self, moves, n, ahead):
-        """the next n steps of the move stream (fewer if the generator's piece ends earlier and
-        `ahead`) behind the ones `blk` holds; ahead: on the copy stream, beside the running
-        launch (nh_upload_ahead), else on the main stream"""
-        ctx, mv, sb = self.ctx, self._mv, 8 * 2 * 3 * self.ns
-        done = 0
-        while done < n:
-            # nh_moves_take's contract: only the copy of the MOST RECENT take may still be
-            # queued when the next one is taken
-            while len(self._inflight) >= 2:
-                ctx.call("nh_marker_wait", self._inflight.pop(0))
-            addr, got = moves.take(n - done)
-            mark = self._markers[self._nmark % len(self._markers)]
-            self._nmark += 1
-            dst = self.blk.ptr + sb * mv["have"]
-            if ahead:
-                # (the first ahead-upload of a loop waits for the launch just queued: whatever
-                # ran before it -- the per-launch loop's graphs read `blk` too -- is then done)
-                ctx.call("nh_upload_ahead", dst, addr, sb * got, mark,
-                         mv["prev"] if mv["prev"] is not None else mv["last"])
-                mv["ahead"] = mark
-            else:
-                ctx.call("nh_upload", dst, addr, sb * got)
-                ctx.call("nh_marker_record", mark)
-            self._inflight.append(mark)
-            mv["have"] += got
-            done += got
-
-    def _moves_to_front(self, k=None):
-        """the unused steps `blk` holds (the first k of them) move to its front, in stream order
-        behind whatever still reads the block; with k the loop that follows consumes them"""
-        ctx, mv, sb = self.ctx, self._mv, 8 * 2 * 3 * self.ns
-        avail = mv["have"] - mv["used"]
-        n = avail if k is None else k
-        if mv["ahead"] is not None:
-            ctx.call("nh_stream_wait_marker", mv["ahead"])
-            mv["ahead"] = None
-        if n > 0 and mv["used"] > 0:
-            if self._blk_tmp is None:
-                self._blk_tmp = ctx.empty((2 * self.MOVES_CAP, 3 * self.ns))
-            ctx.call("nh_copy", self._blk_tmp, self.blk.ptr + sb * mv["used"], sb * n)
-            ctx.call("nh_copy", self.blk, self._blk_tmp, sb * n)
-        if k is None:
-            mv["have"], mv["used"] = avail, 0
-        else:
-            mv["used"] += k  # (what is left stays where it is, behind the part now at the front)
-            if mv["used"] == mv["have"]:
-                mv["have"] = mv["used"] = 0
+    def _append_closed_row(self, block, blobs_too):
+        """the history row of the step the per-launch kernel closed last, which it leaves to the
+        next launch of the block of moves: there is none"""
+        self.ctx.call("nh_hist_append", self.coords, self.logp, self.N, self.ndim, self.histd,
+                      block["n"] - 1)
+        if blobs_too:
+            self.ctx.call("nh_half_step_append_blobs", self._plan["hs"]["plan"], block["n"] - 1)
 
     # ------------------------------------------------------------- resident loop
     def _resident_ok(self):
@@ -1077,16 +961,16 @@ class DeviceLoop:
                 return False
             self._run = h
             self._rl_count, self._rl_pending = 0, []  # (the library numbers a loop's launches from 1)
-            self._res["runs"].append(h)
-            self.ctx.sorted_tables(hs, h)
-            g, t, l = _lib._i(), _lib._i(), _lib._ll()
-            _lib._chk(_lib._lib.nh_half_step_run_info(h, C.byref(g), C.byref(t), C.byref(l)))
-            self.resident_info = dict(grid=g.value, threads=t.value, lds_bytes=l.value,
-                                      **self._syn_info(h))
+            self._adopt_run(hs, h)
         return True
 
-    @staticmethod
-    def _syn_info(h):
+    def _adopt_run(self, hs, h):
+        """a resident loop that was created well: owned by this loop, its tables sorted, its
+        shape on record (resident_info)"""
+        self._res["runs"].append(h)
+        self.ctx.sorted_tables(hs, h)
+        g, t, l = _lib._i(), _lib._i(), _lib._ll()
+        _lib._chk(_lib._lib.nh_half_step_run_info(h, C.byref(g), C.byref(t), C.byref(l)))
         mode, m, pcs = _lib._i(), _lib._i(), _lib._i()
         _lib._chk(_lib._lib.nh_half_step_run_syn_info(h, C.byref(mode), C.byref(m), C.byref(pcs)))
         inreg, nmax = _lib._i(), _lib._i()
@@ -1095,9 +979,11 @@ class DeviceLoop:
         _lib._chk(_lib._lib.nh_half_step_run_split_info(h, C.byref(spl), C.byref(rows)))
         deep = _lib._i()
         _lib._chk(_lib._lib.nh_half_step_run_pipeline_info(h, C.byref(deep)))
-        return dict(syn_log_domain=bool(mode.value), syn_nodes_per_piece=m.value, syn_pieces=pcs.value,
-                    tables_in_registers=bool(inreg.value), workgroups_per_walker=spl.value,
-                    rows_split=bool(rows.value), two_walkers_in_flight=bool(deep.value))
+        self.resident_info = dict(
+            grid=g.value, threads=t.value, lds_bytes=l.value,
+            syn_log_domain=bool(mode.value), syn_nodes_per_piece=m.value, syn_pieces=pcs.value,
+            tables_in_registers=bool(inreg.value), workgroups_per_walker=spl.value,
+            rows_split=bool(rows.value), two_walkers_in_flight=bool(deep.value))
 
     def _create_shared_run(self, hs):
         """the resident loop over an ensemble shared with the other ranks' GPUs: rings in
@@ -1117,7 +1003,6 @@ class DeviceLoop:
                 lib.nh_half_step_run_destroy(ctx.h, h)
             self.resident_reason = msg
             if comm.rank == 0:
-                import warnings
                 warnings.warn("the resident loop over a shared ensemble is not available (%s): "
                               "one launch and one all-gather per half-step instead" % msg)
             return None
@@ -1151,12 +1036,7 @@ class DeviceLoop:
             ok, why = False, "refused on request (NAIMA_AMD_LADDER_REFUSE=ring: fault injection of the tests)"
         if not agreed(ok):
             return give_up("a record stored by another GPU did not reach a running kernel; %s" % why)
-        self._res["runs"].append(h)
-        ctx.sorted_tables(hs, h)
-        gr, t, l = _lib._i(), _lib._i(), _lib._ll()
-        _lib._chk(lib.nh_half_step_run_info(h, C.byref(gr), C.byref(t), C.byref(l)))
-        self.resident_info = dict(grid=gr.value, threads=t.value, lds_bytes=l.value,
-                                  **self._syn_info(h))
+        self._adopt_run(hs, h)
         self.shared_info = dict(ranks=comm.size, probe_us_per_exchange=us.value)
         return h
 
@@ -1176,80 +1056,14 @@ class DeviceLoop:
         if not self._cur_dirty:
             return
         self._cur_dirty = False
-        ctx, comm = self.ctx, self.s.comm
-        g, N = comm.group, self.N
-        stamps = np.empty(N, dtype=np.int32)
-        _lib._chk(_lib._lib.nh_half_step_run_counters(ctx.h, self._run, None,
+        stamps = np.empty(self.N, dtype=np.int32)
+        _lib._chk(_lib._lib.nh_half_step_run_counters(self.ctx.h, self._run, None,
                                                       stamps.ctypes.data, 2))
-        allst = np.array([np.frombuffer(p_, dtype=np.int32) for p_ in
-                          g.allgather_bytes(stamps.tobytes())])
-        owner, has = allst.argmax(axis=0), allst.max(axis=0) >= 0
-        mine = has & (owner == comm.rank)
-        stash = []
-        for cur, m, _, _ in self.cur_blobs or []:
-            host = cur.get().reshape(N, m)
-            # (in slabs of walkers: a gathered message is every rank's rows together, and the
-            # control plane refuses messages beyond 64 MiB)
-            step = max(1, (16 << 20) // (8 * m))
-            idx = np.arange(N)
-            for lo in range(0, N, step):
-                slab = (idx >= lo) & (idx < lo + step)
-                parts = g.allgather_bytes(np.ascontiguousarray(host[mine & slab]).tobytes())
-                for r, p_ in enumerate(parts):
-                    if r != comm.rank:
-                        host[has & (owner == r) & slab] = np.frombuffer(p_, dtype=float).reshape(-1, m)
+        hosts = [cur.get().reshape(self.N, m) for cur, m, _, _ in self.cur_blobs or []]
+        shared_merge.merge_current_blobs(self.s.comm.group, self.s.comm.rank, stamps, hosts)
+        for (cur, _, _, _), host in zip(self.cur_blobs or [], hosts):
             cur.set(host.ravel())
-            stash.append(host)
-        self._cur_host = stash  # (valid until a launch changes the blobs again)
-
-    def _merge_shared_block(self, block, n, c, l, per):
-        """the rows a shared ensemble's launches wrote, gathered from the ranks that moved each
-        walker (c [n][N][ndim], l [n][N], per[b] [n][N][m_b]: this rank's copies, completed in
-        place), blob rows of rejected moves filled from the row before.  Collective."""
-        comm = self.s.comm
-        g, N, ndim = comm.group, self.N, self.ndim
-        own = block["own"].get()[:n].reshape(n, N)
-        valid = np.zeros(n, dtype=bool)  # (rows of launches per half-step are whole on every rank)
-        for r0, r1 in block["shared_rows"]:
-            valid[r0:r1] = True
-        own[~valid] = -1
-        ms = [p_.shape[2] for p_ in per]
-        moved, acc = own >= 0, own > 0
-        rows_per = max(1, (16 << 20) // (N * (8 * (ndim + 1 + sum(ms)) + 1)))
-        for t0 in range(0, n, rows_per):
-            t1 = min(n, t0 + rows_per)
-            mv, ac = moved[t0:t1], acc[t0:t1]
-            flags = own[t0:t1].astype(np.int8).tobytes()
-            flags += b"\0" * (-len(flags) % 8)
-            payload = flags + c[t0:t1][mv].tobytes() + l[t0:t1][mv].tobytes() + \
-                b"".join(p_[t0:t1][ac].tobytes() for p_ in per)
-            for r, blob in enumerate(g.allgather_bytes(payload)):
-                if r == comm.rank:
-                    continue
-                nel = (t1 - t0) * N
-                o = np.frombuffer(blob, dtype=np.int8, count=nel).reshape(t1 - t0, N)
-                off = nel + (-nel % 8)
-                mv_r, ac_r = o >= 0, o > 0
-                cnt, cnta = int(mv_r.sum()), int(ac_r.sum())
-                c[t0:t1][mv_r] = np.frombuffer(blob, dtype=float, count=cnt * ndim,
-                                               offset=off).reshape(cnt, ndim)
-                off += 8 * cnt * ndim
-                l[t0:t1][mv_r] = np.frombuffer(blob, dtype=float, count=cnt, offset=off)
-                off += 8 * cnt
-                for p_, m in zip(per, ms):
-                    p_[t0:t1][ac_r] = np.frombuffer(blob, dtype=float, count=cnta * m,
-                                                    offset=off).reshape(cnta, m)
-                    off += 8 * cnta * m
-                moved[t0:t1] |= mv_r
-                acc[t0:t1] |= ac_r
-        if per:
-            cur0 = [(b_ if isinstance(b_, np.ndarray) else b_.get()).reshape(N, m)
-                    for b_, m in zip(block["cur0"], ms)]
-            for t in range(n):
-                rej = moved[t] & ~acc[t]
-                if rej.any():
-                    for p_, c0 in zip(per, cur0):
-                        p_[t][rej] = (p_[t - 1] if t > 0 else c0)[rej]
+        self._cur_host = hosts  # (valid until a launch changes the blobs again)
 
     def _run_resident(self, slice0, nslices, block):
         """queue a launch of the resident loop -> the books as it found them (_checkpoint, with the
@@ -1290,11 +1104,10 @@ class DeviceLoop:
         self._rl_count += 1
         books["launch"] = self._rl_count  # (the library numbers a loop's launches the same way)
         if probation:
-            st = _lib._i()
-            _lib._chk(_lib._lib.nh_half_step_run_status(ctx.h, self._run, C.byref(st)))
-            if st.value != 0:
+            st = self.resident_status()
+            if st != 0:
                 # (nothing consumed the launch's moves: the per-launch loop takes them from `blk`)
-                self._leave_resident(_GAVE_UP % st.value, "the block of moves is replayed "
+                self._leave_resident(_GAVE_UP % st, "the block of moves is replayed "
                                      "and the run continues with one launch per half-step", 1, books)
                 return None
             self._resident_trust += 1
@@ -1321,7 +1134,6 @@ class DeviceLoop:
     def _leave_resident(self, reason, then, failed, books, rewind=False):
         """the resident loop given up for good: `failed` launches of it void, the books back to
         `books` (with `rewind` the move stream too), the per-launch loop carries the run on"""
-        import warnings
         self.resident_reason = reason
         if self.s.comm.rank == 0:
             warnings.warn(reason + "; " + then)
@@ -1356,17 +1168,14 @@ class DeviceLoop:
     def _rewind_moves(self, steps):
         """the move stream made again from the seed (a fresh generator, every upload of the old one
         done) and its first `steps` steps skipped: the steps every loop of this sampler has made"""
-        s, mv = self.s, self._mv
-        while self._inflight:
-            self.ctx.call("nh_marker_wait", self._inflight.pop(0))
-        mv["have"] = mv["used"] = 0
-        mv["ahead"] = mv["prev"] = mv["last"] = None
+        s = self.s
+        self.ring.reset()
         old, s._moves = s._moves, None
         moves = s.moves(pinned=True)
         if old is not None:
             old.close()
         while steps > 0:
-            steps -= moves.take(min(self.KSTEPS, steps))[1]
+            steps -= moves.take(min(self.ring.KSTEPS, steps))[1]
 
     def _snapshot_cur_blobs(self):
         """device copies of the current blobs, in stream order ahead of the launch about to be
@@ -1384,6 +1193,13 @@ class DeviceLoop:
         for src, (cur, m, _, _) in zip(self._cur_snaps[k], self.cur_blobs):
             self.ctx.call("nh_copy", cur, src, 8 * self.N * m)
         self._cur_host = None
+
+    def _before_read(self):
+        """what comes before a download of the ensemble's state"""
+        self._flush_pending()
+        self._settle_before_read()  # (one GPU: the friendlier message, ahead of the status)
+        self.check_resident()
+        self.check_nan()
 
     def _settle_before_read(self):
         """somebody reads the state (or drains the counters) while launches of the resident loop
@@ -1434,7 +1250,7 @@ class DeviceLoop:
         """the last thing a flush does, and a reset (the sampler's, once ITS books are cleared):
         keep the ensemble every rank was found well at (here, where every rank is anyway, and
         not inside the next call: a 20-step call is a millisecond)"""
-        if getattr(self, "_sh_want", False):
+        if self._sh_want:
             self._sh_want = False
             if self.shared and self._have_state:
                 self._shared_snapshot()
@@ -1531,10 +1347,7 @@ class DeviceLoop:
         n, f = self._nan_pending, self._forbidden_pending
         self._nan_pending = self._forbidden_pending = 0
         if multi:
-            import struct
-            parts = self.s.comm.group.allgather_bytes(struct.pack("<qq", n, f))
-            n = sum(struct.unpack("<qq", p_)[0] for p_ in parts)
-            f = sum(struct.unpack("<qq", p_)[1] for p_ in parts)
+            n, f = (int(x) for x in shared_merge.sum_over_ranks(self.s.comm.group, (n, f)))
         self.s.prior_forbidden_proposals += f
         if n:
             self.s.nan_proposals += n
@@ -1565,22 +1378,19 @@ class DeviceLoop:
             # the one rank that reads its state here would leave the others waiting in their next
             # collective -- the launch that gave up is found there and replayed by all
             return
-        st = _lib._i(0)
-        if self._run:
-            _lib._chk(_lib._lib.nh_half_step_run_status(self.ctx.h, self._run, C.byref(st)))
-        bad = st.value
+        mine = bad = self.resident_status()
         if collective and self.s.comm is not None and self.s.comm.size > 1:
             bad = int(self.s.comm.group.reduce_scalar(float(bad), "max"))
             if bad == 0:
                 self._shared_verified()
             elif self.shared and self._sh_snap is not None and not self._replaying:
-                self._replay_shared(bad, st.value)
+                self._replay_shared(bad, mine)
                 return
         if bad != 0:
             raise _lib.NaimaHipError(
                 "the resident half-step loop timed out waiting for a walker's record (status "
                 "%d%s): its workgroups were not all resident%s.  Run with NAIMA_AMD_%s=0"
-                % (bad, "" if bad == st.value else ", on another rank",
+                % (bad, "" if bad == mine else ", on another rank",
                    ", or a rank of the shared ensemble fell behind or failed"
                    if self.shared else "", "SHARED" if self.shared else "RESIDENT"))
 
@@ -1670,7 +1480,6 @@ class DeviceLoop:
         except _lib.NaimaHipError:
             if self._plan.get("hs") is not None:
                 raise  # the plan exists: this was a real failure of a launch
-            import warnings
             warnings.warn("nh_half_step_create turned the one-launch plan down (%s); the device "
                           "loop keeps the three-launch half-step"
                           % _lib._lib.nh_last_error().decode())
@@ -1728,11 +1537,7 @@ class DeviceLoop:
             # to disk, as the reference's save_run does in its one process, analysis.py:366-471 --
             # is not left waiting for peers that are gone.)
             return
-        self._flush_pending()
-        self.check_resident(collective=True)
-        self.check_nan(collective=True)
-        self.ctx.check_general()  # (a per-walker grid longer than the general kernel's LDS)
-        self._sync_cur_blobs()
+        self._meet()
         s = self.s
         for block in self.hist:
             n = block["n"]
@@ -1743,7 +1548,10 @@ class DeviceLoop:
             per = [hb.get()[:n].reshape(n, self.N, m)
                    for hb, (cur, m, _, trail) in zip(block["blobs"], self.cur_blobs or [])]
             if self.shared and block.get("own") is not None:
-                self._merge_shared_block(block, n, c, l, per)
+                cur0 = [b_ if isinstance(b_, np.ndarray) else b_.get() for b_ in block["cur0"]]
+                shared_merge.merge_history_rows(
+                    s.comm.group, s.comm.rank, block["own"].get()[:n].reshape(n, self.N),
+                    block["shared_rows"], cur0, c, l, per)
             tb = block.get("thin_by", 1)
             if tb > 1:  # (several ranks: a thinned call's rows, full-rate up to here)
                 c, l, per = c[tb - 1::tb], l[tb - 1::tb], [a[tb - 1::tb] for a in per]
@@ -1769,9 +1577,7 @@ class DeviceLoop:
                 own = np.empty(self.N, dtype=np.int32)
                 _lib._chk(_lib._lib.nh_half_step_run_counters(self.ctx.h, self._run,
                                                               own.ctypes.data, None, 0))
-                self._acc_shared = np.zeros(self.N)
-                for p_ in s.comm.group.allgather_bytes(own.tobytes()):
-                    self._acc_shared += np.frombuffer(p_, dtype=np.int32)
+                self._acc_shared = shared_merge.sum_over_ranks(s.comm.group, own).astype(float)
             s.naccepted += self._acc_shared
         self.keep_verified()
         self._flushed_at = self._changes

@@ -1364,3 +1364,79 @@ def test_seeded_call_sequences_equal_the_host_loop(na):
                     assert_allclose(sd.coords, sh.coords, rtol=1e-8, err_msg=where)
         resident += d._dev.resident_launches if d._dev is not None else 0
     assert resident > 0  # (the device samplers took the resident loop)
+
+
+def test_move_ring_holds_the_stream_in_order(na):
+    """naima_amd.move_ring.MoveRing alone (uploads and copies, no model): whatever the two step
+    loops ask of it, rows [2*used, 2*have) of its block are the move stream's steps with the
+    ordinals the loops will consume next, bit for bit -- through appends, uploads ahead on the
+    copy stream, the wrap at MOVES_CAP, left-overs brought to the front for the per-launch loop,
+    a fresh take, and a reset.  Expected: the same seed's stream from an unpinned generator,
+    read on the host."""
+    import ctypes as C
+
+    from naima_amd import _lib
+    from naima_amd.move_ring import MoveRing
+    ctx, seed, N = _lib.get_context(), 1234, 8
+    ns = N // 2
+    ref, want = _lib.Moves(seed, N), []
+    while sum(len(w) for w in want) < 400:
+        addr, got = ref.take(32)
+        n = got * 2 * 3 * ns
+        want.append(np.frombuffer((C.c_double * n).from_address(addr), dtype=np.uint64)
+                    .reshape(got, 2 * 3 * ns).copy())
+    want = np.concatenate(want).reshape(-1, 3 * ns)  # [slice][3 ns]: two rows per step
+    ring = MoveRing(ctx, ns)
+    assert (ring.KSTEPS, ring.MOVES_CAP) == (32, 128)
+    moves = _lib.Moves(seed, N, pinned=True)
+    state = dict(next=0)  # ordinal of the step at `used`
+
+    def check(front=0):
+        """... and the `front` steps just handed to the per-launch loop lie at the block's front"""
+        ctx.sync()
+        if ring.ahead is not None:  # (the copy stream's upload: not the main stream's to wait for)
+            ctx.call("nh_marker_wait", ring.ahead)
+        assert 0 <= ring.have - ring.used <= ring.MOVES_CAP and ring.have <= ring.MOVES_CAP
+        blk = ring.blk.get().view(np.uint64)
+        o = state["next"]
+        assert np.array_equal(blk[:2 * front], want[2 * (o - front):2 * o])
+        assert np.array_equal(blk[2 * ring.used:2 * ring.have],
+                              want[2 * o:2 * (o + ring.have - ring.used)])
+
+    # 1. the resident loop: the ring passes MOVES_CAP once and ends with left-overs uploaded ahead
+    for steps in (32, 32, 32, 32, 20):
+        assert ring.reserve(moves, steps) == 2 * ring.used and ring.have - ring.used >= steps
+        check()
+        ring.launched(moves, steps)
+        state["next"] += steps
+        check()
+    assert (ring.used, ring.have) == (20, 52)
+
+    def block(limit):  # the per-launch loop's use: next_block, then a marker behind the block
+        K = ring.next_block(moves, limit)
+        ctx.call("nh_marker_record", ring.block_mark())
+        assert 1 <= K <= min(limit, ring.KSTEPS)
+        state["next"] += K
+        check(front=K)
+        return K
+
+    # 2. a limit smaller than the left-over; 3. the rest of it, then fresh takes
+    ring.forget_launches()
+    assert block(10) == 10 and (ring.used, ring.have) == (30, 52)
+    assert block(100) == 22 and (ring.used, ring.have) == (0, 0)
+    block(100)
+    block(7)
+    assert (ring.used, ring.have) == (0, 0)
+    # 4. reset, the stream made again up to the step the loops have reached (as the loop does);
+    # 5. the resident loop once more
+    ring.reset()
+    assert (ring.used, ring.have, ring.ahead, ring.prev, ring.last) == (0, 0, None, None, None)
+    check()
+    moves.close()
+    moves, skip = _lib.Moves(seed, N, pinned=True), state["next"]
+    while skip > 0:
+        skip -= moves.take(min(32, skip))[1]
+    assert ring.reserve(moves, 5) == 0 and (ring.used, ring.have) == (0, 5)
+    check()
+    ring.reset()
+    moves.close()

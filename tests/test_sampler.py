@@ -319,17 +319,51 @@ def test_save_run_layout_is_the_reference_hdf5_layout(tmp_path):
     assert r.data["flux"].unit == m.data["flux"].unit and r.run_info["n_run"] == 3
 
 
+class _ThreadGroup:
+    """an in-memory control plane for ranks that are threads: of(rank) is that rank's group"""
+
+    def __init__(self, size):
+        import threading
+        self.bar, self.slots = threading.Barrier(size), [None] * size
+
+    def allgather_bytes(self, rank, payload):
+        self.slots[rank] = bytes(payload)
+        self.bar.wait()
+        out = list(self.slots)
+        self.bar.wait()
+        return out
+
+    def of(self, rank):
+        import types
+        return types.SimpleNamespace(allgather_bytes=lambda p: self.allgather_bytes(rank, p))
+
+    def run(self, fn):
+        """fn(rank) on one thread per rank -> {rank: result}"""
+        import threading
+        results, errors = {}, []
+
+        def body(rank):
+            try:
+                results[rank] = fn(rank)
+            except Exception as e:  # pragma: no cover
+                errors.append(e)
+                self.bar.abort()
+
+        ts = [threading.Thread(target=body, args=(r,)) for r in range(len(self.slots))]
+        [t.start() for t in ts]
+        [t.join(60) for t in ts]
+        assert not errors, errors
+        return results
+
+
 def test_shared_ensemble_history_merge_on_two_ranks():
-    """DeviceLoop._merge_shared_block (host arithmetic only; the launches that produce its input
+    """shared_merge.merge_history_rows (host arithmetic only; the launches that produce its input
     are covered on the GPU by test_gpu_loops.py::test_shared_ensemble_two_ranks_one_gpu): rows a
     shared ensemble's launches wrote hold, on each rank, only the walkers that rank moved (flags
     -1 | 0 | 1); rows of launches per half-step are whole everywhere.  Two ranks (threads, an
     in-memory control plane) each end with the full chain, blob rows of rejected moves filled
     from the row before (the blobs of where the walker IS, as emcee keeps them)."""
-    import threading
-    import types
-
-    from naima_amd.device_sampler import DeviceLoop
+    from naima_amd import shared_merge
 
     n, N, ndim, ms = 7, 10, 3, (4, 1)
     rng = np.random.default_rng(5)
@@ -350,50 +384,72 @@ def test_shared_ensemble_history_merge_on_two_ranks():
     for a, b in shared_rows:
         shared[a:b] = True
 
-    class Group:
-        def __init__(self):
-            self.bar, self.slots = threading.Barrier(2), [None, None]
-
-        def allgather_bytes(self, rank, payload):
-            self.slots[rank] = bytes(payload)
-            self.bar.wait()
-            out = list(self.slots)
-            self.bar.wait()
-            return out
-
-    group, results, errors = Group(), {}, []
+    group = _ThreadGroup(2)
 
     def run(rank):
-        try:
-            mine = shared[:, None] & (owner == rank)
-            whole = ~shared[:, None] & np.ones((n, N), dtype=bool)
-            c = np.where((mine | whole)[:, :, None], truth_c, np.nan)
-            l = np.where(mine | whole, truth_l, np.nan)
-            per = [np.where(whole[:, :, None], tb, np.where((mine & accepted)[:, :, None], b, np.nan))
-                   for tb, b in zip(truth_b, prop)]
-            own = np.where(mine, accepted.astype(np.int32), -1).astype(np.int32)
-            own[~shared] = rng.integers(-1, 2, size=(int((~shared).sum()), N))  # (never written: anything)
-            g = types.SimpleNamespace(allgather_bytes=lambda p, r=rank: group.allgather_bytes(r, p))
-            fake = types.SimpleNamespace(
-                s=types.SimpleNamespace(comm=types.SimpleNamespace(group=g, rank=rank, size=2)),
-                N=N, ndim=ndim)
-            block = dict(own=types.SimpleNamespace(get=lambda: own.copy()), shared_rows=shared_rows,
-                         cur0=[x.copy() for x in cur0])
-            DeviceLoop._merge_shared_block(fake, block, n, c, l, per)
-            results[rank] = (c, l, per)
-        except Exception as e:  # pragma: no cover
-            errors.append(e)
-            group.bar.abort()
+        mine = shared[:, None] & (owner == rank)
+        whole = ~shared[:, None] & np.ones((n, N), dtype=bool)
+        c = np.where((mine | whole)[:, :, None], truth_c, np.nan)
+        l = np.where(mine | whole, truth_l, np.nan)
+        per = [np.where(whole[:, :, None], tb, np.where((mine & accepted)[:, :, None], b, np.nan))
+               for tb, b in zip(truth_b, prop)]
+        own = np.where(mine, accepted.astype(np.int32), -1).astype(np.int32)
+        own[~shared] = rng.integers(-1, 2, size=(int((~shared).sum()), N))  # (never written: anything)
+        shared_merge.merge_history_rows(group.of(rank), rank, own, shared_rows,
+                                        [x.copy() for x in cur0], c, l, per)
+        return c, l, per
 
-    ts = [threading.Thread(target=run, args=(r,)) for r in (0, 1)]
-    [t.start() for t in ts]
-    [t.join(60) for t in ts]
-    assert not errors, errors
+    results = group.run(run)
     for rank in (0, 1):
         c, l, per = results[rank]
         assert np.array_equal(c, truth_c) and np.array_equal(l, truth_l)
         for have, want in zip(per, truth_b):
             assert np.array_equal(have, want)
+
+
+def test_shared_ensemble_current_blob_merge_on_three_ranks(monkeypatch):
+    """shared_merge.merge_current_blobs: each walker's current blobs are held by the rank that
+    accepted its last move -- the one with the largest stamp; a walker that never accepted
+    (stamp -1 on every rank: 2 and 7) keeps the row every rank already has.  With slabs of three
+    walkers of the 4-wide blob (four messages; the 1-wide blob travels in one), three ranks each
+    end with the true arrays."""
+    from naima_amd import shared_merge
+
+    size, N, ms = 3, 10, (4, 1)
+    monkeypatch.setattr(shared_merge, "SLAB_BYTES", 8 * 4 * 3)
+    rng = np.random.default_rng(11)
+    never = np.isin(np.arange(N), (2, 7))
+    owner = rng.integers(0, size, size=N)
+    top = rng.permutation(N) + 5  # the owning rank's stamp: unique, above every other rank's
+    stamps = np.array([np.where(owner == r, top, rng.integers(-1, 5, size=N)) for r in range(size)],
+                      dtype=np.int32)
+    stamps[:, never] = -1
+    assert set(owner[~never]) == set(range(size))  # (every rank sends and receives)
+    truth = [rng.normal(size=(N, m)) for m in ms]
+    group = _ThreadGroup(size)
+
+    def run(rank):
+        held = never | (owner == rank)
+        hosts = [np.where(held[:, None], t, np.nan) for t in truth]
+        shared_merge.merge_current_blobs(group.of(rank), rank, stamps[rank].copy(), hosts)
+        return hosts
+
+    results = group.run(run)
+    for rank in range(size):
+        for have, want in zip(results[rank], truth):
+            assert np.array_equal(have, want)
+
+
+def test_sum_over_ranks_adds_small_integer_arrays():
+    """shared_merge.sum_over_ranks: the (NaN, forbidden) pair of check_nan and the acceptance
+    counts of flush, whatever integer type they arrive in"""
+    from naima_amd import shared_merge
+
+    group = _ThreadGroup(3)
+    vals = [np.array([1, 2 ** 40, 0]), np.array([3, 4, 5], dtype=np.int32), (7, 8, 9)]
+    results = group.run(lambda rank: shared_merge.sum_over_ranks(group.of(rank), vals[rank]))
+    for rank in range(3):
+        assert results[rank].tolist() == [11, 2 ** 40 + 12, 14]
 
 
 def test_control_plane_client_does_not_take_itself_for_the_hub():
