@@ -74,7 +74,7 @@ if __name__ == "__main__":
     dev = getattr(sampler, "_dev", None)
     if dev is not None and dev._plan is not None:
         print("half-step: %s" % ("two launches of the half-step kernel around the SSC integral"
-                                 if dev._plan.get("staged") else "separate kernels"))
+                                 if dev._plan.staged else "separate kernels"))
     out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "crab_synssc_run")
     naima.save_run(out, sampler, clobber=True)
     back = naima.read_run(out)

@@ -351,7 +351,7 @@ class Context:
         self._accept_hook = None
         self._cap_pool = {}
         self._retained = []
-        self._release_later = []  # device loops collected during a stream capture
+        self._release_later = []  # what to call after a stream capture (loops collected during it)
         self._deferred = []
         self._pinned = set()
         self._pinned_ptrs = set()
@@ -421,57 +421,32 @@ class Context:
                 self.call(p[0], *p[1])
         self._deferred = [a for a in self._deferred if a.pending is not None]
 
-    # -- launches that the device step loop folds into nh_step_front ------------------
-    # The loop first RECORDS what a model evaluation asks for (parameter packs, the
-    # particle-weights launch, single-row reductions such as We; persistent output
-    # buffers), then has nh_step_front produce all of it right after the proposal; in
-    # REPLAY mode a request only checks that it is the recorded one and returns its
-    # buffers.
-    def plan_begin(self):
-        self._plan = dict(mode="record", packs=[], weights=[], moments=[], i=[0, 0, 0, 0, 0],
-                          emit=[], calls=[], mega=False, hs=None, bufs=[])
-        return self._plan
-
-    def _replayed(self, kind, slot, key):
+    # -- requests of a model evaluation that the device step loop records and replays -----
+    # The loop first RECORDS what a model evaluation asks for (step_plan.StepPlan: parameter
+    # packs, the particle-weights launch, single-row reductions such as We; persistent output
+    # buffers), then has nh_step_front produce all of it right after the proposal; while
+    # the plan REPLAYS, a request only checks that it is the recorded one and returns its
+    # buffers.  The loop puts the plan of the evaluation in progress into ``_plan``.
+    def _replayed(self, kind, key, label=None):
         plan = self._plan
-        if plan is None or plan["mode"] != "replay":
-            return None
-        i = plan["i"][slot]
-        if i >= len(plan[kind]) or plan[kind][i][0] != key:
-            raise NaimaHipError("the model's launch sequence changed between evaluations (%s); "
-                                "run the sampler with use_graph=False" % kind)
-        plan["i"][slot] = i + 1
-        return plan[kind][i][1]
+        return plan.replayed(kind, key, label)[1] if plan is not None and plan.replaying else None
 
     def _recorded(self, kind, key, value):
-        if self._plan is not None and self._plan["mode"] == "record":
-            self._plan[kind].append((key, value))
-        return value
+        return value if self._plan is None else self._plan.record(kind, key, value)
 
     def plan_buffer(self, key, shape):
         """an output buffer of a launch that is NOT one of the step loop's recorded kinds (the SSC
         seed integral) but whose result the likelihood reads: the same buffer at every
         evaluation of a recorded plan, so that the plan's component pointers stay what they
         were; a fresh one outside a plan"""
-        plan = self._plan
-        if plan is None:
-            return self.empty(shape)
-        if plan["mode"] == "record":
-            buf = self.empty(shape)
-            plan["bufs"].append((key, buf))
-            return buf
-        i = plan["i"][4]
-        if i >= len(plan["bufs"]) or plan["bufs"][i][0] != key:
-            raise NaimaHipError("the model's launch sequence changed between evaluations (%s); "
-                                "run the sampler with use_graph=False" % (key[0],))
-        plan["i"][4] = i + 1
-        return plan["bufs"][i][1]
+        hit = self._replayed("bufs", key, key[0])
+        return hit if hit is not None else self._recorded("bufs", key, self.empty(shape))
 
     def pack_rows(self, cols, ncols, N):
         """out[N][ncols] from lazy columns (one nh_pack_rows launch unless replayed)"""
         import ctypes as C
         key = (bytes(C.string_at(C.addressof(cols), C.sizeof(cols))), ncols, N)
-        hit = self._replayed("packs", 0, key)
+        hit = self._replayed("packs", key)
         if hit is not None:
             return hit
         out = self.empty((N, ncols))
@@ -484,7 +459,7 @@ class Context:
         from .darray import nh_grid
         key = (kind, rows.ptr, N, tuple((g[0].ptr, g[1].ptr, g[2].ptr, g[3].ptr, g[4], g[5])
                                         for g in grids))
-        hit = self._replayed("weights", 1, key)
+        hit = self._replayed("weights", key)
         if hit is not None:
             return hit
         desc = (nh_grid * len(grids))()
@@ -500,19 +475,15 @@ class Context:
         """REPLAY mode: the grids and buffers of the recorded weights launch (the grid
         bookkeeping of the radiative classes is shared state and is bypassed), else None"""
         plan = self._plan
-        if plan is None or plan["mode"] != "replay":
+        if plan is None or not plan.replaying:
             return None
-        i = plan["i"][1]
-        if i >= len(plan["weights"]) or plan["weights"][i][0][:3] != (kind, rows.ptr, N):
-            raise NaimaHipError("the model's launch sequence changed between evaluations "
-                                "(weights); run the sampler with use_graph=False")
-        plan["i"][1] = i + 1
-        return plan["weights"][i][0][3], plan["weights"][i][1]
+        key, bufs = plan.replayed("weights", (kind, rows.ptr, N))
+        return key[3], bufs
 
     def moment(self, w, lw, N, nG, lx, Kt, dlnKt):
         """out[N] = trapz_loglog(n * K, x) for ONE table row K (We, Wp)"""
         key = (w.ptr, lw.ptr, N, nG, lx.ptr, Kt.ptr, dlnKt.ptr)
-        hit = self._replayed("moments", 2, key)
+        hit = self._replayed("moments", key)
         if hit is not None:
             return hit
         out = self.empty((N, 1))
@@ -554,21 +525,20 @@ class Context:
                                 "(at most ~4600) or lower nEed" % (n, self.general_nmax))
 
     # -- emission launches of a model evaluation ------------------------------------------
-    # In the one-launch-per-half-step mode of the device loop (plan["mega"]) these are not
+    # In the one-launch-per-half-step mode of the device loop (the plan's ``mega``) these are not
     # launched at all: nh_half_step produces every spectrum of the model, into buffers that
     # belong to the plan.  While a half-step is RECORDED they run as usual and leave their
-    # arguments in plan["emit"]; outside the step loop they are plain launches.
+    # arguments in the plan; outside the step loop they are plain launches.
     def _emit_replayed(self, kind, key, shape):
-        plan = self._plan
-        i = plan["i"][3]
-        if i >= len(plan["emit"]) or plan["emit"][i]["key"] != key:
-            raise NaimaHipError("the model's launch sequence changed between evaluations (%s); "
-                                "run the sampler with use_graph=False" % kind)
-        plan["i"][3] = i + 1
-        ent = plan["emit"][i]
-        if ent["out"] is None:
-            ent["out"] = self.empty(shape)
-        return ent["out"]
+        ent = self._plan.replayed("emit", key, kind)[1]
+        if ent.out is None:
+            ent.out = self.empty(shape)
+        return ent.out
+
+    def _rides(self, N, n):
+        """device step loop: may this launch be held back for the likelihood to ride on it?"""
+        hook = self._accept_hook
+        return hook is not None and not hook.used and hook.N == N and n <= 64 and not self._deferred
 
     def emit_tables(self, w, lw, N, nG, lx, Kt, dlnKt, nK, scale, nonneg, may_split=True):
         """out[N][nK] = scale[k] * trapz_loglog(n K_k, x) for every walker (nh_integrate_tables).
@@ -576,18 +546,14 @@ class Context:
         plan = self._plan
         key = ("tab", w.ptr, lw.ptr, N, nG, lx.ptr, Kt.ptr, dlnKt.ptr, nK,
                scale.ptr if scale is not None else 0, int(nonneg))
-        if plan is not None and plan["mega"] and plan["mode"] == "replay":
+        if plan is not None and plan.mega and plan.replaying:
             return self._emit_replayed("tables", key, (N, nK)), 1
         ns = _lib.nh_integrate_tables_nsplit(N, nG, nK) if may_split else 1
         out = self.empty((ns * N, nK))
         args = (w, lw, N, nG, lx, Kt, dlnKt, nK, scale, out, nK, int(nonneg), ns)
-        if plan is not None and plan["mode"] == "record":
-            plan["emit"].append(dict(kind="tab", key=key, out=None, N=N,
-                                     keep=(w, lw, lx, Kt, dlnKt, scale)))
-        hook = self._accept_hook
-        if hook is not None and not hook["used"] and hook["N"] == N and nK <= 64 and ns == 1 \
-                and not self._deferred:
-            # device step loop: hold the launch back, the likelihood may ride on it
+        if plan is not None and not plan.replaying:
+            plan.record_emission(key, N, keep=(w, lw, lx, Kt, dlnKt, scale))
+        if ns == 1 and self._rides(N, nK):
             self.defer(out, "nh_integrate_tables", args)
         else:
             self.call("nh_integrate_tables", *args)
@@ -597,233 +563,20 @@ class Context:
         """out[N][nE] = Synchrotron._spectrum of every walker (nh_synchrotron)"""
         plan = self._plan
         key = ("syn", w.ptr, lw.ptr, int(Bp), int(ldB), N, gd.ptr, lx.ptr, nG, Ed.ptr, nE)
-        if plan is not None and plan["mega"] and plan["mode"] == "replay":
-            if plan.get("staged"):
-                return self._stage_a(plan, key, N, nE)
+        if plan is not None and plan.mega and plan.replaying:
+            if plan.staged:
+                return plan.stage_a(self, key, N, nE)
             return self._emit_replayed("synchrotron", key, (N, nE))
         out = self.empty((N, nE))
         args = (w, lw, Bp, ldB, N, gd, lx, nG, Ed, nE, out, nE)
-        if plan is not None and plan["mode"] == "record":
-            plan["emit"].append(dict(kind="syn", key=key, out=None, N=N, keep=(w, lw, gd, lx, Ed) + tuple(keep),
-                                     E_host=None if E_host is None else np.array(E_host, dtype=float)))
-        hook = self._accept_hook
-        if hook is not None and not hook["used"] and hook["N"] == N and nE <= 64 \
-                and not self._deferred:
+        if plan is not None and not plan.replaying:
+            plan.record_emission(key, N, keep=(w, lw, gd, lx, Ed) + tuple(keep),
+                                 E_host=None if E_host is None else np.array(E_host, dtype=float))
+        if self._rides(N, nE):
             self.defer(out, "nh_synchrotron", args, keep=keep)
         else:
             self.call("nh_synchrotron", *args)
         return out
-
-    def _hs_front(self, d, f):
-        """the part of an nh_hs_desc every plan of a device loop shares: the ensemble, the block of
-        moves, the parameter packs, the grids (returns {weights pointer: grid index})"""
-        for name in ("coords", "logp", "blk", "cursor", "qT", "factors"):
-            setattr(d, name, f[name])
-        d.ns, d.ndim, d.lo, d.nloc = f["ns"], f["ndim"], f["lo"], f["nloc"]
-        pk, npk, kind, rows_ptr, gd, ngr, mm, nmm = f["front_args"]
-        for q in range(npk):
-            d.packs[q] = pk[q]
-        d.npacks, d.kind, d.params = npk, kind, rows_ptr
-        wgrid = {}
-        for g in range(ngr):
-            d.grids[g] = gd[g]
-            wgrid[gd[g].w] = g
-        d.ngrids = ngr
-        return wgrid
-
-    def _stage_a(self, plan, key, N, nE):
-        """A model that asks for its synchrotron spectrum TWICE -- at the energies of a seed photon
-        field it then builds from it, and at the data's (examples/CrabNebula_SynSSC.py:29-45) --
-        with launches of other kernels in between (the SSC seed integral batches sixteen WALKERS
-        per wave: nothing a one-workgroup-per-walker launch can absorb): the half-step is two
-        nh_half_step launches around them.  Stage A, launched where the model asks for the first
-        spectrum: proposal -> packs -> weights (written to HBM for the kernels in between) ->
-        ONE synchrotron component over both sets of energies, no accept.  Stage C is the plan's
-        own launch (Context.half_step): proposal, packs and weights again (a few microseconds),
-        the table reductions, the spectra of the launches in between and stage A's from HBM,
-        likelihood, accept."""
-        import ctypes as C
-
-        from . import darray as D
-        i = plan["i"][3]
-        ent = plan["emit"][i] if i < len(plan["emit"]) else None
-        if ent is None or ent["key"] != key:
-            raise NaimaHipError("the model's launch sequence changed between evaluations "
-                                "(synchrotron); run the sampler with use_graph=False")
-        plan["i"][3] = i + 1
-        syn = [e for e in plan["emit"] if e["kind"] == "syn"]
-        st = plan.get("stage")
-        if st is None:
-            e1, e2 = syn
-            n1, n2 = e1["key"][10], e2["key"][10]
-            base = self.empty((N * (n1 + n2),))
-            e1["out"] = DeviceArray(self, base.ptr, (N, n1), np.float64, 0)
-            e2["out"] = DeviceArray(self, base.ptr + 8 * N * n1, (N, n2), np.float64, 0)
-            Ecat = self.array(np.concatenate([e1["E_host"], e2["E_host"]]))
-            f = plan["front"]
-            d = D.nh_hs_desc()
-            wgrid = self._hs_front(d, f)
-            rows_ptr = f["front_args"][3]
-            d.hist = None
-            d.do_accept, d.write_weights = 0, 1
-            d.nmoms, d.ntab = 0, 0
-            _, w, lw, Bp, ldB, _, gdp, lx, nG, _, _ = e1["key"]
-            in_rows = ldB == NH_PD_NPAR and 0 <= Bp - rows_ptr < 8 * NH_PD_NPAR
-            d.syn = D.nh_hs_syn(wgrid[w], n1 + n2, n1, (Bp - rows_ptr) // 8 if in_rows else -1, ldB,
-                                n1, Ecat.ptr, None if in_rows else Bp, base.ptr,
-                                base.ptr + 8 * N * n1, n2, 0)
-            # (a launch has a likelihood: this one's is of the first spectrum against columns of
-            # ones and zeros, into a buffer nobody reads)
-            ones, zeros = self.array(np.ones(n1)), self.array(np.zeros(n1))
-            izero = self.array(np.zeros(n1, dtype=np.int32), dtype=np.int32)
-            half = self.array(np.full(n1, 0.5))
-            dummy = self.empty((N,))
-            d.comps[0] = D.nh_comp(base.ptr, n1, 1.0)
-            d.ncomp, d.nE = 1, n1
-            d.conv, d.flux, d.err_lo, d.err_hi = ones.ptr, zeros.ptr, ones.ptr, ones.ptr
-            d.ul, d.cl, d.lp, d.nterms = izero.ptr, half.ptr, None, 0
-            # the prior of the recorded evaluation: a proposal it forbids is integrated by nobody
-            # (its synchrotron spectrum is written as zeros, the seed field made of it is empty and
-            # the SSC kernel packs such walkers out of its groups: k_ssc_order) -- as the plan's
-            # own launch does for it
-            pt = plan.get("prior_terms")
-            if pt is not None:
-                for q in range(pt[1]):
-                    d.terms[q] = pt[0][q]
-                d.nterms = pt[1]
-            d.model_out, d.total, d.nblobs, d.send_width = None, dummy.ptr, 0, 0
-            h = _dp()
-            _chk(_lib.nh_half_step_create(self.h, C.addressof(d), C.byref(h)))
-            st = plan["stage"] = dict(plan=h, keep=(base, Ecat, ones, zeros, izero, half, dummy))
-            # the span clock: this launch opens the half-step's span, the plan's own closes it
-            _chk(_lib.nh_half_step_span(h, 1, 0))
-            self.call("nh_half_step_begin_block", h, f["pos"]["slice"], 0)
-        if ent is syn[0]:
-            pos = plan["front"]["pos"]
-            self.call("nh_half_step_launch", st["plan"], pos["slice"] if pos["bake"] else -1)
-        return ent["out"]
-
-    def half_step(self, hook, comps, ncomp, nE, conv, dd, lpd, terms, nterms, total, blobs=()):
-        """the plan's nh_half_step launch: everything the recorded model evaluation asked
-        for plus the likelihood of ``comps`` (created on first use, then checked and reused)"""
-        import ctypes as C
-
-        from . import darray as D
-        plan = self._plan
-        if plan["i"][3] != len(plan["emit"]):
-            raise NaimaHipError("the model's launch sequence changed between evaluations "
-                                "(fewer emission components); run with use_graph=False")
-        key = (bytes(C.string_at(C.addressof(comps), C.sizeof(comps))), ncomp, nE, conv.ptr,
-               lpd.ptr if lpd is not None else 0,
-               bytes(C.string_at(C.addressof(terms), C.sizeof(terms))) if nterms else b"",
-               total.ptr)
-        hs = plan["hs"]
-        if hs is not None:
-            if hs["key"] != key:
-                raise NaimaHipError("the model's likelihood inputs changed between evaluations; "
-                                    "run the sampler with use_graph=False")
-            self.call("nh_half_step_launch", hs["plan"],
-                      plan["front"]["pos"]["slice"] if plan["front"]["pos"]["bake"] else -1)
-            return
-        f = plan["front"]  # filled in by the device loop when it chose this mode
-        d = D.nh_hs_desc()
-        for name in ("coords", "logp", "blk", "cursor", "qT", "factors", "hist",
-                     "accepted", "naccepted", "sel"):
-            setattr(d, name, f[name])
-        d.ns, d.ndim, d.lo, d.nloc = f["ns"], f["ndim"], f["lo"], f["nloc"]
-        d.do_accept, d.write_weights = int(hook["mv"] is not None), 0
-        pk, npk, kind, rows_ptr, gd, ngr, mm, nmm = f["front_args"]
-        for q in range(npk):
-            d.packs[q] = pk[q]
-        d.npacks, d.kind, d.params = npk, kind, rows_ptr
-        wgrid = {}
-        for g in range(ngr):
-            d.grids[g] = gd[g]
-            wgrid[gd[g].w] = g
-        d.ngrids = ngr
-        for q in range(nmm):
-            d.moms[q] = mm[q]
-        d.nmoms = nmm
-        d.syn.grid = -1
-        nt = 0
-        tabs = []  # (what the resident loop sorts the columns of: sorted_tables)
-        for ent in plan["emit"]:
-            k = ent["key"]
-            if ent["kind"] == "tab":
-                _, w, lw, N, nG, lx, Kt, dKt, nK, sc, nonneg = k
-
-                def interleaved(Kt=Kt, dKt=dKt, nG=nG, nK=nK, lx=lx, nonneg=nonneg):
-                    kd = self.empty((2 * nG * nK,))
-                    # (a non-negative table carries its log-ratios in units of lx)
-                    self.call("nh_table_interleave", Kt, dKt, lx if nonneg else None, nG, nK, kd)
-                    return kd
-
-                kd = self.table(("kd", Kt, dKt, nG * nK, bool(nonneg)), interleaved)
-                self._pinned.add(("kd", Kt, dKt, nG * nK, bool(nonneg)))  # the plan points into it
-                d.tab[nt] = D.nh_hs_table(wgrid[w], nK, nK, nonneg, kd.ptr, None, sc or None,
-                                          ent["out"].ptr)
-                tabs.append((Kt, dKt, nG, nK, lx, bool(nonneg)))
-                nt += 1
-            elif plan.get("staged"):
-                pass  # (stage A's launch has produced it: the likelihood reads it from HBM)
-            else:
-                _, w, lw, Bp, ldB, N, gdp, lx, nG, Ed, nEs = k
-                in_rows = ldB == NH_PD_NPAR and 0 <= Bp - rows_ptr < 8 * NH_PD_NPAR
-                d.syn = D.nh_hs_syn(wgrid[w], nEs, nEs, (Bp - rows_ptr) // 8 if in_rows else -1,
-                                    ldB, 0, Ed, None if in_rows else Bp, ent["out"].ptr, None, 0, 0)
-        d.ntab = nt
-        for q in range(ncomp):
-            d.comps[q] = comps[q]
-        d.ncomp, d.nE = ncomp, nE
-        d.conv, d.flux, d.err_lo, d.err_hi = conv.ptr, dd.flux.ptr, dd.elo.ptr, dd.ehi.ptr
-        d.ul, d.cl = dd.ul.ptr, dd.cl.ptr
-        d.lp = lpd.ptr if lpd is not None else None
-        for q in range(nterms):
-            d.terms[q] = terms[q]
-        d.nterms = nterms
-        d.model_out, d.total = None, total.ptr
-        # blobs the launch keeps itself (the device loop says where: hook["blobs"]); anything
-        # it cannot express leaves them to the separate staging / scatter launches
-        hook["blobs_in_kernel"] = False
-        blobs = [b for b in blobs if not isinstance(b, (float, int))]  # (lnprob's constant NaN)
-        dest = hook.get("blobs")
-        if dest and (hook["mv"] is not None or hook.get("send_width")) and \
-                len(dest) == len(blobs) <= 4:
-            from . import units as u
-            model_terms = [(int(comps[q].ptr), int(comps[q].ld), float(comps[q].scale))
-                           for q in range(ncomp)]
-            mouts = [mm[q].out for q in range(nmm)]
-            ent = []
-            for (cur, m, hist_word), b in zip(dest, blobs):
-                v = b.value if isinstance(b, u.Quantity) else b
-                if isinstance(v, D.DMat) and v.colfac is None and v.shape[1] == nE == m and \
-                        [(int(t[1]), int(t[2]), float(t[3])) for t in v.terms] == model_terms:
-                    ent.append(D.nh_hs_blob(0, 0, m, 0, D.lazy_const(1.0), cur, hist_word))
-                elif isinstance(v, D.DVec) and m == 1 and v.stride == 1 and v.ptr in mouts:
-                    ent.append(D.nh_hs_blob(1, mouts.index(v.ptr), 1, 0, v.lazy(), cur, hist_word))
-                else:
-                    ent = None
-                    break
-            if ent is not None:
-                for q, e in enumerate(ent):
-                    d.blobs[q] = e
-                d.nblobs = len(ent)
-                d.send_width = int(hook.get("send_width") or 0) if hook["mv"] is None else 0
-                hook["rows_active"] = d.send_width
-                hook["blobs_in_kernel"] = True
-        h = _dp()
-        _chk(_lib.nh_half_step_create(self.h, C.addressof(d), C.byref(h)))
-        thr, blk, lds = _i(), _i(), _ll()
-        _chk(_lib.nh_half_step_info(h, C.byref(thr), C.byref(blk), C.byref(lds)))
-        spl = _i()
-        _chk(_lib.nh_half_step_split(h, C.byref(spl)))
-        if plan.get("staged"):  # (the span clock: stage A's launch has opened this half-step's span)
-            _chk(_lib.nh_half_step_span(h, 0, 1))
-        plan["hs"] = dict(key=key, plan=h, keep=(conv, lpd, total, dd), threads=thr.value,
-                          blocks=blk.value, lds_bytes=lds.value, split=spl.value, tabs=tabs)
-        # where the step loop stands in the current block of moves
-        self.call("nh_half_step_begin_block", h, f["pos"]["slice"], f["pos"]["steps"])
-        self.call("nh_half_step_launch", h, -1)
 
     def sorted_tables(self, hs, run):
         """the resident loop's own copies of the plan's tables, columns sorted by the first grid
@@ -836,7 +589,7 @@ class Context:
         if os.environ.get("NAIMA_AMD_SORTED_TABLES", "1") == "0":
             return
         ptrs, keep = (C.c_void_p * 4)(), []
-        for t, (Kt, dKt, nG, nK, lx, nonneg) in enumerate(hs.get("tabs", [])[:4]):
+        for t, (Kt, dKt, nG, nK, lx, nonneg) in enumerate(hs.tabs[:4]):
             tiles = (nK + 63) // 64
             if tiles > 8 or nG < 2:
                 continue
@@ -860,8 +613,8 @@ class Context:
             ptrs[t] = kd.ptr
             keep.append(kd)
         if keep:
-            _chk(_lib.nh_half_step_run_tables(self.h, hs["plan"], run, ptrs, 4))
-            hs.setdefault("sorted", []).append(keep)  # (alive as long as the plan)
+            _chk(_lib.nh_half_step_run_tables(self.h, hs.handle, run, ptrs, 4))
+            hs.sorted.append(keep)  # (alive as long as the plan)
 
     def array(self, host, dtype=np.float64):
         host = np.ascontiguousarray(host, dtype=dtype)
@@ -968,11 +721,9 @@ class Context:
 
     def _release_deferred(self):
         """device loops that were collected while a capture was in progress"""
-        if self._release_later:
-            from .device_sampler import _release_loop
-            later, self._release_later = self._release_later, []
-            for res in later:
-                _release_loop(self, res)
+        later, self._release_later = self._release_later, []
+        for release in later:
+            release()
 
     def graph_abort(self):
         if self.capturing:
@@ -1051,8 +802,8 @@ class Context:
         """invoke an entry point; DeviceArray arguments are passed as their pointers"""
         conv = [a.ptr if isinstance(a, DeviceArray) else a for a in args]
         plan = self._plan
-        if plan is not None and plan["mode"] == "record" and self._in_eval:
-            plan["calls"].append(name)
+        if plan is not None and not plan.replaying and self._in_eval:
+            plan.calls.append(name)
         _chk(getattr(_lib, name)(self.h, *conv))
 
     def close(self):

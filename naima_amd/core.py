@@ -153,23 +153,22 @@ def lnprobmodel(model, data, lp=None, blobs=()):
         if nE != dd.n:
             raise ValueError("model has %d energies, data table has %d" % (nE, dd.n))
         hook = ctx._accept_hook
-        if hook is not None and (hook["N"] != N or hook["used"]):
+        if hook is not None and (hook.N != N or hook.used):
             hook = None
         # the sharded step loop wants the result in its all-gather send buffer
-        total = hook["total"] if hook is not None and hook.get("total") is not None \
-            else ctx.empty((N,))
-        if hook is not None and hook.get("total_rows") is not None:
-            total = hook["total_rows"]  # rows { lnprob | blobs }: see Context.half_step
+        total = hook.total if hook is not None and hook.total is not None else ctx.empty((N,))
+        if hook is not None and hook.total_rows is not None:
+            total = hook.total_rows  # rows { lnprob | blobs }: see StepPlan.half_step
         lpd = terms = None
         nterms = 0
         if isinstance(lp, LazyPrior):
             terms, nterms = lp.packed()  # evaluated inside the likelihood kernel
             if terms is None:
                 lpd = lp.evaluate()
-            elif ctx._plan is not None and ctx._plan["mode"] == "record":
+            elif ctx._plan is not None and not ctx._plan.replaying:
                 # (a staged plan's first launch evaluates the prior too: a proposal it forbids
-                # gets no synchrotron spectrum, hence no seed photons -- Context._stage_a)
-                ctx._plan["prior_terms"] = (terms, nterms)
+                # gets no synchrotron spectrum, hence no seed photons -- StepPlan.stage_a)
+                ctx._plan.prior_terms = (terms, nterms)
         elif lp is not None:
             lpd = lp.dense()
         args = (m.comps(), len(m.terms), N, nE, dd.conv(model.unit, m.colfac),
@@ -178,19 +177,19 @@ def lnprobmodel(model, data, lp=None, blobs=()):
         owners = [t[0] for t in m.terms]
         held = [j for j, o in enumerate(owners) if getattr(o, "pending", None) is not None]
         plan = ctx._plan
-        if hook is not None and plan is not None and plan["mega"] and plan["mode"] == "replay":
+        if hook is not None and plan is not None and plan.mega and plan.replaying:
             # ONE launch for the whole half-step: proposal, packs, weights, We/Wp, every
             # spectrum of the model, this likelihood, the priors and the accept
-            ctx.half_step(hook, m.comps(), len(m.terms), nE, args[4], dd, lpd, terms, nterms, total,
-                          blobs=blobs)
-            hook["used"] = True
+            plan.half_step(ctx, hook, m.comps(), len(m.terms), nE, args[4], dd, lpd, terms, nterms,
+                           total, blobs=blobs)
+            hook.used = True
             del lpd
-            return DVec(ctx, total, total.ptr, N, stride=int(hook.get("rows_active") or 1))
+            return DVec(ctx, total, total.ptr, N, stride=hook.rows_active or 1)
         if hook is not None:
             # device step loop: the stretch move's accept rides on this launch (single
             # rank; sharded, the accept has to wait for the all-gather: mv is None)
             import ctypes as C
-            mv = C.addressof(hook["mv"]) if hook["mv"] is not None else None
+            mv = C.addressof(hook.mv) if hook.mv is not None else None
             j = held[0] if len(held) == 1 else -1
             o = owners[j] if j >= 0 else None
             if o is not None and o.pending[0] == "nh_synchrotron" and m.terms[j][1] == o.ptr \
@@ -217,7 +216,7 @@ def lnprobmodel(model, data, lp=None, blobs=()):
                     ctx.call("nh_lnprob_accept", *args, mv)
                 else:
                     ctx.call("nh_lnprob", *args)
-            hook["used"] = True
+            hook.used = True
         else:
             ctx.flush(*owners)
             ctx.call("nh_lnprob", *args)

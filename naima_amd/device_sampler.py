@@ -18,6 +18,7 @@ capture no Python model code runs inside the loop.
 """
 import collections
 import ctypes as C
+import functools
 import os
 import warnings
 import weakref
@@ -25,6 +26,7 @@ import weakref
 import numpy as np
 
 from . import _lib, shared_merge
+from .step_plan import AcceptHook, Front, StepPlan
 from . import units as u
 from .darray import DEbl, DMat, DPars, DVec
 from .dist import shard_bounds, shard_counts
@@ -71,7 +73,7 @@ def _release_loop(ctx, res):
     if ctx.capturing:
         # (the collector may run this in the middle of ANOTHER loop's stream capture, which a
         # synchronisation would invalidate: the context releases it after the capture)
-        ctx._release_later.append(res)
+        ctx._release_later.append(functools.partial(_release_loop, ctx, res))
         return
     try:
         ctx.sync()
@@ -81,12 +83,7 @@ def _release_loop(ctx, res):
             _lib._lib.nh_half_step_run_destroy(ctx.h, r)
         res["runs"] = []
         for plan in res["plans"]:
-            for key in ("hs", "stage") if plan else ():
-                hs = plan.get(key)
-                if hs is not None and hs.get("plan") is not None:
-                    _lib._lib.nh_half_step_destroy(ctx.h, hs["plan"])
-                    hs["plan"] = None
-                    plan[key] = None
+            plan.destroy(ctx)
     except Exception:
         pass
     res["graphs"], res["plans"] = [], []
@@ -158,7 +155,6 @@ class DeviceLoop:
         self._pos = dict(slice=0, steps=0, bake=False)
         self.multi_graphs = {}
         self._plan = None
-        self._front_args = None
         self.done = ctx.empty((1,), dtype=np.int32)
         ctx.call("nh_memset", self.done, 0, 4)
         self._hook = None
@@ -248,6 +244,11 @@ class DeviceLoop:
         self.thin_info = None
         self._finalizer = weakref.finalize(self, _release_loop, self.ctx, self._res)
 
+    @property
+    def _hs(self):
+        """the created one-launch plan (step_plan.OneLaunch), None while there is none"""
+        return self._plan.hs if self._plan else None
+
     # ------------------------------------------------------------------ pieces
     def reset(self):
         """forget the chain and the acceptance counts (the sampler clears its host copies): the
@@ -279,7 +280,7 @@ class DeviceLoop:
             self.ctx._in_eval = False
         self.s.n_lnprob_calls += 1
         self.s.n_walker_evals += n
-        rows = bool(self._hook and self._hook.get("rows_active")) and self.ctx._accept_hook is self._hook
+        rows = bool(self._hook and self._hook.rows_active) and self.ctx._accept_hook is self._hook
         total = res[0] if rows else res[0].dense()  # (rows: exchanged as they are)
         blobs = list(res[1:])
         # plain numbers among the blobs (lnprob's (model, nan) for a model that returns no
@@ -310,9 +311,9 @@ class DeviceLoop:
         ctx = self.ctx
         if self.fused:
             # proposal, parameter rows, weights, We: written by the preceding nh_step_front
-            self._plan["i"] = [0, 0, 0, 0, 0]
+            self._plan.rewind()
             ctx._plan = self._plan
-            self._hook["used"] = False
+            self._hook.used = False
             ctx._accept_hook = self._hook
         else:
             ctx.call("nh_move_propose", self.coords, self.blk, self.cursor, self.ns, self.ndim,
@@ -326,7 +327,7 @@ class DeviceLoop:
         if self.sharded:
             # fixed hand-over buffer so that the two graphs and the collective between
             # them always see the same addresses
-            if self._hook and self._hook.get("rows_active"):
+            if self._hook and self._hook.rows_active:
                 pass  # rows { lnprob | blobs } are exchanged as the launch wrote them
             elif total.ptr != self.mylp.ptr:  # (the fused likelihood wrote it there itself)
                 ctx.call("nh_copy", self.mylp, total.ptr, 8 * self.nloc)
@@ -340,7 +341,7 @@ class DeviceLoop:
         """copy the proposal's blobs into fixed staging buffers (only when kept)"""
         if not (self.s.store_blobs and self.cur_blobs):
             return
-        if self.mega and self._hook.get("blobs_in_kernel"):
+        if self.mega and self._hook.blobs_in_kernel:
             self.blobs_in_kernel = True  # the half-step launch keeps the blobs itself
             return
         if self.new_blobs is None:
@@ -361,7 +362,7 @@ class DeviceLoop:
             ctx.call("nh_move_accept_rows", self.coords, self.logp, self.blk, self.cursor,
                      self.recv_rows, self.send_width, self.ns, self.ndim, self.accepted, self.nacc,
                      self.sel, 0, nb, cur, mm)
-        elif not (self.fused and self._hook and self._hook["used"] and self._hook["mv"] is not None):
+        elif not (self.fused and self._hook and self._hook.used and self._hook.mv is not None):
             # not accepted by the likelihood's own launch: the separate kernels (which also advance
             # the cursor: 1), sharded (the accept waits for the all-gather), a foreign likelihood
             ctx.call("nh_move_accept", self.coords, self.logp, self.blk, self.cursor,
@@ -380,7 +381,7 @@ class DeviceLoop:
         reductions (+ chain history, cursor advance): one launch"""
         self.ctx.call("nh_step_front", self.coords, self.logp, self.blk, self.cursor, self.done,
                       self.ns, self.ndim, self.lo, self.nloc, self.qT, self.factors,
-                      *self._front_args, self.histd)
+                      *self._plan.front.step_front_args(), self.histd)
 
     def _record_half_step(self):
         """a half-step launched piece by piece while the model's parameter packs, weights
@@ -388,14 +389,14 @@ class DeviceLoop:
         the loop switches to it"""
         from .darray import nh_accept, nh_grid, nh_lazy, nh_moment, nh_pack
         ctx = self.ctx
-        plan = ctx.plan_begin()
+        plan = ctx._plan = StepPlan()
         try:
             self._half_step_body()
         finally:
             ctx._plan = None
         if not self.s.fuse_moves:
             return
-        packs, weights, moments = plan["packs"], plan["weights"], plan["moments"]
+        packs, weights, moments = plan.packs, plan.weights, plan.moments
         if not (1 <= len(packs) <= 4 and len(weights) == 1 and len(moments) <= 4):
             return
         lo_a = self.qT.ptr
@@ -429,103 +430,42 @@ class DeviceLoop:
             lds_nodes.add(wptr[w])
         if 40 * sum(grids[g][5] for g in lds_nodes) * max(len(moments), 1) > 48 * 1024:
             return
-        plan["mode"] = "replay"
+        plan.replaying = True
         ctx.pin_caches()
         self._plan = plan
         self._res["plans"].append(plan)
-        self._front_args = (pk, len(packs), kind, rows_ptr, gd, len(grids), mm, len(moments))
+        # (pos: the loop's own dict, changed as the loop goes and read when a launch is made)
+        plan.front = Front(self.coords.ptr, self.logp.ptr, self.blk.ptr, self.cursor.ptr, self._pos,
+                           self.qT.ptr, self.factors.ptr, self.histd.ptr, self.accepted.ptr,
+                           self.nacc.ptr, self.sel.ptr, self.ns, self.ndim, self.lo, self.nloc,
+                           pk, len(packs), kind, rows_ptr, gd, len(grids), mm, len(moments))
         if not self.sharded:
-            self._hook = dict(N=self.nloc, used=False, total=None,
-                              mv=nh_accept(self.coords.ptr, self.logp.ptr, self.blk.ptr,
-                                           self.cursor.ptr, self.ns, self.ndim, self.lo, 0,
-                                           self.accepted.ptr, self.nacc.ptr, self.sel.ptr))
+            self._hook = AcceptHook(self.nloc, mv=nh_accept(
+                self.coords.ptr, self.logp.ptr, self.blk.ptr, self.cursor.ptr, self.ns, self.ndim,
+                self.lo, 0, self.accepted.ptr, self.nacc.ptr, self.sel.ptr))
         else:  # sharded: likelihood into the all-gather send buffer, accept afterwards
-            self._hook = dict(N=self.nloc, used=False, total=self.mylp, mv=None)
+            self._hook = AcceptHook(self.nloc, total=self.mylp)
         self.fused = True
-        self.mega = self._can_be_one_launch(plan, grids, wptr, moments)
+        self.mega = plan.mega = plan.can_be_one_launch(self.nloc)
         if self.mega:
-            plan["mega"] = True
-            plan["front"] = dict(coords=self.coords.ptr, logp=self.logp.ptr, blk=self.blk.ptr,
-                                 cursor=self.cursor.ptr, pos=self._pos, qT=self.qT.ptr,
-                                 factors=self.factors.ptr, hist=self.histd.ptr,
-                                 accepted=self.accepted.ptr, naccepted=self.nacc.ptr,
-                                 sel=self.sel.ptr, ns=self.ns, ndim=self.ndim, lo=self.lo,
-                                 nloc=self.nloc, front_args=self._front_args)
-            if self._hook.get("total") is None:
-                self._hook["total"] = ctx.empty((self.nloc,))  # persistent: the plan points at it
+            if self._hook.total is None:
+                self._hook.total = ctx.empty((self.nloc,))  # persistent: the plan points at it
             if self.s.store_blobs and self.cur_blobs:
-                self._hook["blobs"] = [(cur.ptr, m, self.blobhist_ptr + 8 * i)
-                                       for i, (cur, m, _, _) in enumerate(self.cur_blobs)]
+                self._hook.blobs = [(cur.ptr, m, self.blobhist_ptr + 8 * i)
+                                    for i, (cur, m, _, _) in enumerate(self.cur_blobs)]
                 if self.sharded:
                     # the blobs travel with the log-probabilities: ONE all-gather of rows
                     # { lnprob | blob 0 | blob 1 ... } per half-step
                     self.send_width = 1 + sum(m for _, m, _, _ in self.cur_blobs)
-                    self._hook["send_width"] = self.send_width
+                    self._hook.send_width = self.send_width
                     self.send_rows = ctx.empty((max(self.nloc, 1), self.send_width))
                     self.recv_rows = ctx.empty((self.ns, self.send_width))
-                    self._hook["total_rows"] = self.send_rows
+                    self._hook.total_rows = self.send_rows
         # new slice protocol: cursor = the slice accepted last.  The two piecewise
         # half-steps (slices 0 and 1 of the first block) left it at 2.
         self.cursor.set(np.array([1], dtype=np.int32))
         if not self.mega:
             self._front()
-
-    def _can_be_one_launch(self, plan, grids, wptr, moments):
-        """every launch the recorded model evaluation made is one nh_half_step absorbs, and
-        its working set fits in one workgroup's LDS"""
-        if os.environ.get("NAIMA_AMD_MEGA", "1") == "0":
-            return False
-        allowed = {"nh_pack_rows", "nh_particle_weights_multi", "nh_integrate_tables",
-                   "nh_synchrotron", "nh_lnprob"}
-        emit = plan["emit"]
-        ntab = sum(1 for e in emit if e["kind"] == "tab")
-        nsyn = len(emit) - ntab
-        # A model that takes its synchrotron spectrum twice with launches of other kernels in
-        # between -- the SSC seed of examples/CrabNebula_SynSSC.py:29-45: Synchrotron.flux at the
-        # seed's energies, a linear combination, the seed integral (sixteen walkers per wave: not
-        # a one-workgroup-per-walker job), Synchrotron.flux at the data's -- runs as TWO launches
-        # of the half-step kernel around those (Context._stage_a): plan["staged"]
-        between = {"nh_lincomb", "nh_ic_seed_walkers_tab", "nh_ic_seed_walkers"}
-        staged = nsyn == 2 and bool(set(plan["calls"]) & between)
-        if staged:
-            syn = [e for e in emit if e["kind"] == "syn"]
-            if os.environ.get("NAIMA_AMD_STAGED", "1") == "0" or emit[0]["kind"] != "syn" or \
-                    syn[0]["key"][1:9] != syn[1]["key"][1:9] or \
-                    any(e.get("E_host") is None for e in syn) or moments:
-                return False
-            allowed = allowed | between
-            nsyn = 1
-        if not set(plan["calls"]) <= allowed or not emit or ntab > 4 or nsyn > 1:
-            return False
-        if plan["calls"].count("nh_lnprob") != 1:
-            return False
-        # every integrate call is either a recorded single-row reduction or an emission table
-        if plan["calls"].count("nh_integrate_tables") != ntab + len(moments) or \
-                plan["calls"].count("nh_synchrotron") != (2 if staged else nsyn):
-            return False
-        lds = 88 + 3 * sum(g[5] for g in grids) + sum(2 * grids[wptr[m[0][0]]][5] for m in moments)
-        items = nspec = 0
-        for e in emit:
-            k = e["key"]
-            if e["N"] != self.nloc or k[1] not in wptr:
-                return False
-            if e["kind"] == "tab":
-                nG, nK = k[4], k[8]
-                items += ((nK + 63) // 64) * ((nG - 1 + 31) // 32)
-                nspec += nK
-            elif not staged:
-                nG, nE = k[8], k[10]
-                lds += 3 * nG + 4 * nE + 1 + 32 * nE
-                nspec += nE
-        lds += min(items, 96) * 64 + nspec
-        if staged:  # its other launch: one synchrotron component over both sets of energies
-            nG, nEa = syn[0]["key"][8], syn[0]["key"][10] + syn[1]["key"][10]
-            cd = max(1, min(32, (40 * 1024) // (8 * nEa)))
-            lds = max(lds, 88 + 6 * nG + (5 + cd) * nEa + 8 * syn[0]["key"][10])
-        if 8 * lds > 140 * 1024:
-            return False
-        plan["staged"] = staged
-        return True
 
     def _gather_rows(self, send_ptr, recv, n, width):
         """all-gather of rows of `width` doubles, rank r contributing its block of the n rows
@@ -758,7 +698,7 @@ class DeviceLoop:
         (None: no history) from its row block["n"] on"""
         # the launches append the chain history themselves (the nh_hist descriptor) when the
         # call keeps one and the launch's plan exists; else one pair of copies per step ...
-        dev_hist = self.fused and block is not None and not (self.mega and self._plan["hs"] is None)
+        dev_hist = self.fused and block is not None and not (self.mega and self._hs is None)
         # ... and the blobs' histories too, in the one-launch mode
         blob_dev_hist = dev_hist and self.blobs_in_kernel
         # several steps per launch need whatever the call keeps to be kept by the launches
@@ -845,12 +785,12 @@ class DeviceLoop:
             # generator's page-locked ring (filled ahead by its worker thread) ----------
             K = ring.next_block(moves, iterations - it)
             if self.fused:
-                if self.mega and self._plan["hs"] is not None:
+                if self.mega and self._hs is not None:
                     # (the one-launch kernel writes the cursor itself, every launch)
-                    ctx.call("nh_half_step_begin_block", self._plan["hs"]["plan"], 0,
+                    ctx.call("nh_half_step_begin_block", self._hs.handle, 0,
                              block["n"] if dev_hist else 0)
-                    if self._plan.get("stage") is not None:  # (its other launch: Context._stage_a)
-                        ctx.call("nh_half_step_begin_block", self._plan["stage"]["plan"], 0, 0)
+                    if self._plan.stage is not None:  # (its other launch: StepPlan.stage_a)
+                        ctx.call("nh_half_step_begin_block", self._plan.stage.handle, 0, 0)
                 else:
                     ctx.call("nh_memset", self.cursor, 0xFF, 4)  # -1: nothing accepted yet
                     if not self.mega:
@@ -932,19 +872,19 @@ class DeviceLoop:
         self.ctx.call("nh_hist_append", self.coords, self.logp, self.N, self.ndim, self.histd,
                       block["n"] - 1)
         if blobs_too:
-            self.ctx.call("nh_half_step_append_blobs", self._plan["hs"]["plan"], block["n"] - 1)
+            self.ctx.call("nh_half_step_append_blobs", self._hs.handle, block["n"] - 1)
 
     # ------------------------------------------------------------- resident loop
     def _resident_ok(self):
         """can the rest of a block of moves run as ONE launch (nh_half_step_run)?  Needs the
         one-launch plan, a single rank, blobs (if kept) kept by the launch; the library has
         the last word (LDS, occupancy, the plan's shape)"""
-        if self._run is False or not self.mega or not self.s.use_graph or self._plan.get("staged"):
+        if self._run is False or not self.mega or not self.s.use_graph or self._plan.staged:
             return False
         if self.sharded and (self.s.comm.size < 2 or getattr(self.s.comm, "group", None) is None
                              or os.environ.get("NAIMA_AMD_SHARED", "1") == "0"):
             return False
-        hs = self._plan["hs"] if self._plan else None
+        hs = self._hs
         if hs is None:
             return False
         if self.s.store_blobs and self.cur_blobs and not self.blobs_in_kernel:
@@ -955,7 +895,7 @@ class DeviceLoop:
             return self.shared
         if self._run is None:
             h = _lib._dp()
-            if _lib._lib.nh_half_step_run_create(self.ctx.h, hs["plan"], C.byref(h)) != 0:
+            if _lib._lib.nh_half_step_run_create(self.ctx.h, hs.handle, C.byref(h)) != 0:
                 self._run = False
                 self.resident_reason = _lib._lib.nh_last_error().decode()
                 return False
@@ -1007,7 +947,7 @@ class DeviceLoop:
                               "one launch and one all-gather per half-step instead" % msg)
             return None
 
-        ok = lib.nh_half_step_run_create_shared(ctx.h, hs["plan"], comm.rank, comm.size,
+        ok = lib.nh_half_step_run_create_shared(ctx.h, hs.handle, comm.rank, comm.size,
                                                 C.byref(h)) == 0
         if not ok:
             why = lib.nh_last_error().decode()
@@ -1068,7 +1008,7 @@ class DeviceLoop:
     def _run_resident(self, slice0, nslices, block):
         """queue a launch of the resident loop -> the books as it found them (_checkpoint, with the
         launch's number and its copy of the current blobs), or None if it was checked and gave up"""
-        ctx, hs = self.ctx, self._plan["hs"]
+        ctx, hs = self.ctx, self._hs
         if self.shared:
             self._acc_dirty = True
             own = block.get("own") if block is not None else None
@@ -1100,7 +1040,7 @@ class DeviceLoop:
             books["counts"] = self._read_counts(reset=False)
         if block is None and not self.shared and self.s.store_blobs and self.cur_blobs:
             books["snap"] = self._snapshot_cur_blobs()
-        ctx.call("nh_half_step_run", hs["plan"], self._run, slice0, nslices, hc, hl, hb, row0, cap)
+        ctx.call("nh_half_step_run", hs.handle, self._run, slice0, nslices, hc, hl, hb, row0, cap)
         self._rl_count += 1
         books["launch"] = self._rl_count  # (the library numbers a loop's launches the same way)
         if probation:
@@ -1310,7 +1250,7 @@ class DeviceLoop:
     def _read_counts(self, reset, set_to=None):
         """(NaN log-probabilities, proposals forbidden by the prior) the kernels have counted on
         the device since the last reset"""
-        hs = self._plan["hs"] if self._plan else None
+        hs = self._hs
         extra = extra_f = 0
         if set_to is None:
             # launches of the separate kernels (cfg4; the first half-steps of any run): their
@@ -1320,12 +1260,12 @@ class DeviceLoop:
             extra = n.value
             _lib._chk(_lib._lib.nh_forbidden_count(self.ctx.h, 1 if reset else 0, C.byref(n)))
             extra_f = n.value
-        if hs is None or hs.get("plan") is None:
+        if hs is None or hs.handle is None:
             return extra, extra_f
         n, f = _lib._i(0), _lib._i(0)
         if set_to is not None:
             n, f = _lib._i(-set_to[0] - 1), _lib._i(-set_to[1] - 1)
-        _lib._chk(_lib._lib.nh_half_step_counts(self.ctx.h, hs["plan"], 1 if reset else 0,
+        _lib._chk(_lib._lib.nh_half_step_counts(self.ctx.h, hs.handle, 1 if reset else 0,
                                                 C.byref(n), C.byref(f)))
         return n.value + (extra if reset else 0), f.value + (extra_f if reset else 0)
 
@@ -1456,7 +1396,7 @@ class DeviceLoop:
             self._record_half_step()
             self.warm += 2
             return
-        if self.mega and self._plan["hs"] is None:
+        if self.mega and self._hs is None:
             # the first one-launch half-step creates the kernel's descriptor (device
             # allocation + upload): not inside a stream capture
             self._first_one_launch_half_step()
@@ -1471,24 +1411,21 @@ class DeviceLoop:
         ctx.graph_launch(self.step_graph)
 
     def _first_one_launch_half_step(self):
-        """the half-step that creates the one-launch plan.  _can_be_one_launch is an estimate
+        """the half-step that creates the one-launch plan.  StepPlan.can_be_one_launch is an estimate
         made from the recorded launches; nh_half_step_create has the last word (exact LDS
         layout, its admission rules).  If it turns the plan down, nothing has been launched
         yet for this half-step: the loop drops to the three-launch fused sequence for good."""
         try:
             self._half_step_body()
         except _lib.NaimaHipError:
-            if self._plan.get("hs") is not None:
+            if self._hs is not None:
                 raise  # the plan exists: this was a real failure of a launch
             warnings.warn("nh_half_step_create turned the one-launch plan down (%s); the device "
                           "loop keeps the three-launch half-step"
                           % _lib._lib.nh_last_error().decode())
-            self.mega = False
-            self._plan["mega"] = False
-            self._plan["staged"] = False
+            self.mega = self._plan.mega = self._plan.staged = False
             self.blobs_in_kernel = False
-            self._hook.pop("blobs", None)
-            self._hook.pop("blobs_in_kernel", None)
+            self._hook.reset(total=self.mylp if self.sharded else None)
             self._front()  # proposal + packs + weights of this slice, as a launch of its own
             self._half_step_body()
 
@@ -1511,7 +1448,7 @@ class DeviceLoop:
                 self._record_half_step()
             self.warm += 1
             return
-        if self.mega and self._plan["hs"] is None:
+        if self.mega and self._hs is None:
             self._first_one_launch_half_step()  # (never inside a capture)
             return
         if not s.use_graph:

@@ -47,7 +47,7 @@ def rate(model, data, nw, steps, warmup, per_launch):
     plan = getattr(d, "_plan", None)
     return dict(walker_steps_per_s=nw * steps / dt, seconds=dt, device=bool(s.device),
                 fused=bool(d.fused), mega=bool(d.mega),
-                launches_per_half_step=list(plan["calls"]) if plan else None,
+                launches_per_half_step=list(plan.calls) if plan else None,
                 acceptance=float(np.mean(s.acceptance_fraction)))
 
 

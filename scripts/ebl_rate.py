@@ -48,7 +48,7 @@ def rate(model, data, nw, steps, warmup):
     dt = time.perf_counter() - t0
     d = s._dev
     return dict(walker_steps_per_s=nw * steps / dt, seconds=dt, fused=bool(d.fused),
-                mega=bool(d.mega), launches_per_half_step=list(d._plan["calls"]),
+                mega=bool(d.mega), launches_per_half_step=list(d._plan.calls),
                 acceptance=float(np.mean(s.acceptance_fraction)))
 
 

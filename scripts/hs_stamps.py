@@ -20,13 +20,13 @@ s = EnsembleSampler(nw, p0.size, na.lnprob, args=[data, model, prior], seed=seed
 pos = p0 + ball * p0 * s._rng.normal(size=(nw, p0.size))
 st = s.run_mcmc(pos, burn, store=False)
 ctx.sync()
-hs = s._dev._plan["hs"]
-print(name, nw, "threads", hs["threads"], "blocks", hs["blocks"], "lds", hs["lds_bytes"])
+hs = s._dev._plan.hs
+print(name, nw, "threads", hs.threads, "blocks", hs.blocks, "lds", hs.lds_bytes)
 acc = []
 for rep in range(20):
     st = s.run_mcmc(st, 1, store=False)
     out = np.zeros(67840, dtype=np.int64)
-    _lib._chk(_lib._lib.nh_half_step_stamps(ctx.h, hs["plan"], out.ctypes.data))
+    _lib._chk(_lib._lib.nh_half_step_stamps(ctx.h, hs.handle, out.ctypes.data))
     acc.append(out[:128].reshape(8, 16)[:, :12].astype(float))
     last = out
 a = np.array(acc)  # [rep][block][phase]
@@ -38,13 +38,13 @@ for b in (0, 3, 7):
     print("block", b, " ".join("%s=%.2f" % (n, v) for n, v in zip(names, m[b])))
 t0 = last[0]
 print("block 0 per wave: item-phase start / end (us since block start), table items, syn items")
-for w in range(hs["threads"] // 64):
+for w in range(hs.threads // 64):
     print("  wave %2d: %.2f -> %.2f  tab %d syn %d" % (w, (last[176 + w] - t0) / 100.0, (last[128 + w] - t0) / 100.0, last[144 + w], last[160 + w]))
 print("block 0: each wave's arrival at the barrier that ends the weights phase (us):",
-      [round((last[192 + w] - t0) / 100.0, 2) for w in range(hs["threads"] // 64)])
+      [round((last[192 + w] - t0) / 100.0, 2) for w in range(hs.threads // 64)])
 print("block 0: each wave before its LDS fills / at the FIRST barrier (us):",
-      [(round((last[224 + w] - t0) / 100.0, 2), round((last[208 + w] - t0) / 100.0, 2)) for w in range(hs["threads"] // 64)])
-nb = hs["blocks"]
+      [(round((last[224 + w] - t0) / 100.0, 2), round((last[208 + w] - t0) / 100.0, 2)) for w in range(hs.threads // 64)])
+nb = hs.blocks
 st_, en_ = last[256:256 + nb].astype(float), last[1280:1280 + nb].astype(float)
 dur = (en_ - st_) / 100.0
 t00 = st_.min()
@@ -59,14 +59,14 @@ for w in worst[:2]:
     print("  workgroup %d:" % w, " ".join("%s=%.2f" % (n, v) for n, v in zip(names, (allst[w] - allst[w, 0]) / 100.0)))
     print("     per wave (end us, tab, syn):", [(round((pw[w, q, 0] - allst[w, 0]) / 100.0, 1), int(pw[w, q, 1]), int(pw[w, q, 2] & 255)) for q in range(16)],
           "nA", int(pw[w, 0, 2] >> 8 & 4095), "Cd", int(pw[w, 0, 2] >> 20))
-stage = s._dev._plan.get("stage")
+stage = s._dev._plan.stage
 if stage is not None:
-    # the staged plan's other launch (Context._stage_a): its phases the same way
+    # the staged plan's other launch (StepPlan.stage_a): its phases the same way
     import ctypes as C
     th, bl, ld = C.c_int(), C.c_int(), C.c_longlong()
-    _lib._chk(_lib._lib.nh_half_step_info(stage["plan"], C.byref(th), C.byref(bl), C.byref(ld)))
+    _lib._chk(_lib._lib.nh_half_step_info(stage.handle, C.byref(th), C.byref(bl), C.byref(ld)))
     out = np.zeros(67840, dtype=np.int64)
-    _lib._chk(_lib._lib.nh_half_step_stamps(ctx.h, stage["plan"], out.ctypes.data))
+    _lib._chk(_lib._lib.nh_half_step_stamps(ctx.h, stage.handle, out.ctypes.data))
     print("stage A: threads", th.value, "blocks", bl.value, "lds", ld.value)
     a1 = out[:128].reshape(8, 16)[:, :12].astype(float)
     for b in (0, 3, 7):

@@ -44,8 +44,8 @@ for i, b in enumerate(blobs):
         _, st = timed(s, st, steps)
     S.append(s)
     ST.append(st)
-    hs = s._dev._plan["hs"] if s._dev and s._dev._plan else None
-    print("sampler %d (blobs=%s) built; plan %s" % (i, b, {k: hs[k] for k in hs if k != "plan"} if hs else None),
+    hs = s._dev._plan.hs if s._dev and s._dev._plan else None
+    print("sampler %d (blobs=%s) built; plan %s" % (i, b, (hs.threads, hs.blocks, hs.lds_bytes, hs.split) if hs else None),
           flush=True)
     # every sampler built so far, alternately, three rounds
     for rnd in range(3):

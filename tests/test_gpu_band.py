@@ -420,7 +420,7 @@ def test_luminosity_blob_keeps_the_device_loop(na, problem):
         warnings.simplefilter("error")
         d.run_mcmc(pr["pos"], STEPS)
     assert d.device is True and d._dev is not None and d._dev.fused
-    assert "nh_trapz_loglog_comps" in d._dev._plan["calls"] and not d._dev.mega
+    assert "nh_trapz_loglog_comps" in d._dev._plan.calls and not d._dev.mega
     # the blob does not disturb the fit: the model without it (the resident loop), and the
     # host-driven loop of the model with it
     plain = _sampler(na, pr, pr["plain"], True)
@@ -479,8 +479,8 @@ def test_same_per_launch_loop_gives_the_same_chain_bit_for_bit(na, problem, monk
     assert np.array_equal(a.get_chain(), b.get_chain())
     assert np.array_equal(a.get_log_prob(), b.get_log_prob())
     assert np.array_equal(np.asarray(a.get_blobs()[1]), np.asarray(b.get_blobs()[1]))
-    extra = list(a._dev._plan["calls"])
-    for name in b._dev._plan["calls"]:
+    extra = list(a._dev._plan.calls)
+    for name in b._dev._plan.calls:
         extra.remove(name)
     print("launches the blob adds:", extra)
     assert "nh_trapz_loglog_comps" in extra
@@ -609,7 +609,7 @@ def test_integral_of_a_held_back_synchrotron_spectrum(na, problem):
         d.run_mcmc(d.run_mcmc(pr["pos"], 2), 4)
     h.run_mcmc(h.run_mcmc(pr["pos"], 2), 4)
     assert d.device and d._dev.fused and h.device is False
-    assert d._dev._plan["calls"].count("nh_trapz_loglog_comps") == 2
+    assert d._dev._plan.calls.count("nh_trapz_loglog_comps") == 2
     assert_allclose(d.get_chain(), h.get_chain(), rtol=1e-8)
     bd, bh = d.get_blobs(), h.get_blobs()
     assert len(bd) == len(bh) == 4

@@ -292,7 +292,7 @@ def test_one_launch_more_than_without_absorption(na, monkeypatch):
         _, d = _loops(na, 64, (0, 0), prior, model)
         d.run_mcmc(_pos(64), 4)
         assert d._dev.fused and not d._dev.mega
-        calls.append(list(d._dev._plan["calls"]))
+        calls.append(list(d._dev._plan.calls))
     plain, ebl = calls
     print("\nlaunches: without absorption %s, with %s" % (plain, ebl))
     assert "nh_ebl_apply" in ebl and len(ebl) <= len(plain) + 1

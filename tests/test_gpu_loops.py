@@ -113,7 +113,7 @@ def test_cfg4_at_its_baseline_ensemble_size(na):
     import ctypes as C
     from naima_amd import _lib
     form = C.c_int(0)
-    _lib._chk(_lib._lib.nh_half_step_syn_form(d._dev._plan["stage"]["plan"], C.byref(form)))
+    _lib._chk(_lib._lib.nh_half_step_syn_form(d._dev._plan.stage.handle, C.byref(form)))
     assert form.value == 2, form.value
     assert_allclose(d.get_chain(), h.get_chain(), rtol=1e-8)
     lh, ld = h.get_log_prob(), d.get_log_prob()
@@ -161,7 +161,7 @@ def test_register_resident_table_items_of_a_three_seed_model(na, monkeypatch, ki
         if mode in ("registers", "streamed"):
             info = d._dev.resident_info
             assert d._dev.resident_launches > 0 and info["tables_in_registers"] == (mode == "registers"), info
-            assert info["grid"] == nw // 2 and d._dev._plan["hs"]["split"] > 1, (info, d._dev._plan["hs"]["split"])
+            assert info["grid"] == nw // 2 and d._dev._plan.hs.split > 1, (info, d._dev._plan.hs.split)
         runs[mode] = (d.get_chain(), d.get_log_prob(), np.asarray(d.get_blobs()[0], dtype=float))
     a = runs["streamed"]
     for mode in ("registers", "per-launch"):
@@ -307,8 +307,8 @@ def test_one_launch_half_step_with_more_grid_nodes_than_register_units(na):
     sh, sd = h.run_mcmc(pos, 3), d.run_mcmc(pos, 3)
     sh, sd = h.run_mcmc(sh, 9), d.run_mcmc(sd, 9)
     dev = d._dev
-    assert dev is not None and dev.mega and dev._plan["hs"] is not None  # ONE launch per half-step
-    assert dev._plan["hs"]["threads"] == 1024
+    assert dev is not None and dev.mega and dev._plan.hs is not None  # ONE launch per half-step
+    assert dev._plan.hs.threads == 1024
     assert_allclose(sd.coords, sh.coords, rtol=1e-8)
     assert_allclose(sd.log_prob, sh.log_prob, rtol=1e-6)
     assert_allclose(d.get_chain(), h.get_chain(), rtol=1e-8)
@@ -334,9 +334,9 @@ def test_split_launch_equals_unsplit_launch(na, monkeypatch, cfg, nw, steps):
         d = EnsembleSampler(nw, nd, na.lnprob, device=True, **kw)
         st = d.run_mcmc(pos, 2)
         st = d.run_mcmc(st, steps - 2)
-        hs = d._dev._plan["hs"]
+        hs = d._dev._plan.hs
         assert hs is not None and d._dev.mega
-        runs[k] = (hs["split"], st, d.get_chain(), d.get_log_prob(), d.get_blobs(),
+        runs[k] = (hs.split, st, d.get_chain(), d.get_log_prob(), d.get_blobs(),
                    d.acceptance_fraction)
     assert runs["1"][0] == 1
     assert runs["8"][0] == (2 if nw == 256 else 8)  # (nw/2 walkers per launch, 256 CUs)
@@ -391,9 +391,9 @@ def test_split_launch_of_the_table_only_instance(na, monkeypatch):
         d = EnsembleSampler(nw, nd, na.lnprob, device=True, **kw)
         st = d.run_mcmc(pos, 2)
         st = d.run_mcmc(st, steps - 2)
-        hs = d._dev._plan["hs"]
+        hs = d._dev._plan.hs
         assert hs is not None and d._dev.mega
-        runs[k] = (hs["split"], d.get_chain(), d.get_log_prob(), d.get_blobs())
+        runs[k] = (hs.split, d.get_chain(), d.get_log_prob(), d.get_blobs())
     assert runs["1"][0] == 1 and runs["8"][0] > 1
     assert_allclose(runs["8"][1], runs["1"][1], rtol=1e-8)
     assert_allclose(runs["8"][2], runs["1"][2], rtol=1e-6)
@@ -538,7 +538,7 @@ def test_device_loop_equals_host_loop_from_the_benchmarks_ball(na, name, nw, loo
             # the steps both completed are compared.
             died = str(e)
     dev = d._dev
-    assert dev is not None and d.device and dev.mega and dev._plan["hs"] is not None
+    assert dev is not None and d.device and dev.mega and dev._plan.hs is not None
     assert dev.graph is not None or dev.step_graph is not None or dev.resident_launches > 0
     ch, cd = h.get_chain(), d.get_chain()
     lh, ld = h.get_log_prob(), d.get_log_prob()
@@ -612,12 +612,12 @@ def test_device_loop_equals_oracle_driven_sampler_at_the_benchmarks_size(na, nam
     assert dev is not None and dev.mega
     assert dev.resident_launches > 0, getattr(dev, "resident_reason", "")
     if name == "cfg3":
-        assert dev._plan["hs"]["split"] == 1 and dev._plan["hs"].get("sorted")
+        assert dev._plan.hs.split == 1 and dev._plan.hs.sorted
         assert dev.resident_info["syn_log_domain"]
     if name == "cfg1":
-        assert dev._plan["hs"].get("sorted")
+        assert dev._plan.hs.sorted
     if name == "cfg2":
-        assert dev._plan["hs"]["split"] == 2 and dev.resident_info["syn_log_domain"]
+        assert dev._plan.hs.split == 2 and dev.resident_info["syn_log_domain"]
 
     def oprior(q):
         return float(np.asarray(prior(q)))
@@ -690,6 +690,48 @@ def test_rejected_one_launch_plan_falls_back_to_the_three_launch_loop(na, monkey
                         atol=1e-300, equal_nan=True)
 
 
+def test_a_model_that_changes_its_launches_is_refused_before_any_launch(na):
+    """cfg1's model (cut-off power law -> inverse Compton on the CMB, three parameters) at eight of
+    its data energies, the Python model run at every half-step (use_graph=False): from its fifth
+    evaluation on the model adds a second inverse-Compton component -- an emission the recorded
+    plan does not hold.  The request is refused on the host, before anything is launched for it;
+    a fresh sampler in the same process then runs as if nothing had happened."""
+    from naima_amd import _lib
+    from naima_amd.datatable import make_data
+    from naima_amd.sampler import EnsembleSampler
+    u = na.u
+    model, p0, raw, _, prior = _problem(na, "cfg1", {})
+    rows = np.arange(1, 25, 3)
+    data = make_data({k: v[rows] if isinstance(v, np.ndarray) else v for k, v in raw.items()})
+    assert len(data) == 8 and p0.size == 3
+    evaluations = []
+
+    def changing(pars, data):
+        evaluations.append(1)
+        flux = model(pars, data)
+        if len(evaluations) >= 5:
+            ECPL = na.ExponentialCutoffPowerLaw(pars[0] / u.eV, 10.0 * u.TeV, pars[1], 10 ** pars[2] * u.TeV)
+            flux = flux + na.InverseCompton(ECPL, seed_photon_fields=["FIR"]).flux(data, distance=1.0 * u.kpc)
+        return flux
+
+    nw, nd = 16, p0.size
+    kw = dict(seed=17, naima_style=True, store_blobs=False)
+    pos = p0 * (1 + 0.003 * np.random.default_rng(6).standard_normal((nw, nd)))
+    bad = EnsembleSampler(nw, nd, na.lnprob, args=[data, changing, prior], device=True, use_graph=False, **kw)
+    with pytest.raises(_lib.NaimaHipError, match="launch sequence changed"):
+        bad.run_mcmc(pos, 5)
+    assert len(evaluations) >= 5
+    h = EnsembleSampler(nw, nd, na.lnprob, args=[data, model, prior], **kw)
+    d = EnsembleSampler(nw, nd, na.lnprob, args=[data, model, prior], device=True, use_graph=False, **kw)
+    sh, sd = h.run_mcmc(pos, 5), d.run_mcmc(pos, 5)
+    assert d._dev is not None and d.device and d._dev.fused
+    assert_allclose(sd.coords, sh.coords, rtol=1e-8)
+    assert_allclose(sd.log_prob, sh.log_prob, rtol=1e-6)
+    assert_allclose(d.get_chain(), h.get_chain(), rtol=1e-8)
+    assert_allclose(d.get_log_prob(), h.get_log_prob(), rtol=1e-6)
+    assert_allclose(d.acceptance_fraction, h.acceptance_fraction)
+
+
 @pytest.mark.parametrize("name,nw,mkw", [("cfg3", 512, {}), ("cfg5", 256, {}), ("cfg1", 32, {}),
                                          ("cfg5", 256, {"useLUT": False}), ("cfg2", 256, {}),
                                          ("cfg3", 256, {}), ("cfg3", 48, {}), ("cfg3", 1280, {}),
@@ -720,7 +762,7 @@ def test_resident_loop_equals_per_launch_loop(na, monkeypatch, name, nw, mkw):
             st = d.run_mcmc(pos, 4)
             st = d.run_mcmc(st, 96)
             st2 = d.run_mcmc(st, 7, store=False)  # (no history: blobs go to the current array)
-        assert d._dev.mega and d._dev._plan["hs"] is not None
+        assert d._dev.mega and d._dev._plan.hs is not None
         assert (d._dev.resident_launches > 0) == (mode == "1"), getattr(d._dev, "resident_reason", "")
         if mode == "1" and (name == "cfg1" or "nEpd" in mkw):
             # (a table-only model whose items' rows fit a lane's registers: workgroups of 512
@@ -742,7 +784,7 @@ def test_resident_loop_equals_per_launch_loop(na, monkeypatch, name, nw, mkw):
         if mode == "1" and name in ("cfg3", "cfg1"):
             # (the resident loop walks its own copies of the inverse-Compton tables, columns sorted
             # by their first non-zero row, rows below a tile's first one skipped: same spectra)
-            assert d._dev._plan["hs"].get("sorted"), "sorted tables not installed"
+            assert d._dev._plan.hs.sorted, "sorted tables not installed"
         runs[mode] = (d.get_chain(), d.get_log_prob(), d.get_blobs(), d.acceptance_fraction,
                       np.array(st2.coords), np.array(st2.log_prob),
                       [np.array(b) for b in (st2.blobs or [])])
@@ -919,7 +961,7 @@ def test_table_only_model_with_more_walkers_than_compute_units(na):
     sh, sd = h.run_mcmc(pos, 3), d.run_mcmc(pos, 3)
     sh, sd = h.run_mcmc(sh, 37), d.run_mcmc(sd, 37)
     dev = d._dev
-    assert dev.mega and dev._plan["hs"] is not None and dev._plan["hs"]["threads"] == 256
+    assert dev.mega and dev._plan.hs is not None and dev._plan.hs.threads == 256
     assert_allclose(d.get_chain(), h.get_chain(), rtol=1e-8)
     assert_allclose(d.get_log_prob(), h.get_log_prob(), rtol=1e-6)
     assert_allclose(d.acceptance_fraction, h.acceptance_fraction)
@@ -1241,10 +1283,10 @@ def test_sorted_table_trailers_are_checked_at_the_abi(na):
     st = d.run_mcmc(pos, 8)
     st = d.run_mcmc(st, 8)
     dev = d._dev
-    hs = dev._plan["hs"]
-    assert dev.resident_launches > 0 and hs.get("sorted")
+    hs = dev._plan.hs
+    assert dev.resident_launches > 0 and hs.sorted
     ctx = dev.ctx
-    (Kt, dKt, nG, nK, lx, nonneg), good = hs["tabs"][0], hs["sorted"][0][0]
+    (Kt, dKt, nG, nK, lx, nonneg), good = hs.tabs[0], hs.sorted[0][0]
     host = good.get()
     trail = host[2 * nG * nK:].view(np.int32).copy()
     for what, (idx, val) in {"permutation": (8 + 3, nK), "first row": (0, nG + 1)}.items():
@@ -1254,7 +1296,7 @@ def test_sorted_table_trailers_are_checked_at_the_abi(na):
         bad[2 * nG * nK:] = bad_t.view(np.float64)
         buf = ctx.array(bad)
         ptrs = (C.c_void_p * 4)(buf.ptr, None, None, None)
-        rc = _lib._lib.nh_half_step_run_tables(ctx.h, hs["plan"], dev._run, ptrs, 4)
+        rc = _lib._lib.nh_half_step_run_tables(ctx.h, hs.handle, dev._run, ptrs, 4)
         assert rc != 0 and what in _lib._lib.nh_last_error().decode(), what
     ref = EnsembleSampler(32, nd, na.lnprob, args=[data, model, prior], seed=5, naima_style=True,
                           store_blobs=True, device=True)
