@@ -844,6 +844,46 @@ typedef struct { const double* src; double* dst; long long width; } nh_thin_seg;
 int nh_hist_thin(nh_ctx* ctx, const nh_thin_seg* segs /*host*/, int nsegs /* <= 8 */,
                  long long first, long long stride, long long nrows, long long dst_row0);
 
+/* ---- posterior panels and a corner plot: column reductions over a chain ----------------------
+ * What np.histogram, np.histogram2d and scipy.stats.gaussian_kde compute on the host for naima's
+ * posterior panels (plot_chain, plot_distribution) and for a corner figure.  x is a row-major DEVICE matrix
+ * [M][ld] with ncol <= ld columns in use (get_chain(flat=True), stored scalar blobs).  Stream-
+ * ordered on the context's stream, no host synchronisation, library scratch, 64-bit row indices.
+ * Deterministic: integer atomics only; every floating-point sum has an order fixed by the shapes.
+ * Every entry point: NH_EINVAL for M == 0, ncol < 1, ncol > ld or a null argument.
+ * nh_column_moments: counts (DEVICE int64 [2][ncol]) = the number of finite values, of NaNs;
+ *   stats (DEVICE [4][ncol]) = min, max, mean and unbiased variance (ddof = 1) of the finite
+ *   values, two passes (the mean, then sum (x - mean)^2).  Non-finite values are counted and
+ *   otherwise left out.  A column whose finite values are all equal has that value as its mean
+ *   and variance exactly 0; without a finite value min, max and mean are NaN, with fewer than two
+ *   the variance is.
+ * nh_hist_columns: edges is a DEVICE [ncol][nb+1] of increasing edges per column, evenly spaced
+ *   to within rounding (np.linspace); pairs a HOST [npairs][2] of column pairs (i, j), NULL when
+ *   npairs == 0.  h1 (DEVICE int64 [ncol][nb]) = the counts of every column, h2 (DEVICE int64
+ *   [npairs][nb][nb], NULL when npairs == 0) = h2[p][a][b] with a the bin of column i.  A value v
+ *   is in bin k iff edges[k] <= v < edges[k+1]; v == edges[nb] counts in bin nb-1; values outside
+ *   [edges[0], edges[nb]], NaN and +-inf are dropped, a pair entry if either coordinate is (the
+ *   rule of np.histogram(range=) and of np.histogram2d(bins=[e_i, e_j])).  The bin is estimated
+ *   arithmetically and corrected against the edges.
+ *   NH_EINVAL also: ncol > NH_HIST_MAX_COLS, nb < 1, nb > NH_HIST_MAX_BINS_1D, nb >
+ *   NH_HIST_MAX_BINS_2D with pairs, npairs outside [0, NH_HIST_MAX_PAIRS], a pair index outside
+ *   [0, ncol).
+ * nh_kde_columns: out[c][g] = 1/(n_c h_c sqrt(2 pi)) sum_m exp(-((p[c][g] - x[m][c])/h_c)^2 / 2)
+ *   over the n_c finite values of column c; points p and out are DEVICE [ncol][G], bw = h a
+ *   DEVICE [ncol] of positive bandwidths (scipy.stats.gaussian_kde in one dimension with
+ *   h = factor * std).  NH_EINVAL also: G < 1, ncol > 65535. */
+#define NH_HIST_MAX_COLS 32
+#define NH_HIST_MAX_PAIRS 496
+#define NH_HIST_MAX_BINS_1D 4096
+#define NH_HIST_MAX_BINS_2D 100
+int nh_column_moments(nh_ctx* ctx, const double* x, long long M, int ncol, long long ld,
+                      long long* counts, double* stats);
+int nh_hist_columns(nh_ctx* ctx, const double* x, long long M, int ncol, long long ld,
+                    const double* edges, int nb, const int* pairs /*host*/, int npairs,
+                    long long* h1, long long* h2);
+int nh_kde_columns(nh_ctx* ctx, const double* x, long long M, int ncol, long long ld,
+                   const double* points, int G, const double* bw, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,8 @@ if os.environ.get("NAIMA_AMD_LIB"):  # (experiments: a variant of the library bu
 
 NH_PD_NPAR = 8
 NH_EBL_ONE, NH_EBL_HIGH, NH_EBL_OUTSIDE = 1, 2, 4  # nh_ebl_table's per-energy codes
+# nh_hist_columns' caps (include/naima_hip.h)
+NH_HIST_MAX_COLS, NH_HIST_MAX_PAIRS, NH_HIST_MAX_BINS_1D, NH_HIST_MAX_BINS_2D = 32, 496, 4096, 100
 NH_K_NAMES = ("particle_weights", "integrate_tables", "synchrotron", "tables", "lnprob",
               "ic_seed_walkers", "glue", "integrate_rows", "half_step")
 PD_KIND = {"PowerLaw": 0, "ExponentialCutoffPowerLaw": 1, "BrokenPowerLaw": 2,
@@ -160,6 +162,9 @@ _SIGS = {
     "nh_hist_thin": [_dp, _dp, _i, _ll, _ll, _ll, _ll],
     "nh_ebl_table": [_dp, _dp, _i, _dp, _i, _dp, _dp, _i, _d, _dp, _dp],
     "nh_ebl_apply": [_dp, _dp, _i, _i, _dp, _i, _dp, _dp, _i, _dp, _i, _i, _dp, _i],
+    "nh_column_moments": [_dp, _dp, _ll, _i, _ll, _dp, _dp],
+    "nh_hist_columns": [_dp, _dp, _ll, _i, _ll, _dp, _i, C.POINTER(_i), _i, _dp, _dp],
+    "nh_kde_columns": [_dp, _dp, _ll, _i, _ll, _dp, _i, _dp, _dp],
 }
 EXPORTS = tuple(_SIGS) + ("nh_last_error", "nh_version", "nh_ssc_table_bytes")
 

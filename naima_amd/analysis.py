@@ -265,7 +265,8 @@ def save_diagnostic_plots(outname, sampler, modelidxs=None, pdf=False, sed=True,
                           last_step=False, dpi=100):
     """Diagnostic figures of a run (analysis.py:29-162 of the reference): the chain and posterior
     of every parameter (``<outname>_chain_<label>.png``, log prefixes stripped), the corner plot
-    when the corner package is installed (``<outname>_corner.png``) and every model blob
+    (``<outname>_corner.png``; the built-in figure when the corner package is not installed) and
+    every model blob
     (``<outname>_model<i>.png``: a spectrum with 100 sample models, the ML model, data and
     residuals; a scalar as its distribution).  ``pdf=True``: all of them as the pages of
     ``<outname>_plots.pdf`` instead.  Collective on a sampler that spans several ranks."""

@@ -1,0 +1,408 @@
+// nh_posterior.hip -- column reductions over a chain in HBM for the posterior figures: what
+// np.histogram, np.histogram2d and scipy.stats.gaussian_kde compute on the host for naima's
+// plot_chain / plot_distribution panels and for a corner plot, without bringing the samples back.
+// Every entry point reads a row-major device matrix x[M][ld] with ncol <= ld columns in use (the
+// layout of get_chain(flat=True) and of stored scalar blobs).
+//
+//   nh_column_moments  per column: the counts of finite values and of NaNs, min, max, mean and the
+//                      unbiased variance of the finite values.  Two passes (the mean, then the sum
+//                      of (x - mean)^2); workgroups take (column tile, row chunk), a lane per
+//                      column, and reduce their row lanes through an LDS tree; the per-chunk
+//                      partials are summed by one thread per column in chunk order.
+//   nh_hist_columns    1-D counts of every column and 2-D counts of a list of column pairs on
+//                      per-column edges.  A thread reads a row, bins every column once (an
+//                      arithmetic estimate corrected against the edges, as NumPy does), keeps the
+//                      indices in LDS and feeds the 1-D and every pair histogram from them:
+//                      32-bit counts in LDS (integer LDS atomics), merged into the 64-bit global
+//                      bins with agent-scope integer atomics.  Histograms that do not fit one
+//                      workgroup's LDS together are spread over several launches (groups of
+//                      columns and pairs); counts are integers, so the grouping cannot show.
+//   nh_kde_columns     the Gaussian kernel density of every column at G points.  A workgroup takes
+//                      (point tile, row chunk, column), stages the chunk's values in LDS (a
+//                      broadcast read per row) and writes one partial per point; a second launch
+//                      sums the partials in chunk order and normalises.
+//
+// No floating-point atomics: every floating-point sum has an order fixed by the shapes alone, so
+// repeated calls give bit-identical results.  Row indices are 64-bit.  Every launch is on the
+// context's stream; nothing synchronises with the host.
+#include "nh_common.h"
+
+#include <algorithm>
+
+namespace {
+
+constexpr int PO_THREADS = 256;
+constexpr int PO_TARGET_WG = 2048;     // workgroups a launch aims for (a few per CU)
+constexpr int PO_MIN_ROWS = 1024;      // rows a chunk holds at least
+constexpr int PO_CTR_BUDGET = 11264;   // 32-bit LDS counters per histogram workgroup (44 KiB)
+constexpr int PO_KDE_STAGE = 1024;     // values of a column per LDS stage of the KDE kernel
+constexpr unsigned short PO_DROPPED = 0xffffu;
+
+inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
+
+__device__ __forceinline__ bool po_finite(double v) { return fabs(v) < INFINITY; }  // (NaN: false)
+
+// the row chunks of a launch with `ntile` workgroups per chunk: rows per chunk (a multiple of
+// `mult`) and their number, a function of the shapes only
+inline void po_chunks(long long M, long long ntile, long long mult, long long* rows, long long* nch) {
+  long long want = std::max<long long>(1, PO_TARGET_WG / std::max<long long>(1, ntile));
+  long long n = std::min(want, cdiv(M, PO_MIN_ROWS));
+  *rows = cdiv(cdiv(M, n), mult) * mult;
+  *nch = cdiv(M, *rows);
+}
+
+// ---------------------------------------------------------------- moments
+// threads are [R = 256/cw row lanes][cw columns]; v[tid] += v[tid + s*cw] down the row lanes
+template <typename T, typename F>
+__device__ __forceinline__ void po_tree(T* v, int tid, int ty, int cw, F op) {
+  for (int s = (PO_THREADS / cw) >> 1; s > 0; s >>= 1) {
+    __syncthreads();
+    if (ty < s) v[tid] = op(v[tid], v[tid + s * cw]);
+  }
+  __syncthreads();
+}
+
+// per (row chunk k, column c): pd[(k*3 + 0|1|2)*ncol + c] = sum, min, max of the finite values,
+// pc[(k*2 + 0|1)*ncol + c] = the number of finite values, of NaNs
+__global__ __launch_bounds__(PO_THREADS) void k_po_sum(const double* __restrict__ x, long long M,
+                                                       int ncol, long long ld, int cw,
+                                                       long long rows, double* __restrict__ pd,
+                                                       long long* __restrict__ pc) {
+  __shared__ double rs[PO_THREADS], rlo[PO_THREADS], rhi[PO_THREADS];
+  __shared__ long long rn[PO_THREADS], rnan[PO_THREADS];
+  int tid = threadIdx.x, tx = tid % cw, ty = tid / cw, R = PO_THREADS / cw;
+  int c = blockIdx.x * cw + tx;
+  long long k = blockIdx.y;
+  long long t0 = k * rows, t1 = min(M, t0 + rows);
+  double s = 0.0, lo = INFINITY, hi = -INFINITY;
+  long long n = 0, nn = 0;
+  if (c < ncol) {
+    for (long long t = t0 + ty; t < t1; t += R) {
+      double v = x[t * ld + c];
+      if (po_finite(v)) {
+        s += v;
+        lo = fmin(lo, v);
+        hi = fmax(hi, v);
+        ++n;
+      } else if (v != v) {
+        ++nn;
+      }
+    }
+  }
+  rs[tid] = s; rlo[tid] = lo; rhi[tid] = hi; rn[tid] = n; rnan[tid] = nn;
+  po_tree(rs, tid, ty, cw, [](double a, double b) { return a + b; });
+  po_tree(rlo, tid, ty, cw, [](double a, double b) { return fmin(a, b); });
+  po_tree(rhi, tid, ty, cw, [](double a, double b) { return fmax(a, b); });
+  po_tree(rn, tid, ty, cw, [](long long a, long long b) { return a + b; });
+  po_tree(rnan, tid, ty, cw, [](long long a, long long b) { return a + b; });
+  if (ty == 0 && c < ncol) {
+    pd[(k * 3 + 0) * ncol + c] = rs[tid];
+    pd[(k * 3 + 1) * ncol + c] = rlo[tid];
+    pd[(k * 3 + 2) * ncol + c] = rhi[tid];
+    pc[(k * 2 + 0) * ncol + c] = rn[tid];
+    pc[(k * 2 + 1) * ncol + c] = rnan[tid];
+  }
+}
+
+// counts[0|1][c] = n, NaNs; stats[0|1|2][c] = min, max, mean (NaN without a finite value; the
+// value itself for a column whose finite values are all equal)
+__global__ void k_po_mean(const double* __restrict__ pd, const long long* __restrict__ pc,
+                          long long nch, int ncol, long long* __restrict__ counts,
+                          double* __restrict__ stats) {
+  int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ncol) return;
+  double s = 0.0, lo = INFINITY, hi = -INFINITY;
+  long long n = 0, nn = 0;
+  for (long long k = 0; k < nch; ++k) {
+    s += pd[(k * 3 + 0) * ncol + c];
+    lo = fmin(lo, pd[(k * 3 + 1) * ncol + c]);
+    hi = fmax(hi, pd[(k * 3 + 2) * ncol + c]);
+    n += pc[(k * 2 + 0) * ncol + c];
+    nn += pc[(k * 2 + 1) * ncol + c];
+  }
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  counts[c] = n;
+  counts[ncol + c] = nn;
+  stats[c] = n ? lo : nan;
+  stats[ncol + c] = n ? hi : nan;
+  stats[2 * ncol + c] = n ? (lo == hi ? lo : s / (double)n) : nan;
+}
+
+// pq[k*ncol + c] = the chunk's sum of (x - mean)^2 over the finite values
+__global__ __launch_bounds__(PO_THREADS) void k_po_sq(const double* __restrict__ x, long long M,
+                                                      int ncol, long long ld, int cw,
+                                                      long long rows,
+                                                      const double* __restrict__ stats,
+                                                      double* __restrict__ pq) {
+  __shared__ double rq[PO_THREADS];
+  int tid = threadIdx.x, tx = tid % cw, ty = tid / cw, R = PO_THREADS / cw;
+  int c = blockIdx.x * cw + tx;
+  long long k = blockIdx.y;
+  long long t0 = k * rows, t1 = min(M, t0 + rows);
+  double q = 0.0;
+  if (c < ncol) {
+    const double mean = stats[2 * ncol + c];
+    for (long long t = t0 + ty; t < t1; t += R) {
+      double v = x[t * ld + c];
+      if (po_finite(v)) {
+        double d = v - mean;
+        q = fma(d, d, q);
+      }
+    }
+  }
+  rq[tid] = q;
+  po_tree(rq, tid, ty, cw, [](double a, double b) { return a + b; });
+  if (ty == 0 && c < ncol) pq[k * ncol + c] = rq[tid];
+}
+
+// stats[3][c] = sum / (n - 1): exactly 0 for equal values, NaN for fewer than two
+__global__ void k_po_var(const double* __restrict__ pq, long long nch, int ncol,
+                         const long long* __restrict__ counts, double* __restrict__ stats) {
+  int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ncol) return;
+  double q = 0.0;
+  for (long long k = 0; k < nch; ++k) q += pq[k * ncol + c];
+  long long n = counts[c];
+  double var = __longlong_as_double(0x7ff8000000000000ll);
+  if (n > 1) var = stats[c] == stats[ncol + c] ? 0.0 : q / (double)(n - 1);
+  stats[3 * ncol + c] = var;
+}
+
+// ---------------------------------------------------------------- histograms
+struct po_pairs { unsigned char i[NH_HIST_MAX_PAIRS], j[NH_HIST_MAX_PAIRS]; };
+
+// the bin of v on the edges e[0..nb]: k with e[k] <= v < e[k+1], the last bin closed on the right;
+// PO_DROPPED outside [e[0], e[nb]] and for NaN and +-inf
+__device__ __forceinline__ unsigned short po_bin(double v, const double* __restrict__ e, int nb) {
+  const double lo = e[0], hi = e[nb];
+  if (!po_finite(v) || !(v >= lo && v <= hi)) return PO_DROPPED;
+  int k = (int)((v - lo) / (hi - lo) * (double)nb);
+  k = min(max(k, 0), nb - 1);
+  while (k > 0 && v < e[k]) --k;
+  while (k < nb - 1 && v >= e[k + 1]) ++k;
+  return (unsigned short)k;
+}
+
+// the 1-D histograms of columns [c0, c1) and the 2-D ones of pairs [p0, p1) over the rows of
+// this workgroup.  LDS: [(c1-c0)*nb | (p1-p0)*nb*nb] 32-bit counters, then the bin of every
+// column of the thread's row, idx[c][thread] (thread-private: no barrier in the row loop)
+__global__ __launch_bounds__(PO_THREADS) void k_po_hist(const double* __restrict__ x, long long M,
+                                                        int ncol, long long ld,
+                                                        const double* __restrict__ edges, int nb,
+                                                        long long rpb, int c0, int c1, int p0,
+                                                        int p1, po_pairs pr,
+                                                        unsigned long long* __restrict__ h1,
+                                                        unsigned long long* __restrict__ h2) {
+  extern __shared__ unsigned po_lds[];
+  const int n1 = (c1 - c0) * nb, n2 = (p1 - p0) * nb * nb;
+  unsigned* ctr2 = po_lds + n1;
+  unsigned short* idx = (unsigned short*)(po_lds + n1 + n2);
+  int tid = threadIdx.x;
+  for (int i = tid; i < n1 + n2; i += PO_THREADS) po_lds[i] = 0u;
+  __syncthreads();
+  long long row0 = (long long)blockIdx.x * rpb, row1 = min(M, row0 + rpb);
+  for (long long row = row0 + tid; row < row1; row += PO_THREADS) {
+    const double* xr = x + row * ld;
+    for (int c = 0; c < ncol; ++c)
+      idx[c * PO_THREADS + tid] = po_bin(xr[c], edges + (long long)c * (nb + 1), nb);
+    for (int c = c0; c < c1; ++c) {
+      unsigned k = idx[c * PO_THREADS + tid];
+      if (k != PO_DROPPED)
+        __hip_atomic_fetch_add(po_lds + (c - c0) * nb + k, 1u, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    for (int p = p0; p < p1; ++p) {
+      unsigned a = idx[pr.i[p] * PO_THREADS + tid], b = idx[pr.j[p] * PO_THREADS + tid];
+      if (a != PO_DROPPED && b != PO_DROPPED)
+        __hip_atomic_fetch_add(ctr2 + ((p - p0) * nb + a) * nb + b, 1u, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < n1; i += PO_THREADS) {
+    unsigned v = po_lds[i];
+    if (v) __hip_atomic_fetch_add(h1 + (long long)c0 * nb + i, (unsigned long long)v,
+                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  for (int i = tid; i < n2; i += PO_THREADS) {
+    unsigned v = ctr2[i];
+    if (v) __hip_atomic_fetch_add(h2 + (long long)p0 * nb * nb + i, (unsigned long long)v,
+                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// ---------------------------------------------------------------- KDE
+// threads are [RS = 256/gp row lanes][gp points]; part[(c*nch + k)*G + g] = the sum over the
+// finite values of chunk k of exp(-((p[c][g] - x)/h_c)^2 / 2), pn[c*nch + k] their number
+__global__ __launch_bounds__(PO_THREADS) void k_po_kde(const double* __restrict__ x, long long M,
+                                                       long long ld,
+                                                       const double* __restrict__ pts, int G,
+                                                       const double* __restrict__ bw, int gp,
+                                                       long long rows, long long nch,
+                                                       double* __restrict__ part,
+                                                       long long* __restrict__ pn) {
+  __shared__ double xs[PO_KDE_STAGE];
+  __shared__ double red[PO_THREADS];
+  __shared__ unsigned nfin;
+  int tid = threadIdx.x, tg = tid % gp, rl = tid / gp, RS = PO_THREADS / gp;
+  int g = blockIdx.x * gp + tg;
+  long long k = blockIdx.y;
+  int c = blockIdx.z;
+  const double inv = 1.0 / bw[c];
+  const double p = g < G ? pts[(long long)c * G + g] : 0.0;
+  long long t0 = k * rows, t1 = min(M, t0 + rows);
+  if (tid == 0) nfin = 0u;
+  __syncthreads();
+  double acc = 0.0;
+  unsigned nf = 0u;
+  for (long long tb = t0; tb < t1; tb += PO_KDE_STAGE) {
+    int len = (int)min((long long)PO_KDE_STAGE, t1 - tb);
+    __syncthreads();  // (the stage before has been read)
+    for (int i = tid; i < len; i += PO_THREADS) {
+      double v = x[(tb + i) * ld + c];
+      bool f = po_finite(v);
+      xs[i] = f ? v : INFINITY;  // (p - inf)^2 = inf: the term is exp(-inf) = 0
+      nf += f;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int i = rl; i < len; i += RS) {
+      double u = (p - xs[i]) * inv;
+      acc += exp(-0.5 * u * u);
+    }
+  }
+  red[tid] = acc;
+  if (nf) __hip_atomic_fetch_add(&nfin, nf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  for (int s = RS >> 1; s > 0; s >>= 1) {
+    __syncthreads();
+    if (rl < s) red[tid] += red[tid + s * gp];
+  }
+  __syncthreads();
+  if (rl == 0 && g < G) part[((long long)c * nch + k) * G + g] = red[tid];
+  if (tid == 0 && blockIdx.x == 0) pn[(long long)c * nch + k] = (long long)nfin;
+}
+
+// out[c][g] = sum_k part / (n_c h_c sqrt(2 pi)), the chunks in order
+__global__ void k_po_kde_reduce(const double* __restrict__ part, const long long* __restrict__ pn,
+                                long long nch, int G, const double* __restrict__ bw,
+                                double* __restrict__ out) {
+  int g = blockIdx.x * blockDim.x + threadIdx.x;
+  int c = blockIdx.y;
+  if (g >= G) return;
+  double s = 0.0;
+  long long n = 0;
+  for (long long k = 0; k < nch; ++k) {
+    s += part[((long long)c * nch + k) * G + g];
+    n += pn[(long long)c * nch + k];
+  }
+  out[(long long)c * G + g] = s / ((double)n * bw[c] * 2.5066282746310002);
+}
+
+inline int po_pow2_at_least(int n, int cap) {
+  int p = 1;
+  while (p < n && p < cap) p <<= 1;
+  return p;
+}
+
+}  // namespace
+
+#define PO_REQUIRE_MATRIX()                                        \
+  NH_REQUIRE(M > 0, "M == 0: no samples");                         \
+  NH_REQUIRE(ncol > 0, "ncol must be positive");                   \
+  NH_REQUIRE(ld >= ncol, "ncol > ld")
+
+extern "C" int nh_column_moments(nh_ctx* ctx, const double* x, long long M, int ncol, long long ld,
+                                 long long* counts, double* stats) {
+  NH_REQUIRE(ctx && x && counts && stats, "null argument");
+  PO_REQUIRE_MATRIX();
+  int cw = po_pow2_at_least(ncol, 64);
+  long long ntile = cdiv(ncol, cw), rows, nch;
+  po_chunks(M, ntile, PO_THREADS / cw, &rows, &nch);
+  NH_REQUIRE(nch <= 65535 && ntile < (1ll << 31), "too many columns");
+  // scratch: pd [nch][3][ncol] | pq [nch][ncol] | pc [nch][2][ncol]
+  void* base = nullptr;
+  int rc = nh_scratch(ctx, (size_t)nch * ncol * 6 * 8, &base);
+  if (rc) return rc;
+  double* pd = (double*)base;
+  double* pq = pd + (size_t)nch * 3 * ncol;
+  long long* pc = (long long*)(pq + (size_t)nch * ncol);
+  hipStream_t s = ctx->stream;
+  dim3 grid((unsigned)ntile, (unsigned)nch);
+  unsigned cb = (unsigned)cdiv(ncol, PO_THREADS);
+  hipLaunchKernelGGL(k_po_sum, grid, dim3(PO_THREADS), 0, s, x, M, ncol, ld, cw, rows, pd, pc);
+  NH_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_po_mean, dim3(cb), dim3(PO_THREADS), 0, s, pd, pc, nch, ncol, counts, stats);
+  NH_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_po_sq, grid, dim3(PO_THREADS), 0, s, x, M, ncol, ld, cw, rows, stats, pq);
+  NH_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_po_var, dim3(cb), dim3(PO_THREADS), 0, s, pq, nch, ncol, counts, stats);
+  NH_CHECK_HIP(hipGetLastError());
+  return NH_OK;
+}
+
+extern "C" int nh_hist_columns(nh_ctx* ctx, const double* x, long long M, int ncol, long long ld,
+                               const double* edges, int nb, const int* pairs, int npairs,
+                               long long* h1, long long* h2) {
+  NH_REQUIRE(ctx && x && edges && h1, "null argument");
+  PO_REQUIRE_MATRIX();
+  NH_REQUIRE(ncol <= NH_HIST_MAX_COLS, "ncol > NH_HIST_MAX_COLS");
+  NH_REQUIRE(nb >= 1, "nb must be positive");
+  NH_REQUIRE(nb <= NH_HIST_MAX_BINS_1D, "nb > NH_HIST_MAX_BINS_1D");
+  NH_REQUIRE(npairs >= 0 && npairs <= NH_HIST_MAX_PAIRS, "npairs outside [0, NH_HIST_MAX_PAIRS]");
+  NH_REQUIRE(npairs == 0 || (pairs && h2), "null argument");
+  NH_REQUIRE(npairs == 0 || nb <= NH_HIST_MAX_BINS_2D, "nb > NH_HIST_MAX_BINS_2D with pairs");
+  po_pairs pr = {};
+  for (int p = 0; p < npairs; ++p) {
+    int i = pairs[2 * p], j = pairs[2 * p + 1];
+    if (i < 0 || i >= ncol || j < 0 || j >= ncol)
+      return nh_set_error(NH_EINVAL, "nh_hist_columns: pair %d is (%d, %d), outside [0, %d)", p, i,
+                          j, ncol);
+    pr.i[p] = (unsigned char)i;
+    pr.j[p] = (unsigned char)j;
+  }
+  hipStream_t s = ctx->stream;
+  NH_CHECK_HIP(hipMemsetAsync(h1, 0, (size_t)ncol * nb * 8, s));
+  if (npairs) NH_CHECK_HIP(hipMemsetAsync(h2, 0, (size_t)npairs * nb * nb * 8, s));
+  long long rpb = std::max<long long>(4 * PO_MIN_ROWS, cdiv(M, PO_TARGET_WG / 2));
+  rpb = cdiv(rpb, PO_THREADS) * PO_THREADS;
+  unsigned nrb = (unsigned)cdiv(M, rpb);
+  // groups: the columns in order, then the pairs in order, as many as fit the counter budget
+  const int per_c = nb, per_p = nb * nb;
+  int c = 0, p = 0;
+  while (c < ncol || p < npairs) {
+    int used = 0, c0 = c, p0 = p;
+    while (c < ncol && used + per_c <= PO_CTR_BUDGET) { used += per_c; ++c; }
+    if (c == ncol)
+      while (p < npairs && used + per_p <= PO_CTR_BUDGET) { used += per_p; ++p; }
+    size_t lds = (size_t)used * 4 + (size_t)ncol * PO_THREADS * 2;
+    hipLaunchKernelGGL(k_po_hist, dim3(nrb), dim3(PO_THREADS), lds, s, x, M, ncol, ld, edges, nb,
+                       rpb, c0, c, p0, p, pr, (unsigned long long*)h1, (unsigned long long*)h2);
+    NH_CHECK_HIP(hipGetLastError());
+  }
+  return NH_OK;
+}
+
+extern "C" int nh_kde_columns(nh_ctx* ctx, const double* x, long long M, int ncol, long long ld,
+                              const double* points, int G, const double* bw, double* out) {
+  NH_REQUIRE(ctx && x && points && bw && out, "null argument");
+  PO_REQUIRE_MATRIX();
+  NH_REQUIRE(ncol <= 65535, "ncol > 65535");
+  NH_REQUIRE(G > 0, "G must be positive");
+  int gp = po_pow2_at_least(G, PO_THREADS);
+  long long npt = cdiv(G, gp), rows, nch;
+  po_chunks(M, npt * ncol, 1, &rows, &nch);
+  // scratch: part [ncol][nch][G] | pn [ncol][nch]
+  void* base = nullptr;
+  int rc = nh_scratch(ctx, ((size_t)ncol * nch * G + (size_t)ncol * nch) * 8, &base);
+  if (rc) return rc;
+  double* part = (double*)base;
+  long long* pn = (long long*)(part + (size_t)ncol * nch * G);
+  hipStream_t s = ctx->stream;
+  hipLaunchKernelGGL(k_po_kde, dim3((unsigned)npt, (unsigned)nch, (unsigned)ncol),
+                     dim3(PO_THREADS), 0, s, x, M, ld, points, G, bw, gp, rows, nch, part, pn);
+  NH_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_po_kde_reduce, dim3((unsigned)cdiv(G, PO_THREADS), (unsigned)ncol),
+                     dim3(PO_THREADS), 0, s, part, pn, nch, G, bw, out);
+  NH_CHECK_HIP(hipGetLastError());
+  return NH_OK;
+}

@@ -349,13 +349,17 @@ def _value_error(val, elo, ehi):
 
 def _posterior_hist(ax, dist, label, title):
     """density histogram of ``dist`` with its KDE, median and 16-84 % band; returns the three
-    percentiles"""
-    from scipy import stats
+    percentiles.  The bar heights and the KDE curve come from the GPU (posterior.histogram,
+    posterior.gaussian_kde) over one upload of ``dist``."""
+    from . import posterior
     nbins = int(np.clip(np.sqrt(dist.size), 25, 100))
-    heights, edges, _ = ax.hist(dist, bins=nbins, density=True, histtype="stepfilled",
-                                color=color_cycle[0], lw=0)
+    s = posterior._matrix(dist)
+    counts, edges = posterior.histogram(s, bins=nbins)
+    counts, edges = counts[0], edges[0]
+    heights = counts / (counts.sum() * np.diff(edges))  # (np.histogram's density=True)
+    ax.stairs(heights, edges, fill=True, color=color_cycle[0], lw=0)
     if np.ptp(dist) > 0:
-        ax.plot(edges, stats.gaussian_kde(dist)(edges), color="k", label="KDE")
+        ax.plot(edges, posterior.gaussian_kde(s, edges)[0], color="k", label="KDE")
     q = np.percentile(dist, [16, 50, 84])
     ax.axvspan(q[0], q[2], color="0.5", alpha=0.25, lw=0, label="68% CI")
     ax.axvline(q[1], color="k", ls="--", lw=2, alpha=0.5, label="50% quantile")
@@ -688,14 +692,16 @@ def plot_data(input_data, xlabel=None, ylabel=None, sed=True, figure=None, e_uni
 
 
 def plot_corner(sampler, show_ML=True, **kwargs):
-    """Corner plot of the chain through ``corner.corner`` (plot.py:1393-1439); warns and returns
-    None when the corner package is not installed."""
+    """Corner plot of the chain (plot.py:1393-1439): through ``corner.corner`` when the corner
+    package is installed; else, after a warning, the built-in figure ``posterior.corner`` draws
+    from histograms taken on the GPU (of the keywords, those it knows are passed on)."""
     import warnings
     try:
         import corner
     except ImportError:
-        warnings.warn("The corner package is not installed; corner plot not available")
-        return None
+        corner = None
+        warnings.warn("The corner package is not installed; corner plot not available from it: "
+                      "drawing the built-in corner figure (naima_amd.posterior.corner)")
     import matplotlib.pyplot as plt
     oldlw = plt.rcParams["lines.linewidth"]
     plt.rcParams["lines.linewidth"] = 0.7
@@ -706,7 +712,14 @@ def plot_corner(sampler, show_ML=True, **kwargs):
             _, MLp, _, _ = find_ML(sampler, None)
             opts["truths"] = MLp
         opts.update(kwargs)
-        f = corner.corner(np.asarray(sampler.get_chain(flat=True)), **opts)
+        chain = np.asarray(sampler.get_chain(flat=True))
+        if corner is not None:
+            f = corner.corner(chain, **opts)
+        else:
+            from . import posterior
+            known = ("labels", "truths", "quantiles", "bins", "range", "levels", "truth_color",
+                     "fig")
+            f = posterior.corner(chain, **{k: v for k, v in opts.items() if k in known})
     finally:
         plt.rcParams["lines.linewidth"] = oldlw
     return f

@@ -1,0 +1,335 @@
+"""Posterior densities of a chain from GPU reductions, and a corner figure built on them.
+
+The samples are a matrix of M rows and ncol columns in HBM (``get_chain(flat=True)``, the values
+of a scalar blob); per column the device returns the moments (``nh_column_moments``), the 1-D
+histograms and the 2-D histograms of column pairs (``nh_hist_columns``: NumPy's bin rule on
+``np.linspace`` edges, integer counts) and a Gaussian kernel density (``nh_kde_columns``:
+``scipy.stats.gaussian_kde`` in one dimension).  All of them are deterministic.  There is no CPU
+fallback for the reductions; only the edges, the bandwidths and the contour levels of ``nb * nb``
+counts are host arithmetic.
+
+Every function takes a host array ``(M,)`` or ``(M, ncol)``, which is uploaded once per call, or a
+device matrix: a ``plot._Samples``, or ``(DeviceArray, M, ncol, ld)``.
+
+Importing this module creates no GPU context; argument errors come before any device work.
+matplotlib is imported by ``corner`` only.
+"""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import (NH_HIST_MAX_BINS_1D, NH_HIST_MAX_BINS_2D, NH_HIST_MAX_COLS,
+                   NH_HIST_MAX_PAIRS)
+
+__all__ = ["column_stats", "histogram", "histogram_pairs", "gaussian_kde", "contour_thresholds",
+           "corner", "DEFAULT_LEVELS"]
+
+# the mass of a 2-D Gaussian inside 0.5, 1, 1.5 and 2 sigma (corner's default contours)
+DEFAULT_LEVELS = tuple(1.0 - np.exp(-0.5 * np.array([0.5, 1.0, 1.5, 2.0]) ** 2))
+
+
+# ---------------------------------------------------------------------------------------
+# host arithmetic
+# ---------------------------------------------------------------------------------------
+def _check_bins(bins, with_pairs):
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)):
+        raise ValueError("bins must be an integer, the same number for every column")
+    bins = int(bins)
+    if bins < 1:
+        raise ValueError("bins must be at least 1")
+    cap = NH_HIST_MAX_BINS_2D if with_pairs else NH_HIST_MAX_BINS_1D
+    if bins > cap:
+        raise ValueError("bins = %d is more than the %d the %s histograms take"
+                         % (bins, cap, "pair" if with_pairs else "1-D"))
+    return bins
+
+
+def _check_pairs(pairs, ncol):
+    if pairs is None:
+        pairs = [(i, j) for i in range(ncol) for j in range(i + 1, ncol)]
+    out = []
+    for pr in pairs:
+        i, j = (int(v) for v in pr)
+        if not (0 <= i < ncol and 0 <= j < ncol):
+            raise ValueError("pair (%d, %d) is outside the %d columns" % (i, j, ncol))
+        out.append((i, j))
+    if len(out) > NH_HIST_MAX_PAIRS:
+        raise ValueError("%d pairs are more than the %d one call takes"
+                         % (len(out), NH_HIST_MAX_PAIRS))
+    return out
+
+
+def _edges(lo, hi, bins):
+    """np.histogram's edges for ``range=(lo, hi)`` per column: [ncol][bins+1]; lo == hi widens
+    to lo - 0.5, hi + 0.5"""
+    lo, hi = np.array(lo, dtype=float, ndmin=1), np.array(hi, dtype=float, ndmin=1)
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi))):
+        raise ValueError("the range of a column is not finite (a column without finite values?)")
+    if np.any(lo > hi):
+        raise ValueError("max must be larger than min in range")
+    flat = lo == hi
+    lo, hi = np.where(flat, lo - 0.5, lo), np.where(flat, hi + 0.5, hi)
+    return np.stack([np.linspace(a, b, bins + 1) for a, b in zip(lo, hi)])
+
+
+def _range(range, ncol):
+    """(lo, hi) arrays [ncol] of an explicit range: one (lo, hi) for every column, or one each"""
+    r = np.asarray(range, dtype=float)
+    if r.shape == (2,):
+        r = np.tile(r, (ncol, 1))
+    if r.shape != (ncol, 2):
+        raise ValueError("range must be (lo, hi) or one (lo, hi) per column")
+    return r[:, 0], r[:, 1]
+
+
+def _bandwidth_factor(bw_method, n):
+    """scipy.stats.gaussian_kde's factor for n samples in one dimension"""
+    n = np.asarray(n, dtype=float)
+    if bw_method is None or bw_method == "scott":
+        return n ** (-1.0 / 5.0)
+    if bw_method == "silverman":
+        return (n * 3.0 / 4.0) ** (-1.0 / 5.0)
+    if np.isscalar(bw_method) and not isinstance(bw_method, str):
+        return np.full(n.shape, float(bw_method))
+    raise ValueError("bw_method should be 'scott', 'silverman' or a scalar")
+
+
+def _bandwidths(bw_method, n, var):
+    """h [ncol] = factor * sqrt(var); a zero-variance column cannot have a density"""
+    var = np.asarray(var, dtype=float)
+    if np.any(~(var > 0)):
+        raise ValueError("a Gaussian KDE needs a positive variance: column(s) %s have none"
+                         % np.flatnonzero(~(var > 0)).tolist())
+    h = _bandwidth_factor(bw_method, n) * np.sqrt(var)
+    if np.any(~(h > 0) | ~np.isfinite(h)):
+        raise ValueError("the bandwidth must be positive and finite")
+    return h
+
+
+def contour_thresholds(H, levels=None):
+    """The counts at which the contours enclosing the fractions ``levels`` of a 2-D histogram's
+    mass lie, one per level in the levels' order: the counts sorted in descending order, their
+    cumulative fraction taken, the threshold of a level is the smallest count still inside that
+    fraction (the largest count when not even that one is).  ``corner.hist2d``'s rule."""
+    levels = DEFAULT_LEVELS if levels is None else levels
+    h = np.sort(np.asarray(H, dtype=float).ravel())[::-1]
+    if h.size == 0 or not h[0] > 0:
+        raise ValueError("the histogram is empty")
+    sm = np.cumsum(h)
+    sm /= sm[-1]
+    out = np.empty(len(levels))
+    for k, v in enumerate(levels):
+        inside = h[sm <= v]
+        out[k] = inside[-1] if inside.size else h[0]
+    return out
+
+
+# ---------------------------------------------------------------------------------------
+# device
+# ---------------------------------------------------------------------------------------
+def _matrix(x):
+    """x as a plot._Samples (ctx, ptr, M, ncol, ld)"""
+    from . import _lib
+    from .plot import _Samples
+    if isinstance(x, _Samples):
+        return x
+    if isinstance(x, tuple) and len(x) == 4 and isinstance(x[0], _lib.DeviceArray):
+        dev, M, ncol, ld = x[0], int(x[1]), int(x[2]), int(x[3])
+        if M < 1 or ncol < 1 or ld < ncol or M * ld * 8 > dev.nbytes:
+            raise ValueError("a device matrix of %d x %d (ld %d) does not fit its buffer"
+                             % (M, ncol, ld))
+        return _Samples(dev.ctx, dev.ptr, M, ncol, ld, dev)
+    a = np.asarray(x, dtype=np.float64)
+    if a.ndim == 1:
+        a = a[:, np.newaxis]
+    if a.ndim != 2:
+        raise ValueError("samples must be (M,) or (M, ncol)")
+    if a.shape[0] == 0 or a.shape[1] == 0:
+        raise ValueError("no samples")
+    ctx = _lib.get_context()
+    buf = ctx.array(np.ascontiguousarray(a))
+    return _Samples(ctx, buf.ptr, a.shape[0], a.shape[1], a.shape[1], buf)
+
+
+def _shape(x):
+    """(M, ncol) of what _matrix would make of x, without a device"""
+    if hasattr(x, "M") and hasattr(x, "ncol"):
+        return x.M, x.ncol
+    if isinstance(x, tuple) and len(x) == 4 and not np.isscalar(x[0]) and hasattr(x[0], "ptr"):
+        return int(x[1]), int(x[2])
+    s = np.shape(x)
+    return (s[0], 1) if len(s) == 1 else tuple(s)
+
+
+def column_stats(x):
+    """Per column: ``n`` finite values, ``n_nan`` NaNs (int64), and ``min``, ``max``, ``mean``,
+    ``var`` (unbiased, ddof=1) of the finite values, as a dict of arrays [ncol]."""
+    s = _matrix(x)
+    ctx = s.ctx
+    counts, stats = ctx.empty((2, s.ncol), np.int64), ctx.empty((4, s.ncol))
+    ctx.call("nh_column_moments", s.ptr, s.M, s.ncol, s.ld, counts, stats)
+    c, v = counts.get(), stats.get()
+    return dict(n=c[0], n_nan=c[1], min=v[0], max=v[1], mean=v[2], var=v[3])
+
+
+def _histograms(s, bins, range, pairs):
+    """(h1 [ncol][nb], H [npairs][nb][nb], edges [ncol][nb+1]) in one pass over the samples"""
+    if s.ncol > NH_HIST_MAX_COLS:
+        raise ValueError("%d columns are more than the %d one call takes"
+                         % (s.ncol, NH_HIST_MAX_COLS))
+    if range is None:
+        st = column_stats(s)
+        lo, hi = st["min"], st["max"]
+    else:
+        lo, hi = _range(range, s.ncol)
+    edges = _edges(lo, hi, bins)
+    ctx = s.ctx
+    h1 = ctx.empty((s.ncol, bins), np.int64)
+    H = ctx.empty((len(pairs), bins, bins), np.int64) if pairs else None
+    flat = (C.c_int * (2 * len(pairs)))(*[v for pr in pairs for v in pr]) if pairs else None
+    ctx.call("nh_hist_columns", s.ptr, s.M, s.ncol, s.ld, ctx.array(edges), bins, flat, len(pairs),
+             h1, H)
+    return h1.get(), (H.get() if pairs else np.zeros((0, bins, bins), np.int64)), edges
+
+
+def histogram(x, bins=20, range=None):
+    """``np.histogram(col, bins, range)`` of every column: (counts int64 [ncol][bins], edges
+    [ncol][bins+1]).  ``range`` is (lo, hi) for every column or one per column; None takes each
+    column's finite minimum and maximum.  NaN, +-inf and values outside the range are dropped."""
+    bins = _check_bins(bins, False)
+    if range is not None:
+        _range(range, _shape(x)[1])
+    h1, _, edges = _histograms(_matrix(x), bins, range, [])
+    return h1, edges
+
+
+def histogram_pairs(x, bins=20, range=None, pairs=None):
+    """``np.histogram2d(col_i, col_j, bins=[edges_i, edges_j])`` of the column pairs ``pairs``
+    (default: every i < j): (H int64 [npairs][bins][bins], pairs, edges [ncol][bins+1]), with
+    ``H[p][a][b]`` counting the rows in bin a of column i and bin b of column j."""
+    bins = _check_bins(bins, True)
+    ncol = _shape(x)[1]
+    pairs = _check_pairs(pairs, ncol)
+    if range is not None:
+        _range(range, ncol)
+    _, H, edges = _histograms(_matrix(x), bins, range, pairs)
+    return H, pairs, edges
+
+
+def gaussian_kde(x, points, bw_method=None):
+    """``scipy.stats.gaussian_kde(col, bw_method)(points)`` of every column: [ncol][G].
+    ``points`` is (G,) for every column or (ncol, G); ``bw_method`` None / "scott", "silverman"
+    or a scalar factor; the bandwidth is factor * sqrt(var) over the column's finite values."""
+    _bandwidth_factor(bw_method, 2.0)
+    s = _matrix(x)
+    p = np.asarray(points, dtype=np.float64)
+    if p.ndim == 1:
+        p = np.tile(p, (s.ncol, 1))
+    if p.ndim != 2 or p.shape[0] != s.ncol or p.shape[1] == 0:
+        raise ValueError("points must be (G,) or (ncol, G)")
+    st = column_stats(s)
+    h = _bandwidths(bw_method, st["n"], st["var"])
+    ctx = s.ctx
+    out = ctx.empty(p.shape)
+    ctx.call("nh_kde_columns", s.ptr, s.M, s.ncol, s.ld, ctx.array(np.ascontiguousarray(p)),
+             p.shape[1], ctx.array(h), out)
+    return out.get()
+
+
+def _quantiles(s, q):
+    """np.percentile's (linear) quantiles of every column from exact order statistics
+    (nh_column_select): [len(q)][ncol]"""
+    from .plot import column_select
+    pos = np.asarray(q, dtype=float) * (s.M - 1)
+    lo = np.floor(pos).astype(int)
+    hi = np.minimum(lo + 1, s.M - 1)
+    v = column_select(s, list(lo) + list(hi))
+    a, b = v[:len(lo)], v[len(lo):]
+    return a + (b - a) * (pos - lo)[:, np.newaxis]
+
+
+# ---------------------------------------------------------------------------------------
+# the figure
+# ---------------------------------------------------------------------------------------
+def corner(samples, labels=None, truths=None, quantiles=(0.16, 0.5, 0.84), bins=20, range=None,
+           levels=None, truth_color=None, fig=None):
+    """A corner figure of the samples [M][ncol]: the histogram of every column on the diagonal
+    with dashed lines at ``quantiles``, below it the 2-D histogram of every column pair as a
+    density image with contours enclosing the fractions ``levels`` of the samples (default: 0.5,
+    1, 1.5 and 2 sigma of a 2-D Gaussian).  ``truths`` are drawn as lines and a square marker in
+    ``truth_color``.  One pass over the samples on the GPU gives every histogram and one
+    selection the quantiles; no panel downloads samples.  Returns the matplotlib figure."""
+    bins = _check_bins(bins, True)
+    M, n = _shape(samples)
+    pairs = _check_pairs(None, n)
+    quantiles = [float(v) for v in (quantiles if quantiles is not None else ())]
+    if any(not 0.0 <= v <= 1.0 for v in quantiles):
+        raise ValueError("quantiles must be in [0, 1]")
+    if labels is not None and len(labels) != n:
+        raise ValueError("%d labels for %d columns" % (len(labels), n))
+    if truths is not None and len(truths) != n:
+        raise ValueError("%d truths for %d columns" % (len(truths), n))
+    if range is not None:
+        _range(range, n)
+    import matplotlib.pyplot as plt
+    s = _matrix(samples)
+    h1, H, edges = _histograms(s, bins, range, pairs)
+    qv = _quantiles(s, quantiles) if quantiles else np.empty((0, n))
+    truth_color = "#4682b4" if truth_color is None else truth_color
+
+    if fig is None:
+        side = 1.0 + 2.0 * n
+        fig = plt.figure(figsize=(side, side))
+    if len(fig.axes) == n * n:  # (a figure this function made: drawn over, as corner does)
+        axes = np.array(fig.axes).reshape(n, n)
+    else:
+        axes = fig.subplots(n, n, squeeze=False)
+    fig.subplots_adjust(left=0.12, bottom=0.12, right=0.97, top=0.97, wspace=0.05, hspace=0.05)
+    which = {pr: k for k, pr in enumerate(pairs)}
+    for r in np.arange(n):
+        for c in np.arange(n):
+            ax = axes[r, c]
+            if c > r:
+                ax.set_visible(False)
+                ax.set_frame_on(False)
+                continue
+            if r == c:
+                ax.stairs(h1[c], edges[c], color="k")
+                for v in qv[:, c]:
+                    ax.axvline(v, ls="dashed", color="k")
+                if truths is not None and truths[c] is not None:
+                    ax.axvline(truths[c], color=truth_color)
+                ax.set_xlim(edges[c][0], edges[c][-1])
+                ax.set_ylim(0, 1.1 * max(h1[c].max(), 1))
+                ax.set_yticks([])
+            else:
+                # column c along x, column r along y: H[p] is [bin of c][bin of r]
+                Hp = H[which[(c, r)]]
+                ax.pcolormesh(edges[c], edges[r], Hp.T, cmap="Greys", rasterized=True)
+                if Hp.max() > 0:
+                    lv = np.unique(contour_thresholds(Hp, levels))
+                    xc = 0.5 * (edges[c][1:] + edges[c][:-1])
+                    yc = 0.5 * (edges[r][1:] + edges[r][:-1])
+                    if bins > 1:
+                        ax.contour(xc, yc, Hp.T, levels=lv, colors="k")
+                if truths is not None:
+                    if truths[c] is not None:
+                        ax.axvline(truths[c], color=truth_color)
+                    if truths[r] is not None:
+                        ax.axhline(truths[r], color=truth_color)
+                    if truths[c] is not None and truths[r] is not None:
+                        ax.plot(truths[c], truths[r], "s", color=truth_color)
+                ax.set_xlim(edges[c][0], edges[c][-1])
+                ax.set_ylim(edges[r][0], edges[r][-1])
+            # labels and tick labels on the outer axes only
+            if r < n - 1:
+                ax.tick_params(labelbottom=False)
+            else:
+                ax.tick_params(axis="x", labelrotation=45)
+                if labels is not None:
+                    ax.set_xlabel(labels[c])
+            if c > 0 or r == 0:
+                ax.tick_params(labelleft=False)
+            elif labels is not None:
+                ax.set_ylabel(labels[r])
+    return fig
