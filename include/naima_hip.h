@@ -806,6 +806,32 @@ int nh_autocorr_prep(nh_ctx* ctx, const double* x, long long n_t, int n_w, int n
 int nh_autocorr_lags(nh_ctx* ctx, const double* z, const double* s2, long long n_t, int n_w,
                      long long lag0, int nlags, double* f);
 
+/* ---- the same function of a chain that is still growing: running lag sums --------------------
+ * x is a row-major DEVICE block [rows][n_w*n_d] whose rows [row_start, n) hold a chain so far (a
+ * history block of the device loop).  With y = x - pivot (a series' value in row row_start) the
+ * state holds S[col][k] = sum_{t >= row_start + k} y[t] y[t-k] for k < L (DEVICE [n_w*n_d][L]),
+ * stats = {sum of y, min y, max y} (DEVICE [3][n_w*n_d]) and pivot (DEVICE [n_w*n_d]); the caller
+ * owns the three arrays and need not initialise them.  Same conventions as above (no floating-
+ * point atomics, 64-bit indices, the context's stream, no host synchronisation).
+ * nh_acf_accumulate: adds rows [n0, n1) to the state; n0 == row_start starts it (nothing of it is
+ *   read); otherwise the state must hold rows [row_start, n0).  Reads at most 255 + L rows before
+ *   n0, copies nothing.  Every sum is one chain in the order of the rows: the state after rows
+ *   [a, b) is bit-identical however [a, b) was cut into calls.  n0 == n1: nothing is launched.
+ *   NH_EINVAL: n_w, n_d or L not positive, not 0 <= row_start <= n0 <= n1 <= rows.
+ * nh_acf_finalize: f (DEVICE [n_d][L]) from the state of rows [row_start, n): f[d][k] = the mean
+ *   over walkers of c_k / c_0 for k < min(L, n - row_start), NaN behind that, with
+ *   c_k = S_k - m ((T - P_k) + (T - Q_k)) + (n - row_start - k) m^2, m = T / (n - row_start), and
+ *   P_k / Q_k the sums of the first / last k values of y, read from the block: emcee's function_1d
+ *   per walker, averaged, as nh_autocorr_lags gives it.  A walker whose series is constant or
+ *   holds a non-finite value makes its dimension NaN.  Library scratch of 8*n_w*n_d*L bytes.
+ *   NH_EINVAL: n_w, n_d or L not positive, not 0 <= row_start < n <= rows. */
+int nh_acf_accumulate(nh_ctx* ctx, const double* x, long long rows, int n_w, int n_d,
+                      long long row_start, long long n0, long long n1, int L, double* pivot,
+                      double* S, double* stats);
+int nh_acf_finalize(nh_ctx* ctx, const double* x, long long rows, int n_w, int n_d,
+                    long long row_start, long long n, int L, const double* pivot, const double* S,
+                    const double* stats, double* f);
+
 /* ---- EBL absorption with a per-walker redshift (models.py:470-552) ------------------------
  * The reference picks the nearest of the tabulated redshifts zl = arange(0.01, 4, 0.01)
  * (models.py:520-528, no interpolation in z), clips log tau at 150 (models.py:529-531) and

@@ -159,6 +159,8 @@ _SIGS = {
     "nh_column_select": [_dp, _dp, _ll, _i, _ll, C.POINTER(_i), _i, _dp],
     "nh_autocorr_prep": [_dp, _dp, _ll, _i, _i, _i, _dp, _dp],
     "nh_autocorr_lags": [_dp, _dp, _dp, _ll, _i, _ll, _i, _dp],
+    "nh_acf_accumulate": [_dp, _dp, _ll, _i, _i, _ll, _ll, _ll, _i, _dp, _dp, _dp],
+    "nh_acf_finalize": [_dp, _dp, _ll, _i, _i, _ll, _ll, _i, _dp, _dp, _dp, _dp],
     "nh_hist_thin": [_dp, _dp, _i, _ll, _ll, _ll, _ll],
     "nh_ebl_table": [_dp, _dp, _i, _dp, _i, _dp, _dp, _i, _d, _dp, _dp],
     "nh_ebl_apply": [_dp, _dp, _i, _i, _dp, _i, _dp, _dp, _i, _dp, _i, _i, _dp, _i],

@@ -15,6 +15,10 @@
 //                     lane-consecutive, and writes one partial per lag.  A second launch sums the
 //                     partials in a fixed order.
 //
+//   nh_acf_accumulate, nh_acf_finalize  the same function of a chain block that GROWS in HBM, from
+//                     running lag sums (see "the running accumulator" below): a check every few
+//                     steps of a run costs the new rows only, and nothing leaves the device.
+//
 // No floating-point atomics: every sum has an order fixed by the shapes alone (not by the device),
 // so repeated calls, and ranks that hold the same chain, give bit-identical results.  Indices into
 // the chain and the series are 64-bit.  Every launch is on the context's stream.
@@ -187,6 +191,184 @@ __global__ void k_ac_reduce(const double* __restrict__ part, int nparts, long lo
 
 inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
 
+// ---- the running accumulator -------------------------------------------------------------------
+// Over the rows [row_start, n) of a chain block x[row][col] (col = w*n_d + d: a row is contiguous
+// over the series), with y = x - pivot[col], pivot = the series' first value, the state holds
+//   S[col][k] = sum_{t >= row_start + k} y[t] y[t-k], k < L     T[col] = sum y[t]     min, max of y
+// Every one of these is ONE accumulator chain in the order of t, so the state after rows [a, b) is
+// the same bit for bit however [a, b) was cut into calls (padding terms are fma(0, y, acc) or
+// fma(y, 0, acc) on a finite y: they leave acc as it is).  A workgroup takes ACF_CT adjacent
+// series and 256 lags (one per lane): it stages the ACF_TT new rows and the 255 + ACF_TT rows
+// behind them, 64 contiguous bytes per row, into LDS transposed to [series][t]; y[t] is then a
+// broadcast and y[t-k] lane-consecutive, and a lane carries ACF_CT independent chains.
+constexpr int ACF_CT = 8;                       // adjacent series per workgroup (64 B of a row)
+constexpr int ACF_TT = 128;                     // new rows per LDS stage
+constexpr int ACF_AS = ACF_TT + 2;              // row strides = 2 mod 16 doubles: the transposed
+constexpr int ACF_BT = ACF_TT + AC_LAGS;        //   stores of 16 lanes fall on 16 banks
+constexpr int ACF_BS = ACF_BT + 2;
+constexpr int ACF_HS = AC_LAGS + 2;
+static_assert(AC_THREADS == AC_LAGS && AC_THREADS % ACF_CT == 0, "a thread loads one series");
+
+__global__ void k_acf_pivot(const double* __restrict__ x, long long ld, long long row_start,
+                            double* __restrict__ pivot) {
+  long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < ld) pivot[c] = x[row_start * ld + c];
+}
+
+// adds rows [n0, n1) to S and stats = {T, min, max}[ld]; n0 == row_start: the state starts here
+// (nothing of it is read).  grid (series tiles, lag blocks)
+__global__ __launch_bounds__(AC_THREADS) void k_acf_accumulate(
+    const double* __restrict__ x, long long ld, long long row_start, long long n0, long long n1,
+    int L, const double* __restrict__ pivot, double* __restrict__ S, double* __restrict__ stats) {
+  __shared__ double As[ACF_CT][ACF_AS];  // y[t0 + i]                  (0 from n1 on)
+  __shared__ double Bs[ACF_CT][ACF_BS];  // y[t0 - k0 - 255 + j]       (0 before row_start)
+  const int kl = threadIdx.x;
+  const long long c0 = (long long)blockIdx.x * ACF_CT;
+  const long long k0 = (long long)blockIdx.y * AC_LAGS;
+  const long long k = k0 + kl;
+  const bool fresh = n0 == row_start;
+  // no earlier t has a partner t - k >= row_start for any lag of this workgroup
+  const long long tb = max(n0, row_start + k0);
+  if (tb >= n1 && !fresh) return;
+  double acc[ACF_CT];
+#pragma unroll
+  for (int c = 0; c < ACF_CT; ++c)
+    acc[c] = (!fresh && k < L && c0 + c < ld) ? S[(c0 + c) * L + k] : 0.0;
+  const int lc = kl % ACF_CT;  // the series this thread loads
+  const bool col_ok = c0 + lc < ld;
+  const double* xc = x + c0 + lc;
+  const double pv = col_ok ? pivot[c0 + lc] : 0.0;
+  const bool stat = blockIdx.y == 0 && kl < ACF_CT && col_ok;  // (kl == lc there)
+  double T = 0.0, lo = INFINITY, hi = -INFINITY;
+  if (stat && !fresh) {
+    T = stats[c0 + kl];
+    lo = stats[ld + c0 + kl];
+    hi = stats[2 * ld + c0 + kl];
+  }
+  for (long long t0 = tb; t0 < n1; t0 += ACF_TT) {
+    for (int idx = kl; idx < ACF_TT * ACF_CT; idx += AC_THREADS) {
+      int i = idx / ACF_CT;
+      long long t = t0 + i;
+      As[lc][i] = (col_ok && t < n1) ? xc[t * ld] - pv : 0.0;
+    }
+    for (int idx = kl; idx < ACF_BT * ACF_CT; idx += AC_THREADS) {
+      int j = idx / ACF_CT;
+      long long t = t0 - k0 - (AC_LAGS - 1) + j;
+      Bs[lc][j] = (col_ok && t >= row_start && t < n1) ? xc[t * ld] - pv : 0.0;
+    }
+    __syncthreads();
+    if (stat) {
+      int m = (int)min((long long)ACF_TT, n1 - t0);
+      for (int i = 0; i < m; ++i) {
+        double v = As[kl][i];
+        T += v;
+        lo = fmin(lo, v);
+        hi = fmax(hi, v);
+      }
+    }
+    const double* b = &Bs[0][AC_LAGS - 1 - kl];
+#pragma unroll 4
+    for (int i = 0; i < ACF_TT; ++i) {
+#pragma unroll
+      for (int c = 0; c < ACF_CT; ++c) acc[c] = fma(As[c][i], b[c * ACF_BS + i], acc[c]);
+    }
+    __syncthreads();
+  }
+  if (k < L) {
+#pragma unroll
+    for (int c = 0; c < ACF_CT; ++c)
+      if (c0 + c < ld) S[(c0 + c) * L + k] = acc[c];
+  }
+  if (stat) {
+    stats[c0 + kl] = T;
+    stats[ld + c0 + kl] = lo;
+    stats[2 * ld + c0 + kl] = hi;
+  }
+}
+
+// c_k = sum_{t >= k} (y[t] - m)(y[t-k] - m) = S_k - m ((T - P_k) + (T - Q_k)) + (n - k) m^2, with
+// P_k / Q_k the sums of the first / last k values of y (one sequence of operations for every k,
+// so that c_k / c_0 is exactly 1 at k = 0)
+__device__ inline double acf_ck(double S, double T, double m, double P, double Q, double nk) {
+  double u = (T - P) + (T - Q);
+  return fma(nk * m, m, fma(-m, u, S));
+}
+
+// R[col][k] = c_k / c_0 of series col for k < Lc (NaN throughout for a series that is constant or
+// holds a non-finite value); nn = n - row_start values per series.  grid (series tiles)
+__global__ __launch_bounds__(AC_THREADS) void k_acf_ratio(
+    const double* __restrict__ x, long long ld, long long row_start, long long nn, int L, int Lc,
+    const double* __restrict__ pivot, const double* __restrict__ S,
+    const double* __restrict__ stats, double* __restrict__ R) {
+  __shared__ double Ps[ACF_CT][ACF_HS];  // the first values of y, then their exclusive prefix sums
+  __shared__ double Qs[ACF_CT][ACF_HS];  // the last values, backwards, likewise
+  __shared__ double sT[ACF_CT], sm[ACF_CT], sc0[ACF_CT];
+  const int tid = threadIdx.x;
+  const long long c0 = (long long)blockIdx.x * ACF_CT;
+  const int lc = tid % ACF_CT;
+  const bool col_ok = c0 + lc < ld;
+  const double* xc = x + c0 + lc;
+  const double pv = col_ok ? pivot[c0 + lc] : 0.0;
+  if (tid < ACF_CT) {
+    double T = 0.0, m = 0.0, c0v = NAN;
+    if (col_ok) {  // (tid == lc)
+      T = stats[c0 + tid];
+      double lo = stats[ld + c0 + tid], hi = stats[2 * ld + c0 + tid];
+      m = T / (double)nn;
+      double v = acf_ck(S[(c0 + tid) * L], T, m, 0.0, 0.0, (double)nn);
+      if (isfinite(T) && lo < hi && isfinite(v) && v > 0.0) c0v = v;
+    }
+    sT[tid] = T;
+    sm[tid] = m;
+    sc0[tid] = c0v;
+  }
+  double carry = 0.0;  // of the scan this thread makes (tid < 2 * ACF_CT)
+  for (long long kt = 0; kt < Lc; kt += AC_LAGS) {
+    for (int idx = tid; idx < AC_LAGS * ACF_CT; idx += AC_THREADS) {
+      int j = idx / ACF_CT;
+      long long kk = kt + j;
+      bool ok = col_ok && kk < nn;
+      Ps[lc][j] = ok ? xc[(row_start + kk) * ld] - pv : 0.0;
+      Qs[lc][j] = ok ? xc[(row_start + nn - 1 - kk) * ld] - pv : 0.0;
+    }
+    __syncthreads();
+    if (tid < 2 * ACF_CT) {
+      double* a = tid < ACF_CT ? Ps[tid] : Qs[tid - ACF_CT];
+      for (int j = 0; j < AC_LAGS; ++j) {
+        double v = a[j];
+        a[j] = carry;
+        carry += v;
+      }
+    }
+    __syncthreads();
+    long long kk = kt + tid;
+    if (kk < Lc) {
+      for (int c = 0; c < ACF_CT; ++c) {
+        if (c0 + c >= ld) break;
+        double ck = acf_ck(S[(c0 + c) * L + kk], sT[c], sm[c], Ps[c][tid], Qs[c][tid],
+                           (double)(nn - kk));
+        R[(c0 + c) * L + kk] = ck / sc0[c];
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// f[d][k] = the mean over the walkers, in their order, of R[w*n_d + d][k]; NaN for k >= Lc
+__global__ void k_acf_mean(const double* __restrict__ R, int n_w, int n_d, int L, int Lc,
+                           double* __restrict__ f) {
+  int k = blockIdx.x * blockDim.x + threadIdx.x;
+  int d = blockIdx.y;
+  if (k >= L) return;
+  double s = NAN;
+  if (k < Lc) {
+    s = 0.0;
+    for (int w = 0; w < n_w; ++w) s += R[((long long)w * n_d + d) * L + k];
+    s /= (double)n_w;
+  }
+  f[(long long)d * L + k] = s;
+}
+
 }  // namespace
 
 extern "C" int nh_autocorr_prep(nh_ctx* ctx, const double* x, long long n_t, int n_w, int n_d,
@@ -249,6 +431,58 @@ extern "C" int nh_autocorr_lags(nh_ctx* ctx, const double* z, const double* s2, 
   NH_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_ac_reduce, dim3((unsigned)cdiv(nlags, AC_THREADS)), dim3(AC_THREADS), 0, s,
                      part, (int)nparts, ldp, nlags, n_w, f);
+  NH_CHECK_HIP(hipGetLastError());
+  return NH_OK;
+}
+
+extern "C" int nh_acf_accumulate(nh_ctx* ctx, const double* x, long long rows, int n_w, int n_d,
+                                 long long row_start, long long n0, long long n1, int L,
+                                 double* pivot, double* S, double* stats) {
+  NH_REQUIRE(ctx && x && pivot && S && stats, "null argument");
+  NH_REQUIRE(n_w > 0, "n_w must be positive");
+  NH_REQUIRE(n_d > 0, "n_d must be positive");
+  NH_REQUIRE(L > 0, "L must be positive");
+  NH_REQUIRE(0 <= row_start && row_start <= n0 && n0 <= n1 && n1 <= rows,
+             "need 0 <= row_start <= n0 <= n1 <= rows");
+  long long ld = (long long)n_w * n_d;
+  long long tiles = cdiv(ld, ACF_CT), lagb = cdiv(L, AC_LAGS);
+  NH_REQUIRE(tiles < (1ll << 31) && lagb <= 65535, "too many series or lags for one launch");
+  if (n0 == n1) return NH_OK;
+  hipStream_t s = ctx->stream;
+  if (n0 == row_start) {
+    hipLaunchKernelGGL(k_acf_pivot, dim3((unsigned)cdiv(ld, AC_THREADS)), dim3(AC_THREADS), 0, s, x,
+                       ld, row_start, pivot);
+    NH_CHECK_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_acf_accumulate, dim3((unsigned)tiles, (unsigned)lagb), dim3(AC_THREADS), 0,
+                     s, x, ld, row_start, n0, n1, L, pivot, S, stats);
+  NH_CHECK_HIP(hipGetLastError());
+  return NH_OK;
+}
+
+extern "C" int nh_acf_finalize(nh_ctx* ctx, const double* x, long long rows, int n_w, int n_d,
+                               long long row_start, long long n, int L, const double* pivot,
+                               const double* S, const double* stats, double* f) {
+  NH_REQUIRE(ctx && x && pivot && S && stats && f, "null argument");
+  NH_REQUIRE(n_w > 0, "n_w must be positive");
+  NH_REQUIRE(n_d > 0 && n_d <= 65535, "n_d outside [1, 65535]");
+  NH_REQUIRE(L > 0, "L must be positive");
+  NH_REQUIRE(0 <= row_start && row_start < n && n <= rows, "need 0 <= row_start < n <= rows");
+  long long ld = (long long)n_w * n_d;
+  long long tiles = cdiv(ld, ACF_CT);
+  NH_REQUIRE(tiles < (1ll << 31), "too many series for one launch");
+  long long nn = n - row_start;
+  int Lc = (int)std::min<long long>(L, nn);
+  void* base = nullptr;
+  int rc = nh_scratch(ctx, (size_t)ld * L * sizeof(double), &base);
+  if (rc) return rc;
+  double* R = (double*)base;  // [ld][L]
+  hipStream_t s = ctx->stream;
+  hipLaunchKernelGGL(k_acf_ratio, dim3((unsigned)tiles), dim3(AC_THREADS), 0, s, x, ld, row_start,
+                     nn, L, Lc, pivot, S, stats, R);
+  NH_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_acf_mean, dim3((unsigned)cdiv(L, AC_THREADS), (unsigned)n_d),
+                     dim3(AC_THREADS), 0, s, R, n_w, n_d, L, Lc, f);
   NH_CHECK_HIP(hipGetLastError());
   return NH_OK;
 }

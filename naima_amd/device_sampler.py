@@ -618,7 +618,43 @@ class DeviceLoop:
                     block["cur0"].append(c0)
         return block
 
-    def _sample_thinned(self, rows, t, store, yield_every, block, jentry):
+    def sample_monitored(self, initial_state, max_rows, check_every, thin_by, on_check):
+        """up to ``max_rows`` stored rows into ONE history block of that many rows (the memory of a
+        ``run_mcmc(max_rows)`` call), made as internal calls of ``check_every`` rows, each of which
+        may take the resident loop and ends with its launches settled (what _steps ends with).
+        After each, ``on_check(the block's coordinate buffer, its rows so far)`` looks at the
+        chain where it is, in HBM; a true answer ends the call.  With thin_by > 1 the block is the
+        compact one, in stored rows (_sample_thinned's staging, one staging block per internal
+        call).  The books are those of plain calls: the block is a pending history block like any
+        other and holds ``block["n"]`` rows.  One GPU only -> the last state"""
+        from .sampler import State
+        s = self.s
+        if self.sharded:
+            raise NotImplementedError("a monitored run with walkers sharded over several ranks")
+        cont = isinstance(initial_state, DeviceState) and initial_state._loop is self
+        if not cont:  # (as sample does)
+            st = State(initial_state)
+            if st.coords.shape != (self.N, self.ndim):
+                raise ValueError("incompatible input dimensions")
+            self._init_state(st.coords, st.log_prob)
+        max_rows, check_every, thin_by = int(max_rows), int(check_every), int(thin_by)
+        block = self._new_block(max_rows)
+        self.hist.append(block)
+        if not cont:
+            self._sync_cur_blobs()
+        while block["n"] < max_rows:
+            g = min(check_every, max_rows - block["n"])
+            if thin_by == 1:
+                for _ in self._steps(g, 1 << 30, block, None):
+                    pass
+            else:
+                for _ in self._sample_thinned(g, thin_by, True, 1 << 30, None, None, compact=block):
+                    pass
+            if on_check(block["coords"], block["n"]):
+                break
+        return DeviceState(self, s._rng)
+
+    def _sample_thinned(self, rows, t, store, yield_every, block, jentry, compact=None):
         """`rows` stored rows of `t` steps each.  One GPU, history kept: the steps run as internal
         calls of c*t steps that write a staging block of c*t rows through the usual paths; once
         a call's launches are known to have ended well (what _steps ends with), ONE launch copies
@@ -627,13 +663,14 @@ class DeviceLoop:
         the staging block's allocation within NAIMA_AMD_THIN_STAGE_MB (default 512).  If not even
         t rows fit, a stored row is t-1 steps without a history and one step with it, and the
         staging block holds one row.  `block` (several ranks): the full-rate block, thinned on
-        the host by flush.  thin_info says what was done."""
+        the host by flush.  `compact` (a monitored run): the pending block that takes the rows,
+        from its row compact["n"] on, instead of a new one.  thin_info says what was done."""
         s, ctx, N = self.s, self.ctx, self.N
         group = rows if yield_every >= rows else max(1, int(yield_every))
         info = dict(thin_by=t, where="host" if block is not None else "none", stage_rows=0,
                     stage_bytes=0, stage_alloc_bytes=0, calls=[])
         self.thin_info = info
-        compact = stage = None
+        stage = None
         split = False
         if store and rows > 0 and block is None:
             widths = [N * self.ndim, N]
@@ -651,8 +688,9 @@ class DeviceLoop:
             split = lo == 0
             group = max(1, lo)
             srows = 1 if split else group * t
-            compact = self._new_block(rows)
-            self.hist.append(compact)
+            if compact is None:
+                compact = self._new_block(rows)
+                self.hist.append(compact)
             stage = self._new_block(srows)
             info.update(where="device", stage_rows=srows, stage_bytes=8 * srows * sum(widths),
                         stage_alloc_bytes=alloc(srows))

@@ -377,6 +377,89 @@ class EnsembleSampler:
         return state
 
 
+    def run_until_converged(self, initial_state, max_steps, check_every=100, tol=50, rtol=0.01,
+                            c=5, discard=0, thin_by=1, max_lag=1024):
+        """Run until the integrated autocorrelation time has converged (the loop of emcee's
+        tutorial "Autocorrelation analysis & convergence"), ``max_steps`` stored rows at the most.
+
+        Every ``check_every`` stored rows the autocorrelation time ``tau`` of the rows this call has
+        stored behind its first ``discard`` is estimated (``integrated_time(..., c=c, tol=0)``, in
+        stored rows); the run stops at the first check with ``all(tau * tol < n)`` and
+        ``all(|tau_old - tau| / tau < rtol)``, n being the number of those rows
+        (``autocorr.converged``).  A NaN ``tau`` never converges (one warning).  ``thin_by`` is
+        ``run_mcmc``'s.  Returns the last state; ``self.convergence`` says how it went:
+        ``converged``, ``rows`` (stored by this call), ``tau``, ``history`` (``(rows, tau)`` of every
+        check), ``where``, ``max_lag`` and ``rebuilds``.
+
+        On the device loop (``where == "device"``) the chain stays in HBM: the call allocates ONE
+        history block of ``max_steps`` rows -- the memory of ``run_mcmc(max_steps)`` -- that its
+        groups of ``check_every`` rows fill, and the lag sums below ``max_lag`` grow with it
+        (``autocorr.RunningAutocorr``).  The host-driven loop (``where == "host"``) calls
+        ``integrated_time`` on its chain at every check.  Several ranks: not implemented."""
+        import warnings
+
+        from . import autocorr
+        max_steps, check_every, discard = int(max_steps), int(check_every), int(discard)
+        thin_by, max_lag = int(thin_by), int(max_lag)
+        if max_steps <= 0 or check_every <= 0:
+            raise ValueError("max_steps and check_every must be positive")
+        if not 0 <= discard < max_steps:
+            raise ValueError("discard must lie in [0, max_steps)")
+        if max_lag < 2:
+            raise ValueError("max_lag must be at least 2")
+        if thin_by <= 0:
+            raise ValueError("Invalid thinning argument")
+        if self.comm.size > 1 or (self.device and
+                                  os.environ.get("NAIMA_AMD_FORCE_SHARDED", "0") == "1"):
+            raise NotImplementedError("run_until_converged with walkers sharded over several ranks")
+        info = dict(converged=False, rows=0, tau=np.full(self.ndim, np.nan), history=[],
+                    where="host", max_lag=max_lag, rebuilds=0)
+        self.convergence = info
+        old, warned = [np.inf], []
+
+        def check(rows, tau):
+            """the books of one check -> stop?"""
+            tau = np.asarray(tau, dtype=float)
+            info["history"].append((rows, tau))
+            info["rows"], info["tau"] = rows, tau
+            if np.any(np.isnan(tau)) and not warned:
+                warned.append(True)
+                warnings.warn("the autocorrelation time of a parameter is NaN (a constant walker "
+                              "or a non-finite value): the run cannot converge")
+            info["converged"] = autocorr.converged(tau, old[0], rows - discard, tol, rtol)
+            old[0] = tau
+            return info["converged"]
+
+        if self.device and self._dev is None and self._device_ok is None:
+            self._device_ok = self._probe_device(initial_state)
+        if self.device and self._device_ok is not False:
+            from .device_sampler import DeviceLoop
+            if self._dev is None:
+                self._dev = DeviceLoop(self)
+            info["where"] = "device"
+            ra = autocorr.RunningAutocorr(self.nwalkers, self.ndim, max_lag, c)
+
+            def on_check(buf, rows):
+                if rows <= discard:
+                    return False
+                ra.update(buf, rows, discard)
+                tau = ra.tau()[0]
+                info["max_lag"], info["rebuilds"] = ra.max_lag, ra.rebuilds
+                return check(rows, tau)
+
+            state = self._dev.sample_monitored(initial_state, max_steps, check_every, thin_by,
+                                               on_check)
+        else:
+            state, rows, it0 = initial_state, 0, self.iteration
+            while rows < max_steps:
+                g = min(check_every, max_steps - rows)
+                state = self.run_mcmc(state, g, thin_by=thin_by)
+                rows += g
+                if rows > discard and check(rows, autocorr.integrated_time(
+                        self.get_chain()[it0 + discard:], c=c, tol=0)):
+                    break
+        return state
+
 # --------------------------------------------------------------------------
 # naima's entry points (core.py:220-538)
 # --------------------------------------------------------------------------
@@ -524,10 +607,16 @@ def get_sampler(data_table=None, p0=None, model=None, prior=None, nwalkers=500, 
     return sampler, state
 
 
-def run_sampler(nrun=100, sampler=None, pos=None, verbose=True, thin_by=1, **kwargs):
+def run_sampler(nrun=100, sampler=None, pos=None, verbose=True, thin_by=1, converge=None,
+                **kwargs):
     """Run an MCMC sampler (core.py:496-538).  ``thin_by`` = t (emcee's): ``nrun`` is the number
     of STORED rows, each t ensemble steps after the one before; ``run_info["thin_by"]`` records
-    it.  The burn-in of ``get_sampler`` is not thinned."""
+    it.  The burn-in of ``get_sampler`` is not thinned.
+
+    ``converge`` = True, or a dict of ``EnsembleSampler.run_until_converged``'s keywords
+    (``check_every``, ``tol``, ``rtol``, ``c``, ``discard``, ``max_lag``): ``nrun`` is then the
+    MAXIMUM, the run stops once the autocorrelation time has converged, and ``run_info`` gains
+    ``converged`` and ``autocorr_time`` (in stored rows)."""
     thin_by = int(thin_by)
     if thin_by <= 0:
         raise ValueError("Invalid thinning argument")
@@ -545,6 +634,17 @@ def run_sampler(nrun=100, sampler=None, pos=None, verbose=True, thin_by=1, **kwa
         pos = State(pos.coords)
     elif not hasattr(pos, "_loop"):  # (a DeviceState continues from the ensemble in HBM)
         pos = State(pos)
-    sampler, pos = _run_mcmc(sampler, pos, nrun, verbose, thin_by)
+    if converge:
+        opts = dict(converge) if isinstance(converge, dict) else {}
+        pos = sampler.run_until_converged(pos, int(nrun), thin_by=thin_by, **opts)
+        conv = sampler.convergence
+        sampler.run_info["converged"] = bool(conv["converged"])
+        sampler.run_info["autocorr_time"] = [float(t) for t in conv["tau"]]
+        if verbose and sampler.comm.rank == 0:
+            print("{0} after {1} of at most {2} steps; autocorrelation time: {3}".format(
+                "Converged" if conv["converged"] else "Not converged", conv["rows"], int(nrun),
+                conv["tau"]))
+    else:
+        sampler, pos = _run_mcmc(sampler, pos, nrun, verbose, thin_by)
     sampler.run_info["wall_s"] = time.time() - t0
     return sampler, pos
