@@ -243,8 +243,10 @@ int nh_table_pion_lut(nh_ctx* ctx, const double* Ep_GeV, int nG, const double* E
  * approximation (:1693-1714) below, joined at Etrans by nhat (:1743-1748) when `mixed`
  * (the host sets it when energies lie on both sides).  params: the [N][8] particle rows of
  * nh_particle_weights (eV).  The reference's adaptive quad (epsrel 1e-3) is replaced by a
- * converged fixed Gauss-Legendre rule.  nhat_out[N], wp_TeV_out[N] (the `Wp` property,
- * :1716-1728, in TeV) may be NULL. */
+ * fixed Gauss-Legendre rule whose panels end at the integrand's kinks: within 1e-8 of the
+ * converged integral for every kind.  nhat_out[N], wp_TeV_out[N] (the `Wp` property,
+ * :1716-1728, in TeV) may be NULL.  EINVAL: a kind outside the enum, nE < 1, ldo < nE,
+ * Etrans_eV <= 0, nE + 3 doubles beyond 60 KiB of LDS.  N = 0 is no error. */
 int nh_pion_kelner06(nh_ctx* ctx, int kind, const double* params, int N, const double* E_eV,
                      int nE, double Etrans_eV, int mixed, double* out, int ldo,
                      double* nhat_out, double* wp_TeV_out);

@@ -10,9 +10,23 @@
 //   E_gamma <  Etrans (delta-functional, :1693-1714):
 //       2 int_{Epimin}^inf q_pi / sqrt(Epi^2 - m_pi^2) dEpi,  Epi = m_pi cosh(s)
 //       -> 2 int_{s_min}^{s_min+T} q_pi(m_pi cosh s) ds      (the root singularity is gone)
-// T = 64 (the integrands fall like exp(-(alpha-1) t)), 128 panels x 8 points.  The result
-// is the CONVERGED integral: it differs from the reference's number by the reference's
-// own quadrature error (measured 4e-5, bound 1e-3); tests/test_oracle.py pins both.
+// T = 64 (the integrands fall like exp(-(alpha-1) t)), panels of h = 0.5 x 8 points.
+//
+// A fixed rule converges spectrally only where the integrand is smooth inside every panel, so
+// no panel straddles a kink: the break energy of the broken power laws (a jump of the slope)
+// and the two of k06_sigma_inel (0.1 TeV, where it changes form with a relative jump of
+// 4.4e-8, and the 1.22e-3 TeV threshold).  Each is mapped to the integration variable; the
+// stretch up to it is cut into ceil(length / h) equal panels and the h-grid starts again
+// behind it.  Without this a broken power law was 1e-4 off, with a sign and size that changed
+// as e_break moved across panel edges.  A cut-off that is already steep where the range
+// starts -- beta (E/e_cutoff)^beta > 2, a photon energy beyond the cut-off -- is resolved in
+// the same way: the 40 e-foldings in which it kills the integrand get panels of its own
+// e-folding length in t.
+//
+// The result is the CONVERGED integral to 1e-8 (tests/test_gpu_kelner.py: every kind, against
+// a reference certified by mpmath; measured figures in profiles/NOTES_kelner.md): it differs
+// from the reference's number by the reference's own quadrature error (measured 4e-5, bound
+// 1e-3); tests/test_oracle.py pins both.
 #include "nh_pdist.h"
 
 namespace {
@@ -23,6 +37,10 @@ constexpr double K06_MPI_TEV = 1.349766e-4;            // :1691
 constexpr double K06_ETH_TEV = 1.22e-3;                // :1643
 constexpr int K06_PANELS = 128;
 constexpr double K06_H = 0.5;
+constexpr int K06_KINKS = 4;                           // e_break, 0.1 TeV, threshold, steep cut-off
+constexpr double K06_SEG_PANELS_MAX = 8.0 * K06_PANELS;  // per stretch between two kinks
+constexpr double K06_SIGMA_SWITCH_TEV = 0.1;           // :1640
+constexpr double K06_CUT_EFOLDS = 40.0;                // exp(-40): nothing left of the integrand
 
 __constant__ double GLX[8] = {-0.9602898564975363, -0.7966664774136267, -0.5255324099163290,
                               -0.1834346424956498, 0.1834346424956498,  0.5255324099163290,
@@ -35,7 +53,7 @@ __constant__ double GLW[8] = {0.1012285362903763, 0.2223810344533745, 0.31370664
 __device__ __forceinline__ double k06_sigma_inel(double Ep) {
   const double L = log(Ep);
   double s = 34.3 + 1.88 * L + 0.25 * L * L;
-  if (Ep <= 0.1) {
+  if (Ep <= K06_SIGMA_SWITCH_TEV) {
     const double r = K06_ETH_TEV / Ep, r2 = r * r;
     const double f = 1.0 - r2 * r2;
     s *= f * f * nh_heaviside(Ep - K06_ETH_TEV);
@@ -73,19 +91,79 @@ __device__ __forceinline__ double k06_wave_sum(double v) {
   return __shfl(v, 0, 64);
 }
 
+// proton energy [TeV] -> integration variable: the inverse of the node maps in k06_integral
+// (an energy the variable never reaches gives a value at or below the range's start, or NaN)
+__device__ __forceinline__ double k06_t_of(int mode, double Ep, double Eg) {
+  if (mode == 0) return log(Ep / Eg);
+  if (mode == 1) return acosh(fmax((Ep - K06_MP_TEV) * K06_KPI / K06_MPI_TEV, 1.0));
+  return log(Ep / K06_ETH_TEV);
+}
+
 // mode 0: full calculation at E_gamma; mode 1: delta-functional (nhat = 1); mode 2: Wp
 __device__ double k06_integral(int mode, int kind, const pd_par& p, double Eg, int lane) {
-  double t0 = 0.0;
+  double t0 = 0.0, Estart = mode == 0 ? Eg : K06_ETH_TEV;
   if (mode == 1) {
     const double Epimin = Eg + K06_MPI_TEV * K06_MPI_TEV / (4.0 * Eg);
     t0 = acosh(fmax(Epimin / K06_MPI_TEV, 1.0));
+    Estart = K06_MP_TEV + Epimin / K06_KPI;
   }
-  double acc = 0.0;
   // Wp's integrand falls only like exp(-(alpha-2) t): eight times the range
   const int panels = mode == 2 ? 8 * K06_PANELS : K06_PANELS;
-  for (int n = lane; n < panels * 8; n += 64) {
+  const double tend = t0 + panels * K06_H;
+
+  // the kinks inside (t0, tend); one that is absent is NaN and never chosen
+  double tk[K06_KINKS];
+  tk[0] = pd_has_break(kind) ? k06_t_of(mode, p.eb * 1e-12, Eg) : __builtin_nan("");
+  tk[1] = k06_t_of(mode, K06_SIGMA_SWITCH_TEV, Eg);
+  tk[2] = k06_t_of(mode, K06_ETH_TEV, Eg);
+  tk[3] = __builtin_nan("");
+  // a steep cut-off: up to tk[3], where it has fallen by K06_CUT_EFOLDS, panels of width h_cut
+  // (d ln E / dt <= 1 in every mode, so 1 / (beta x0) is at most its e-folding length in t)
+  double h_cut = K06_H;
+  if (pd_has_cutoff(kind)) {
+    const double x0 = pow(Estart / (p.ec * 1e-12), p.be);
+    if (p.be * x0 > 2.0) {
+      tk[3] = k06_t_of(mode, Estart * pow(1.0 + K06_CUT_EFOLDS / x0, 1.0 / p.be), Eg);
+      h_cut = 1.0 / (p.be * x0);
+    }
+  }
+  // stretch s = 0..K06_KINKS-1 ends at the s-th kink in ascending order (empty when there
+  // are fewer); the last one is the plain h-grid behind the last kink
+  double sa[K06_KINKS + 1], sw[K06_KINKS + 1];
+  int sp[K06_KINKS + 1];  // a stretch's first panel
+  double cur = t0;
+  int np = 0;
+#pragma unroll
+  for (int s = 0; s < K06_KINKS; ++s) {
+    double nx = tend;
+#pragma unroll
+    for (int c = 0; c < K06_KINKS; ++c)
+      if (tk[c] > cur && tk[c] < nx) nx = tk[c];
+    sa[s] = cur;
+    sw[s] = K06_H;
+    sp[s] = np;
+    if (nx < tend) {
+      const double hs = cur < tk[3] ? h_cut : K06_H;
+      const double cnt = fmin(fmax(ceil((nx - cur) / hs), 1.0), K06_SEG_PANELS_MAX);
+      sw[s] = (nx - cur) / cnt;
+      np += (int)cnt;
+      cur = nx;
+    }
+  }
+  sa[K06_KINKS] = cur;
+  sw[K06_KINKS] = K06_H;
+  sp[K06_KINKS] = np;
+  np += panels;
+
+  double acc = 0.0;
+  for (int n = lane; n < np * 8; n += 64) {
     const int pan = n >> 3, q = n & 7;
-    const double t = t0 + (pan + 0.5 * (1.0 + GLX[q])) * K06_H;
+    double a = sa[0], w = sw[0];
+    int first = 0;
+#pragma unroll
+    for (int s = 1; s <= K06_KINKS; ++s)
+      if (pan >= sp[s]) a = sa[s], w = sw[s], first = sp[s];
+    const double t = a + (pan - first + 0.5 * (1.0 + GLX[q])) * w;
     double f;
     if (mode == 0) {
       const double Ep = Eg * exp(t);
@@ -98,9 +176,9 @@ __device__ double k06_integral(int mode, int kind, const pd_par& p, double Eg, i
       f = E * E * k06_J(kind, p, E);
     }
     if (!(f == f) || isinf(f)) f = 0.0;  // overflowed tails contribute nothing
-    acc += GLW[q] * f;
+    acc += GLW[q] * w * f;
   }
-  acc = k06_wave_sum(acc) * (0.5 * K06_H);
+  acc = k06_wave_sum(acc) * 0.5;
   if (mode == 0) return NH_C_CGS * acc;
   if (mode == 1) return 2.0 * NH_C_CGS / K06_KPI * acc;
   return acc;

@@ -1410,9 +1410,10 @@ class PionDecayKelner06(BaseRadiative):
     delta-functional approximation below, normalised to meet at ``Etrans``.
 
     The reference integrates adaptively (scipy ``quad``, epsrel = 1e-3) one photon energy
-    at a time; here every (walker, energy) is one wave with a converged fixed rule
-    (``nh_pion_kelner06``), so values agree with the reference within its own quadrature
-    tolerance (measured 4e-5) and with the converged integral to 1e-9."""
+    at a time; here every (walker, energy) is one wave with a fixed rule whose panels end at
+    the integrand's kinks (``nh_pion_kelner06``), so values agree with the reference within
+    its own quadrature tolerance (measured 4e-5) and with the converged integral to 1e-8,
+    for every analytic particle distribution, ``nhat`` and ``Wp`` included."""
     param_names = ["nh", "Etrans"]
     _walker_scalars = ("nh",)
 

@@ -22,6 +22,7 @@ Conventions (all float64, no unit objects):
 Every function cites the reference file:line it follows (paths relative to
 /root/reference/src/naima/).
 """
+import math
 import warnings
 
 import numpy as np
@@ -623,12 +624,37 @@ def k06_sigma_inel(Ep):
     return sigma * 1e-27
 
 
-def k06_spectrum(E_eV, J_per_TeV, nh=1.0, Etrans_TeV=0.1, epsrel=1e-3):
+K06_SIGMA_SWITCH_TEV = 0.1        # k06_sigma_inel changes form here (radiative.py:1640)
+K06_QUAD_LIMIT = 400              # subdivisions per piece of a split integral
+
+
+def k06_kinks(breaks_TeV):
+    """the proton energies [TeV] at which a Kelner06 integrand is not smooth: the listed
+    ones (a broken power law's e_break) and the two of k06_sigma_inel; sorted, unique"""
+    return sorted(set(float(b) for b in breaks_TeV) | {K06_SIGMA_SWITCH_TEV, K06_ETH_TEV})
+
+
+def _k06_quad_pieces(f, ends, epsrel):
+    """sum of one quad per interval of the ascending ``ends`` (the last may be inf)"""
+    from scipy.integrate import quad
+    return math.fsum(quad(f, a, b, epsrel=epsrel, epsabs=0, limit=K06_QUAD_LIMIT)[0]
+                     for a, b in zip(ends[:-1], ends[1:]))
+
+
+def k06_spectrum(E_eV, J_per_TeV, nh=1.0, Etrans_TeV=0.1, epsrel=1e-3, breaks_TeV=()):
     """radiative.py:1649-1767: differential luminosity 1/(s eV) at photon energies E_eV.
     ``J_per_TeV(E_TeV)``: particles per TeV.  ``epsrel`` = the reference's quad
-    tolerance (1e-3); smaller values give the converged integrals.  Returns (spec, nhat)."""
+    tolerance (1e-3); smaller values give the converged integrals.  Returns (spec, nhat).
+
+    ``breaks_TeV``: proton energies at which J has a kink.  Empty (the default): the
+    reference's two unbroken quad calls.  Otherwise every integral is split there and at the
+    two kinks of k06_sigma_inel (0.1 TeV and 1.22e-3 TeV) wherever they lie inside its range,
+    one quad per piece -- without that an adaptive rule's error estimate cannot be trusted
+    below ~1e-6 for a broken power law.  (Pass a break that is one of those two, e.g.
+    ``(0.1,)``, to split a smooth distribution's integrals at the cross section's kinks only.)"""
     from scipy.integrate import quad
     Eg = np.atleast_1d(np.asarray(E_eV, dtype=float)) * 1e-12
+    kinks = k06_kinks(breaks_TeV) if len(breaks_TeV) else ()
 
     def hiE(Egamma):  # Eq. 72, radiative.py:1665-1684
         def f(x):
@@ -637,6 +663,9 @@ def k06_spectrum(E_eV, J_per_TeV, nh=1.0, Etrans_TeV=0.1, epsrel=1e-3):
                         * k06_Fgamma(x, Egamma / x) / x)
             except ZeroDivisionError:
                 return np.nan
+        if kinks:  # x = Egamma / E_b of the kinks above Egamma (one within rounding of it: none)
+            ends = [0.0] + sorted(Egamma / b for b in kinks if b > Egamma * (1 + 1e-12)) + [1.0]
+            return C_CGS * _k06_quad_pieces(f, ends, epsrel)
         return C_CGS * quad(f, 0.0, 1.0, epsrel=epsrel, epsabs=0)[0]
 
     def loE(Egamma, nhat):  # delta-functional approximation, radiative.py:1693-1714
@@ -645,6 +674,10 @@ def k06_spectrum(E_eV, J_per_TeV, nh=1.0, Etrans_TeV=0.1, epsrel=1e-3):
             qpi = C_CGS * (nhat / K06_KPI) * k06_sigma_inel(Ep0) * J_per_TeV(Ep0)
             return qpi / np.sqrt(Epi ** 2 - K06_MPI_TEV ** 2)
         Epimin = Egamma + K06_MPI_TEV ** 2 / (4 * Egamma)
+        if kinks:  # E_pi = (E_b - m_p) K_pi of the kinks whose pion lies above Epimin
+            mid = sorted((b - K06_MP_TEV) * K06_KPI for b in kinks)
+            ends = [Epimin] + [e for e in mid if e > Epimin * (1 + 1e-12)] + [np.inf]
+            return 2 * _k06_quad_pieces(f, ends, epsrel)
         return 2 * quad(f, Epimin, np.inf, epsrel=epsrel, epsabs=0)[0]
 
     nhat = 1.0
@@ -656,6 +689,18 @@ def k06_spectrum(E_eV, J_per_TeV, nh=1.0, Etrans_TeV=0.1, epsrel=1e-3):
                 nhat = hiE(Etrans_TeV) / loE(Etrans_TeV, 1.0)
             spec = np.array([hiE(e) if e >= Etrans_TeV else loE(e, nhat) for e in Eg])
     return nh * spec * 1e-12, nhat  # 1/(s TeV) -> 1/(s eV)
+
+
+def k06_Wp(J_per_TeV, breaks_TeV=(), epsrel=1e-11):
+    """radiative.py:1716-1728: energy in protons above 1.22e-3 TeV, int E J dE [TeV]; split
+    at ``breaks_TeV`` and at 0.1 TeV like k06_spectrum (empty: one quad over the whole range)"""
+    def f(E):
+        return E * J_per_TeV(E)
+    kinks = k06_kinks(breaks_TeV) if len(breaks_TeV) else ()
+    ends = [K06_ETH_TEV] + [b for b in kinks if b > K06_ETH_TEV] + [np.inf]
+    with np.errstate(all="ignore"), warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        return _k06_quad_pieces(f, ends, epsrel)
 
 
 # ---------------------------------------------------------------------------
