@@ -747,7 +747,18 @@ int nh_half_step_append_blobs(nh_ctx* ctx, const nh_halfstep_plan* plan, long lo
 typedef struct nh_moves nh_moves;
 int nh_moves_create(unsigned long long seed, int N, double a, int ksteps_per_block, int depth,
                     int pinned, nh_moves** out);
-/* up to `want` consecutive steps, contiguous in host memory (2*got slices); depth >= 3.
+/* k independent ensembles of n walkers each as ONE stream of N = k*n walkers (ns = k*n/2): k
+ * generator states, state r seeded as nh_moves_create(seeds[r], n, ...) seeds its own.  Per
+ * ensemble step every ensemble r runs the recipe above on its own state with N = n and writes its
+ * n/2 entries at [r*n/2, (r+1)*n/2) of z, ln U', S and partner of both slices, r*n added to S and
+ * partner.  Ensemble r's sub-stream is therefore bit for bit the stream of
+ * nh_moves_create(seeds[r], n, a, ...) apart from that offset; walkers [r*n, (r+1)*n) form
+ * ensemble r, and every partner lies in the inactive half of its own ensemble.  k == 1 is
+ * nh_moves_create's stream.  seeds is a HOST array of k values, read during the call only.
+ * NH_EINVAL: k < 1, n odd or < 2, k*n beyond an int, a null seeds or out, a <= 1, depth < 3. */
+int nh_moves_create_ensembles(const unsigned long long* seeds /*host*/, int k, int n, double a,
+                              int ksteps_per_block, int depth, int pinned, nh_moves** out);
+/* both kinds of stream: up to `want` consecutive steps, contiguous in host memory (2*got slices); depth >= 3.
  * A used-up block goes back to the producer one block late: an asynchronous copy out of
  * the MOST RECENT take may still be pending at the next take, all earlier ones must be done. */
 int nh_moves_take(nh_moves* m, int want, const void** host_ptr, int* got);
@@ -911,6 +922,25 @@ int nh_hist_columns(nh_ctx* ctx, const double* x, long long M, int ncol, long lo
                     long long* h1, long long* h2);
 int nh_kde_columns(nh_ctx* ctx, const double* x, long long M, int ncol, long long ld,
                    const double* points, int G, const double* bw, double* out);
+
+/* ---- the sequences of a Gelman-Rubin R-hat over k independent ensembles -----------------------
+ * x is the DEVICE chain [rows][ld] of k ensembles of n walkers (nh_moves_create_ensembles), a row
+ * laid out [walker][parameter] with k*n*ndim <= ld values in use: walkers [r*n, (r+1)*n) are
+ * ensemble r (a history block of the device loop; an uploaded get_chain()).  Rows
+ * [row0, row0 + nrows) are cut into nsplit equal parts of nrows / nsplit rows, a remainder being
+ * dropped from the FRONT.  With q = (part*k + r)*ndim + d, all walkers of the ensemble pooled:
+ *   counts (DEVICE int64 [nsplit*k*ndim]): counts[q] = the number of finite values;
+ *   stats  (DEVICE [2][nsplit*k*ndim]): stats[0][q] = their mean, stats[1][q] = their unbiased
+ *     variance (ddof = 1).
+ * Two passes (the mean, then sum (x - mean)^2), as nh_column_moments: non-finite values are left
+ * out of both; equal values have that value as their mean and variance exactly 0; the mean is NaN
+ * without a finite value, the variance with fewer than two.  Stream-ordered on the context's
+ * stream, no host synchronisation, library scratch, 64-bit row indices.  Deterministic: no
+ * floating-point atomics, every sum in an order fixed by the shapes alone.
+ * NH_EINVAL: a null argument, k or nsplit outside [1, 65535], n < 1, ndim outside [1, 256],
+ *   row0 < 0, nrows < nsplit, k*n*ndim > ld. */
+int nh_group_moments(nh_ctx* ctx, const double* x, long long row0, long long nrows, long long ld,
+                     int k, int n, int ndim, int nsplit, long long* counts, double* stats);
 
 #ifdef __cplusplus
 }

@@ -99,6 +99,7 @@ _SIGS = {
     "nh_scatter_rows": [_dp, _dp, _i, _dp, _i, _dp, _dp, _i, _i, _i],
     "nh_copy": [_dp, _dp, _dp, _ll],
     "nh_moves_create": [C.c_ulonglong, _i, _d, _i, _i, _i, C.POINTER(_dp)],
+    "nh_moves_create_ensembles": [C.POINTER(C.c_ulonglong), _i, _i, _d, _i, _i, _i, C.POINTER(_dp)],
     "nh_moves_take": [_dp, _i, C.POINTER(_dp), C.POINTER(_i)],
     "nh_moves_destroy": [_dp],
     "nh_graph_begin": [_dp],
@@ -165,6 +166,7 @@ _SIGS = {
     "nh_ebl_table": [_dp, _dp, _i, _dp, _i, _dp, _dp, _i, _d, _dp, _dp],
     "nh_ebl_apply": [_dp, _dp, _i, _i, _dp, _i, _dp, _dp, _i, _dp, _i, _i, _dp, _i],
     "nh_column_moments": [_dp, _dp, _ll, _i, _ll, _dp, _dp],
+    "nh_group_moments": [_dp, _dp, _ll, _ll, _ll, _i, _i, _i, _i, _dp, _dp],
     "nh_hist_columns": [_dp, _dp, _ll, _i, _ll, _dp, _i, C.POINTER(_i), _i, _dp, _dp],
     "nh_kde_columns": [_dp, _dp, _ll, _i, _ll, _dp, _i, _dp, _dp],
 }
@@ -258,11 +260,23 @@ class Moves:
     """the stretch-move random stream (nh_moves_*): a C++ worker thread draws ahead.
     ``take(k)`` -> (address, got, S, P, Z, L views for `got` consecutive steps)"""
 
-    def __init__(self, seed, N, a=2.0, ksteps=32, depth=4, pinned=False):
+    def __init__(self, seed, N, a=2.0, ksteps=32, depth=4, pinned=False, ensembles=None):
+        """``ensembles`` = k: ``seed`` is a sequence of k seeds and ``N`` the walkers of EACH of k
+        independent ensembles (nh_moves_create_ensembles); the stream is one of k * N walkers"""
         load()
         h = _dp()
-        _chk(_lib.nh_moves_create(int(seed) & (2 ** 64 - 1), int(N), float(a), int(ksteps),
-                                  int(depth), int(bool(pinned)), C.byref(h)))
+        if ensembles is None:
+            _chk(_lib.nh_moves_create(int(seed) & (2 ** 64 - 1), int(N), float(a), int(ksteps),
+                                      int(depth), int(bool(pinned)), C.byref(h)))
+        else:
+            k = int(ensembles)
+            seeds = [int(v) & (2 ** 64 - 1) for v in seed]
+            if k < 1 or len(seeds) != k:
+                raise ValueError("%d seeds for %d ensembles" % (len(seeds), k))
+            _chk(_lib.nh_moves_create_ensembles((C.c_ulonglong * k)(*seeds), k, int(N), float(a),
+                                                int(ksteps), int(depth), int(bool(pinned)),
+                                                C.byref(h)))
+            N = k * int(N)
         self.h, self.N, self.ns, self.ksteps = h, int(N), int(N) // 2, int(ksteps)
 
     def take(self, want):

@@ -15,6 +15,13 @@
 //   4. for half h, j:                  lnU = log(u)
 // Block layout = what nh_move_propose/accept read: per half-step slice of 3*ns doubles
 //   { z[ns] | lnU[ns] | S[ns] int32 | partner[ns] int32 }.
+//
+// Several independent ensembles in one launch (nh_moves_create_ensembles): k generator states,
+// one per ensemble of n walkers; per ensemble step every ensemble r runs the recipe above on its
+// own state with N = n and writes its n/2 entries at [r n/2, (r+1) n/2) of the four arrays of
+// both slices (ns = k n/2), r n added to S and partner.  A walker's partner is thus always a
+// walker of its own ensemble, and ensemble r's sub-stream is what nh_moves_create(seeds[r], n)
+// produces, apart from that index offset.  nh_moves_create is the case k = 1.
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -22,10 +29,11 @@
 #include "nh_common.h"
 
 struct nh_moves {
-  int N, ns, ksteps, depth;
+  int N, ns, ksteps, depth;  // N = k * n walkers in all, ns = N / 2
+  int k, n;                  // ensembles, walkers of each
   double a;
   bool pinned;
-  uint64_t s[4];
+  std::vector<uint64_t> s;   // k states of 4 words
   std::vector<double*> blocks;   // depth blocks of ksteps*2 slices
   std::vector<int> ready;        // 0 = free, 1 = filled, 2 = consumed but not yet handed back
   int head = 0;                  // block the consumer reads
@@ -64,32 +72,39 @@ static inline uint32_t xo_bounded(uint64_t* s, uint32_t n) {  // Lemire, unbiase
   return (uint32_t)(m >> 32);
 }
 
-static void fill_step(nh_moves* m, double* slice0) {
-  const int N = m->N, ns = m->ns;
+// ensemble r's share of one ensemble step: the recipe on state r with N = n
+static void fill_step_one(nh_moves* m, int r, double* slice0) {
+  const int N = m->n, ns = m->n / 2, j0 = r * ns, i0 = r * m->n;
+  const size_t NS = (size_t)m->ns;  // entries per array of the combined slice
+  uint64_t* st = m->s.data() + 4 * (size_t)r;
   int* p = m->perm.data();
   for (int i = 0; i < N; ++i) p[i] = i;
   for (int i = N - 1; i > 0; --i) {
-    int j = (int)xo_bounded(m->s, (uint32_t)(i + 1));
+    int j = (int)xo_bounded(st, (uint32_t)(i + 1));
     int t = p[i]; p[i] = p[j]; p[j] = t;
   }
-  double* sl[2] = {slice0, slice0 + 3 * (size_t)ns};
+  double* sl[2] = {slice0, slice0 + 3 * NS};
   for (int h = 0; h < 2; ++h) {
-    int* iv = reinterpret_cast<int*>(sl[h] + 2 * (size_t)ns);
-    for (int j = 0; j < ns; ++j) iv[j] = p[h * ns + j];
+    int* iv = reinterpret_cast<int*>(sl[h] + 2 * NS);
+    for (int j = 0; j < ns; ++j) iv[j0 + j] = i0 + p[h * ns + j];
   }
   for (int h = 0; h < 2; ++h)
     for (int j = 0; j < ns; ++j) {
-      double u = xo_uniform(m->s);
+      double u = xo_uniform(st);
       double t = (m->a - 1.0) * u + 1.0;
-      sl[h][j] = t * t / m->a;
+      sl[h][j0 + j] = t * t / m->a;
     }
   for (int h = 0; h < 2; ++h) {
-    int* iv = reinterpret_cast<int*>(sl[h] + 2 * (size_t)ns);
+    int* iv = reinterpret_cast<int*>(sl[h] + 2 * NS);
     const int* other = p + (1 - h) * ns;
-    for (int j = 0; j < ns; ++j) iv[ns + j] = other[(int)(xo_uniform(m->s) * ns)];
+    for (int j = 0; j < ns; ++j) iv[NS + j0 + j] = i0 + other[(int)(xo_uniform(st) * ns)];
   }
   for (int h = 0; h < 2; ++h)
-    for (int j = 0; j < ns; ++j) sl[h][ns + j] = std::log(xo_uniform(m->s));
+    for (int j = 0; j < ns; ++j) sl[h][NS + j0 + j] = std::log(xo_uniform(st));
+}
+
+static void fill_step(nh_moves* m, double* slice0) {
+  for (int r = 0; r < m->k; ++r) fill_step_one(m, r, slice0);
 }
 
 static void producer(nh_moves* m) {
@@ -112,32 +127,37 @@ static void producer(nh_moves* m) {
   }
 }
 
-extern "C" int nh_moves_create(unsigned long long seed, int N, double a, int ksteps, int depth,
-                               int pinned, nh_moves** out) {
-  NH_REQUIRE(out && N >= 2 && N % 2 == 0 && a > 1.0 && ksteps >= 1 && depth >= 3, "bad argument");
+static int moves_create(const unsigned long long* seeds, int k, int n, double a, int ksteps,
+                        int depth, int pinned, nh_moves** out) {
   nh_moves* m = new nh_moves();
-  m->N = N; m->ns = N / 2; m->ksteps = ksteps; m->depth = depth; m->a = a; m->pinned = pinned != 0;
-  uint64_t z = seed;  // splitmix64 seeding
-  for (int i = 0; i < 4; ++i) {
-    z += 0x9e3779b97f4a7c15ull;
-    uint64_t x = z;
-    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
-    x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
-    m->s[i] = x ^ (x >> 31);
+  m->k = k; m->n = n; m->N = k * n; m->ns = m->N / 2;
+  m->ksteps = ksteps; m->depth = depth; m->a = a; m->pinned = pinned != 0;
+  m->s.resize(4 * (size_t)k);
+  for (int r = 0; r < k; ++r) {
+    uint64_t z = seeds[r];  // splitmix64 seeding
+    for (int i = 0; i < 4; ++i) {
+      z += 0x9e3779b97f4a7c15ull;
+      uint64_t x = z;
+      x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
+      x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
+      m->s[4 * (size_t)r + i] = x ^ (x >> 31);
+    }
   }
-  m->perm.resize(N);
+  m->perm.resize(n);
   const size_t bytes = (size_t)ksteps * 2 * 3 * m->ns * sizeof(double);
   for (int b = 0; b < depth; ++b) {
     void* p = nullptr;
-    if (m->pinned) {
-      hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
-      if (e != hipSuccess) {
-        delete m;
-        return nh_set_error(NH_ENOMEM, "hipHostMalloc(%zu): %s", bytes, hipGetErrorString(e));
+    hipError_t e = hipSuccess;
+    if (m->pinned) e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+    else p = malloc(bytes);
+    if (e != hipSuccess || !p) {  // (no worker yet: free what the earlier rounds got)
+      for (double* q : m->blocks) {
+        if (m->pinned) (void)hipHostFree(q); else free(q);
       }
-    } else {
-      p = malloc(bytes);
-      if (!p) { delete m; return nh_set_error(NH_ENOMEM, "malloc(%zu) failed", bytes); }
+      const bool pin = m->pinned;
+      delete m;
+      if (pin) return nh_set_error(NH_ENOMEM, "hipHostMalloc(%zu): %s", bytes, hipGetErrorString(e));
+      return nh_set_error(NH_ENOMEM, "malloc(%zu) failed", bytes);
     }
     m->blocks.push_back(static_cast<double*>(p));
     m->ready.push_back(0);
@@ -145,6 +165,22 @@ extern "C" int nh_moves_create(unsigned long long seed, int N, double a, int kst
   m->worker = std::thread(producer, m);
   *out = m;
   return NH_OK;
+}
+
+extern "C" int nh_moves_create(unsigned long long seed, int N, double a, int ksteps, int depth,
+                               int pinned, nh_moves** out) {
+  NH_REQUIRE(out && N >= 2 && N % 2 == 0 && a > 1.0 && ksteps >= 1 && depth >= 3, "bad argument");
+  return moves_create(&seed, 1, N, a, ksteps, depth, pinned, out);
+}
+
+extern "C" int nh_moves_create_ensembles(const unsigned long long* seeds, int k, int n, double a,
+                                         int ksteps, int depth, int pinned, nh_moves** out) {
+  NH_REQUIRE(out && seeds, "null argument");
+  NH_REQUIRE(k >= 1, "k < 1");
+  NH_REQUIRE(n >= 2 && n % 2 == 0, "n must be even and at least 2");
+  NH_REQUIRE((long long)k * n <= 0x7fffffffll, "k * n does not fit an int");
+  NH_REQUIRE(a > 1.0 && ksteps >= 1 && depth >= 3, "bad argument");
+  return moves_create(seeds, k, n, a, ksteps, depth, pinned, out);
 }
 
 // up to `want` consecutive steps of the stream, contiguous in (pinned) host memory.

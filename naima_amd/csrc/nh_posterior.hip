@@ -21,6 +21,14 @@
 //                      (point tile, row chunk, column), stages the chunk's values in LDS (a
 //                      broadcast read per row) and writes one partial per point; a second launch
 //                      sums the partials in chunk order and normalises.
+//   nh_group_moments   the chain [rows][walker][parameter] of k ensembles of n walkers, its rows cut
+//                      into nsplit parts: per (part, ensemble, parameter) the count, mean and
+//                      unbiased variance of the finite values over all the ensemble's walkers (the
+//                      sequences of a Gelman-Rubin R-hat).  Two passes as above; a workgroup takes
+//                      (row chunk, ensemble, part) and walks the ensemble's n*ndim contiguous
+//                      values of its rows with a stride that is a multiple of ndim, so a thread
+//                      keeps one parameter; the threads of a parameter are summed in thread order,
+//                      the chunks in chunk order.
 //
 // No floating-point atomics: every floating-point sum has an order fixed by the shapes alone, so
 // repeated calls give bit-identical results.  Row indices are 64-bit.  Every launch is on the
@@ -166,6 +174,130 @@ __global__ void k_po_var(const double* __restrict__ pq, long long nch, int ncol,
   double var = __longlong_as_double(0x7ff8000000000000ll);
   if (n > 1) var = stats[c] == stats[ncol + c] ? 0.0 : q / (double)(n - 1);
   stats[3 * ncol + c] = var;
+}
+
+// ---------------------------------------------------------------- group moments
+// rows [first + p*L, first + (p+1)*L) are part p; a part has nch chunks of `rows` rows
+struct po_groups {
+  long long first, L, rows, nch, ld;
+  int k, n, ndim;
+};
+
+// the values of (part, ensemble, chunk) that thread `tid` of T = (256/ndim)*ndim visits: the flat
+// index tid + j*T over [row][n*ndim]; n*ndim and T are multiples of ndim, so the parameter of
+// every one of them is tid % ndim.  f(v) per value.
+template <typename F>
+__device__ __forceinline__ void po_group_walk(const double* __restrict__ x, const po_groups& g,
+                                              int tid, int T, F f) {
+  const long long E = (long long)g.n * g.ndim;
+  const long long t0 = g.first + blockIdx.z * g.L + blockIdx.x * g.rows;
+  const long long t1 = min(g.first + (blockIdx.z + 1) * g.L, t0 + g.rows);
+  const double* base = x + (long long)blockIdx.y * E;
+  const long long qT = T / E, rT = T % E;
+  long long row = t0 + tid / E, e = tid % E;
+  while (row < t1) {
+    f(base[row * g.ld + e]);
+    e += rT;
+    row += qT;
+    if (e >= E) { e -= E; ++row; }
+  }
+}
+
+// per (part p, ensemble r, chunk c, parameter d), i = ((p*k + r)*nch + c)*ndim + d:
+// pd[3 i + 0|1|2] = sum, min, max of the finite values, pc[i] their number
+__global__ __launch_bounds__(PO_THREADS) void k_po_gsum(const double* __restrict__ x, po_groups g,
+                                                        double* __restrict__ pd,
+                                                        long long* __restrict__ pc) {
+  __shared__ double rs[PO_THREADS], rlo[PO_THREADS], rhi[PO_THREADS];
+  __shared__ long long rn[PO_THREADS];
+  const int tid = threadIdx.x, T = (PO_THREADS / g.ndim) * g.ndim;
+  double s = 0.0, lo = INFINITY, hi = -INFINITY;
+  long long n = 0;
+  if (tid < T)
+    po_group_walk(x, g, tid, T, [&](double v) {
+      if (po_finite(v)) {
+        s += v;
+        lo = fmin(lo, v);
+        hi = fmax(hi, v);
+        ++n;
+      }
+    });
+  rs[tid] = s; rlo[tid] = lo; rhi[tid] = hi; rn[tid] = n;
+  __syncthreads();
+  if (tid < g.ndim) {
+    for (int j = tid + g.ndim; j < T; j += g.ndim) {
+      s += rs[j];
+      lo = fmin(lo, rlo[j]);
+      hi = fmax(hi, rhi[j]);
+      n += rn[j];
+    }
+    long long i = (((long long)blockIdx.z * g.k + blockIdx.y) * g.nch + blockIdx.x) * g.ndim + tid;
+    pd[3 * i] = s; pd[3 * i + 1] = lo; pd[3 * i + 2] = hi;
+    pc[i] = n;
+  }
+}
+
+// per group q = (p*k + r)*ndim + d of nq: counts[q] = n, stats[q] = mean (NaN without a finite
+// value; the value itself when all are equal), lohi[2 q + 0|1] = min, max
+__global__ void k_po_gmean(const double* __restrict__ pd, const long long* __restrict__ pc,
+                           long long nch, int ndim, long long nq, long long* __restrict__ counts,
+                           double* __restrict__ stats, double* __restrict__ lohi) {
+  long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nq) return;
+  const long long i0 = (q / ndim) * nch * ndim + q % ndim;
+  double s = 0.0, lo = INFINITY, hi = -INFINITY;
+  long long n = 0;
+  for (long long c = 0; c < nch; ++c) {
+    long long i = i0 + c * ndim;
+    s += pd[3 * i];
+    lo = fmin(lo, pd[3 * i + 1]);
+    hi = fmax(hi, pd[3 * i + 2]);
+    n += pc[i];
+  }
+  counts[q] = n;
+  stats[q] = n ? (lo == hi ? lo : s / (double)n) : __longlong_as_double(0x7ff8000000000000ll);
+  lohi[2 * q] = lo;
+  lohi[2 * q + 1] = hi;
+}
+
+// pq[i] = the chunk's sum of (x - mean)^2 over the finite values (i as in k_po_gsum)
+__global__ __launch_bounds__(PO_THREADS) void k_po_gsq(const double* __restrict__ x, po_groups g,
+                                                       const double* __restrict__ stats,
+                                                       double* __restrict__ pq) {
+  __shared__ double rq[PO_THREADS];
+  const int tid = threadIdx.x, T = (PO_THREADS / g.ndim) * g.ndim;
+  const long long grp = (long long)blockIdx.z * g.k + blockIdx.y;
+  double q = 0.0;
+  if (tid < T) {
+    const double mean = stats[grp * g.ndim + tid % g.ndim];
+    po_group_walk(x, g, tid, T, [&](double v) {
+      if (po_finite(v)) {
+        double d = v - mean;
+        q = fma(d, d, q);
+      }
+    });
+  }
+  rq[tid] = q;
+  __syncthreads();
+  if (tid < g.ndim) {
+    for (int j = tid + g.ndim; j < T; j += g.ndim) q += rq[j];
+    pq[(grp * g.nch + blockIdx.x) * g.ndim + tid] = q;
+  }
+}
+
+// stats[nq + q] = sum / (n - 1): exactly 0 for equal values, NaN for fewer than two
+__global__ void k_po_gvar(const double* __restrict__ pq, long long nch, int ndim, long long nq,
+                          const long long* __restrict__ counts,
+                          const double* __restrict__ lohi, double* __restrict__ stats) {
+  long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nq) return;
+  const long long i0 = (q / ndim) * nch * ndim + q % ndim;
+  double sq = 0.0;
+  for (long long c = 0; c < nch; ++c) sq += pq[i0 + c * ndim];
+  long long n = counts[q];
+  double var = __longlong_as_double(0x7ff8000000000000ll);
+  if (n > 1) var = lohi[2 * q] == lohi[2 * q + 1] ? 0.0 : sq / (double)(n - 1);
+  stats[nq + q] = var;
 }
 
 // ---------------------------------------------------------------- histograms
@@ -403,6 +535,54 @@ extern "C" int nh_kde_columns(nh_ctx* ctx, const double* x, long long M, int nco
   NH_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_po_kde_reduce, dim3((unsigned)cdiv(G, PO_THREADS), (unsigned)ncol),
                      dim3(PO_THREADS), 0, s, part, pn, nch, G, bw, out);
+  NH_CHECK_HIP(hipGetLastError());
+  return NH_OK;
+}
+
+extern "C" int nh_group_moments(nh_ctx* ctx, const double* x, long long row0, long long nrows,
+                                long long ld, int k, int n, int ndim, int nsplit,
+                                long long* counts, double* stats) {
+  NH_REQUIRE(ctx && x && counts && stats, "null argument");
+  NH_REQUIRE(k >= 1 && k <= 65535, "k outside [1, 65535]");
+  NH_REQUIRE(n >= 1, "n must be positive");
+  NH_REQUIRE(ndim >= 1 && ndim <= PO_THREADS, "ndim outside [1, 256]");
+  NH_REQUIRE(nsplit >= 1 && nsplit <= 65535, "nsplit outside [1, 65535]");
+  NH_REQUIRE(row0 >= 0, "row0 is negative");
+  NH_REQUIRE(nrows >= nsplit, "fewer rows than parts");
+  const long long E = (long long)n * ndim;
+  NH_REQUIRE(E <= (1ll << 40) / k && ld >= (long long)k * E, "k * n * ndim > ld");
+  po_groups g;
+  g.L = nrows / nsplit;
+  g.first = row0 + (nrows - g.L * nsplit);  // (the remainder is dropped from the front)
+  g.ld = ld; g.k = k; g.n = n; g.ndim = ndim;
+  // chunks of a part: a workgroup reads 16 values per thread at least, the launch aims at
+  // PO_TARGET_WG workgroups -- a function of the shapes only
+  long long want = std::max<long long>(1, PO_TARGET_WG / ((long long)k * nsplit));
+  long long nch = std::min(
+      want, std::max<long long>(1, (long long)((double)g.L * (double)E / (16.0 * PO_THREADS))));
+  g.rows = cdiv(g.L, nch);
+  g.nch = cdiv(g.L, g.rows);
+  const long long nq = (long long)nsplit * k * ndim, ni = nq * g.nch;
+  // scratch: pd [ni][3] | pq [ni] | lohi [nq][2] | pc [ni]
+  void* base = nullptr;
+  int rc = nh_scratch(ctx, ((size_t)ni * 5 + (size_t)nq * 2) * 8, &base);
+  if (rc) return rc;
+  double* pd = (double*)base;
+  double* pq = pd + (size_t)ni * 3;
+  double* lohi = pq + (size_t)ni;
+  long long* pc = (long long*)(lohi + (size_t)nq * 2);
+  hipStream_t s = ctx->stream;
+  dim3 grid((unsigned)g.nch, (unsigned)k, (unsigned)nsplit);
+  unsigned qb = (unsigned)cdiv(nq, PO_THREADS);
+  hipLaunchKernelGGL(k_po_gsum, grid, dim3(PO_THREADS), 0, s, x, g, pd, pc);
+  NH_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_po_gmean, dim3(qb), dim3(PO_THREADS), 0, s, pd, pc, g.nch, ndim, nq, counts,
+                     stats, lohi);
+  NH_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_po_gsq, grid, dim3(PO_THREADS), 0, s, x, g, stats, pq);
+  NH_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_po_gvar, dim3(qb), dim3(PO_THREADS), 0, s, pq, g.nch, ndim, nq, counts, lohi,
+                     stats);
   NH_CHECK_HIP(hipGetLastError());
   return NH_OK;
 }

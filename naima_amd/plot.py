@@ -368,7 +368,7 @@ def _posterior_hist(ax, dist, label, title):
     return tuple(q)
 
 
-def _chain_text(sampler, label, dist, shape, last_step, tau=None):
+def _chain_text(sampler, label, dist, shape, last_step, tau=None, rhat=None):
     """the summary printed beside a chain plot: run size, the parameter's integrated
     autocorrelation time ``tau`` (left out when None: naima leaves it out for a chain too short to
     estimate it), acceptance, and the posterior's median with 16/84 % errors (de-logged too for a
@@ -377,6 +377,8 @@ def _chain_text(sampler, label, dist, shape, last_step, tau=None):
     lines = ["Walkers: %d" % shape[0], "Steps in chain: %d" % shape[1]]
     if tau is not None:
         lines.append("Autocorrelation time: %.1f" % tau)
+    if rhat is not None:  # (a run of several independent ensembles)
+        lines.append("Gelman-Rubin R-hat: %.3f" % rhat)
     lines += ["Mean acceptance fraction: %.3f" % np.mean(sampler.acceptance_fraction),
              "Distribution properties for the %s:" % ("last ensemble" if last_step
                                                       else "whole chain"),
@@ -392,8 +394,21 @@ def _chain_text(sampler, label, dist, shape, last_step, tau=None):
     return "\n".join(lines)
 
 
-def _plot_chain_func(sampler, p, last_step=False):
-    """one parameter: walker traces (top left), posterior (right), summary (bottom left)"""
+def _chain_rhat(sampler):
+    """Gelman-Rubin R-hat of every parameter of a run of several independent ensembles (a sampler,
+    or a ``read_run`` result through ``run_info["ensembles"]``), else None; also None for a chain
+    of fewer than four rows (split R-hat: two per half)"""
+    k = int(getattr(sampler, "run_info", {}).get("ensembles", getattr(sampler, "ensembles", 1)))
+    chain = np.asarray(sampler.get_chain())
+    if k < 2 or chain.shape[0] < 4:
+        return None
+    from .posterior import rhat
+    return rhat(chain, k)
+
+
+def _plot_chain_func(sampler, p, last_step=False, rhat=None):
+    """one parameter: walker traces (top left), posterior (right), summary (bottom left);
+    ``rhat``: what ``_chain_rhat`` gave for the sampler"""
     import matplotlib.pyplot as plt
     from .autocorr import AutocorrError, integrated_time
     chain = np.asarray(sampler.get_chain())
@@ -418,7 +433,8 @@ def _plot_chain_func(sampler, p, last_step=False):
                    color=color_cycle[0] if hi else "0.1", rasterized=not hi)
     ax_tr.set(xlabel="step number", ylabel=label, title="Walker traces")
     _posterior_hist(ax_post, dist, label, "posterior distribution")
-    fig.text(0.05, 0.45, _chain_text(sampler, label, dist, traces.shape, last_step, tau),
+    fig.text(0.05, 0.45, _chain_text(sampler, label, dist, traces.shape, last_step, tau,
+                                     None if rhat is None else rhat[p]),
              ha="left", va="top")
     return fig
 
@@ -426,11 +442,12 @@ def _plot_chain_func(sampler, p, last_step=False):
 def plot_chain(sampler, p=None, **kwargs):
     """Diagnostic figure of parameter ``p``'s walker traces and posterior (all parameters, one
     figure each, when ``p`` is None: returns None then).  plot.py:26-52."""
+    rhat = _chain_rhat(sampler)  # (once for all the figures)
     if p is None:
         for pp in range(np.asarray(sampler.get_chain()).shape[-1]):
-            _plot_chain_func(sampler, pp, **kwargs)
+            _plot_chain_func(sampler, pp, rhat=rhat, **kwargs)
         return None
-    return _plot_chain_func(sampler, p, **kwargs)
+    return _plot_chain_func(sampler, p, rhat=rhat, **kwargs)
 
 
 def _plot_MLmodel(ax, sampler, modelidx, e_range, e_npoints, e_unit, sed):

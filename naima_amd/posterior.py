@@ -11,6 +11,11 @@ counts are host arithmetic.
 Every function takes a host array ``(M,)`` or ``(M, ncol)``, which is uploaded once per call, or a
 device matrix: a ``plot._Samples``, or ``(DeviceArray, M, ncol, ld)``.
 
+``group_moments`` and ``rhat`` read a chain of several independent ensembles
+(``EnsembleSampler(..., ensembles=k)``): per (part of the rows, ensemble, parameter) the device
+pools the ensemble's walkers into one sequence and returns its count, mean and variance
+(``nh_group_moments``); the Gelman-Rubin formula over those ``m * ndim`` moments is host arithmetic.
+
 Importing this module creates no GPU context; argument errors come before any device work.
 matplotlib is imported by ``corner`` only.
 """
@@ -22,7 +27,7 @@ from ._lib import (NH_HIST_MAX_BINS_1D, NH_HIST_MAX_BINS_2D, NH_HIST_MAX_COLS,
                    NH_HIST_MAX_PAIRS)
 
 __all__ = ["column_stats", "histogram", "histogram_pairs", "gaussian_kde", "contour_thresholds",
-           "corner", "DEFAULT_LEVELS"]
+           "corner", "DEFAULT_LEVELS", "group_moments", "rhat", "rhat_from_moments"]
 
 # the mass of a 2-D Gaussian inside 0.5, 1, 1.5 and 2 sigma (corner's default contours)
 DEFAULT_LEVELS = tuple(1.0 - np.exp(-0.5 * np.array([0.5, 1.0, 1.5, 2.0]) ** 2))
@@ -234,6 +239,103 @@ def gaussian_kde(x, points, bw_method=None):
     ctx.call("nh_kde_columns", s.ptr, s.M, s.ncol, s.ld, ctx.array(np.ascontiguousarray(p)),
              p.shape[1], ctx.array(h), out)
     return out.get()
+
+
+# ---------------------------------------------------------------------------------------
+# Gelman-Rubin R-hat over independent ensembles
+# ---------------------------------------------------------------------------------------
+def _chain_shape(x, ensembles, discard, nsplit):
+    """(rows, nwalkers, ndim, k, n) of a host chain (rows, nwalkers, ndim) or of a device block
+    ``(DeviceArray [rows at least][nwalkers * ndim], rows, nwalkers, ndim)``, checked without a
+    device"""
+    if isinstance(ensembles, bool) or not isinstance(ensembles, (int, np.integer)):
+        raise ValueError("ensembles must be an integer")
+    k = int(ensembles)
+    if k < 2:
+        raise ValueError("R-hat compares independent ensembles: ensembles must be at least 2")
+    if isinstance(x, tuple):
+        if len(x) != 4 or not hasattr(x[0], "ptr"):
+            raise ValueError("a device chain is (DeviceArray, rows, nwalkers, ndim)")
+        rows, nw, ndim = (int(v) for v in x[1:])
+        if rows < 0 or nw < 1 or ndim < 1 or rows * nw * ndim * 8 > x[0].nbytes:
+            raise ValueError("a device chain of %d x %d x %d does not fit its buffer"
+                             % (rows, nw, ndim))
+    else:
+        shape = np.shape(x)
+        if len(shape) != 3:
+            raise ValueError("a chain must be (rows, nwalkers, ndim)")
+        rows, nw, ndim = shape
+    if nw % k:
+        raise ValueError("%d walkers do not split into %d ensembles" % (nw, k))
+    if ndim > 256:
+        raise ValueError("more than 256 parameters")
+    discard = int(discard)
+    if discard < 0:
+        raise ValueError("discard must not be negative")
+    if rows - discard < 2 * nsplit:
+        raise ValueError("%d rows behind discard = %d: every sequence needs two at least"
+                         % (max(0, rows - discard), discard))
+    return rows, nw, ndim, k, nw // k
+
+
+def group_moments(x, ensembles, discard=0, nsplit=1):
+    """The chain ``x`` -- a host array (rows, nwalkers, ndim) as ``get_chain()`` returns it, which
+    is uploaded, or a device block ``(DeviceArray, rows, nwalkers, ndim)`` laid out
+    [rows][nwalkers * ndim] -- holds ``ensembles`` = k ensembles, walkers [r n, (r+1) n) being
+    ensemble r.  The rows behind ``discard`` are cut into ``nsplit`` equal parts (a remainder is
+    dropped from the front); per (part, ensemble, parameter), all walkers of the ensemble pooled:
+    ``n`` finite values (int64), their ``mean`` and ``var`` (unbiased), arrays [nsplit][k][ndim],
+    and ``draws``, the number of values of each such sequence."""
+    from . import _lib
+    nsplit = int(nsplit)
+    if nsplit < 1:
+        raise ValueError("nsplit must be at least 1")
+    rows, nw, ndim, k, n = _chain_shape(x, ensembles, discard, nsplit)
+    if isinstance(x, tuple):
+        buf = x[0]
+        ctx = buf.ctx
+    else:
+        ctx = _lib.get_context()
+        buf = ctx.array(np.ascontiguousarray(x, dtype=np.float64).reshape(rows, nw * ndim))
+    nq = nsplit * k * ndim
+    counts, stats = ctx.empty((nq,), np.int64), ctx.empty((2, nq))
+    ctx.call("nh_group_moments", buf, int(discard), rows - int(discard), nw * ndim, k, n, ndim,
+             nsplit, counts, stats)
+    c, v = counts.get(), stats.get()
+    shape = (nsplit, k, ndim)
+    return dict(n=c.reshape(shape), mean=v[0].reshape(shape), var=v[1].reshape(shape),
+                draws=(rows - int(discard)) // nsplit * n)
+
+
+def rhat_from_moments(count, mean, var, draws):
+    """The BDA3 formula over m sequences of ``draws`` = L values each, given per sequence and
+    parameter ([m][ndim]) the number of finite values, their mean and unbiased variance:
+    W = the mean of the variances, B/L = the variance (ddof=1) of the means,
+    R-hat = sqrt(((L-1)/L W + B/L) / W).  NaN for a parameter of which any sequence is constant
+    (variance 0) or holds a non-finite value (fewer than L finite ones)."""
+    count, mean, var = np.asarray(count), np.asarray(mean, float), np.asarray(var, float)
+    L = float(draws)
+    W = var.mean(axis=0)
+    BL = mean.var(axis=0, ddof=1)
+    bad = np.any(count != draws, axis=0) | np.any(~(var > 0), axis=0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        r = np.sqrt(((L - 1.0) / L * W + BL) / W)
+    r[bad] = np.nan
+    return r
+
+
+def rhat(x, ensembles, discard=0, split=True):
+    """Gelman-Rubin R-hat per parameter of a chain of ``ensembles`` >= 2 independent ensembles
+    (``x`` as ``group_moments`` takes it).  The walkers of ONE ensemble are not independent chains
+    -- every proposal is built from another walker of it -- so each ensemble is pooled into one
+    sequence; ``split=True`` cuts each into its first and second half (split-R-hat, which also
+    sees a drift within the run), giving m = 2 k sequences, else m = k.  Every sequence has
+    L = (rows per part) x (walkers of an ensemble) draws; the formula is ``rhat_from_moments``'s.
+    Only the m x ndim moments come to the host."""
+    gm = group_moments(x, ensembles, discard, 2 if split else 1)
+    m = gm["n"].shape[0] * gm["n"].shape[1]
+    return rhat_from_moments(gm["n"].reshape(m, -1), gm["mean"].reshape(m, -1),
+                             gm["var"].reshape(m, -1), gm["draws"])
 
 
 def _quantiles(s, q):

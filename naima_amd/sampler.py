@@ -54,19 +54,42 @@ class EnsembleSampler:
     With ``naima_style=True`` (what ``get_sampler`` uses) the function is naima's
     ``lnprob(pars, data, model, prior)`` and is called with ``coords.T`` so that
     ``pars[i]`` is a vector over walkers.
+
+    ``ensembles`` = k > 1: the ``nwalkers`` = k n walkers are k INDEPENDENT ensembles of n, walkers
+    [r n, (r+1) n) being ensemble r, that share every launch: each walker's partner is drawn from
+    its own ensemble (``_lib.Moves(..., ensembles=k)``), nothing else differs.  ``seed`` is then an
+    int s, for the seeds (s, s+1, ..., s+k-1), or a sequence of k ints; ensemble r makes exactly
+    the moves of a single-ensemble sampler of n walkers with seed ``seeds[r]``.  ``get_rhat``
+    compares the ensembles (Gelman-Rubin).  One rank only.
     """
 
     def __init__(self, nwalkers, ndim, log_prob_fn, args=(), a=2.0, seed=None, comm=None,
                  naima_style=False, store_blobs=True, device=False, use_graph=True,
-                 nan_policy="raise"):
-        if nwalkers % 2 or nwalkers < 2 * ndim:
-            raise ValueError("need an even number of walkers, at least twice the dimension")
+                 nan_policy="raise", ensembles=1):
+        if isinstance(ensembles, bool) or not isinstance(ensembles, (int, np.integer)) \
+                or ensembles < 1:
+            raise ValueError("ensembles must be a positive integer")
+        k = int(ensembles)
+        if nwalkers % k or (nwalkers // k) % 2 or nwalkers // k < 2 * ndim:
+            raise ValueError("need an even number of walkers%s, at least twice the dimension"
+                             % (" in each of the %d ensembles" % k if k > 1 else ""))
         self.nwalkers, self.ndim, self.a = int(nwalkers), int(ndim), float(a)
+        self.ensembles, self.nwalkers_each = k, int(nwalkers) // k
         self.log_prob_fn, self.args = log_prob_fn, tuple(args)
         self.comm = comm if comm is not None else LocalComm()
         # the streams are replicated on every rank: proposals/accepts are identical.
         # _rng: numpy, for the initial ball; _moves: the C++ stretch-move stream
-        self.seed = int(seed if seed is not None else 12345)
+        if seed is None or np.ndim(seed) == 0:
+            s0 = int(seed if seed is not None else 12345)
+            self.seeds = tuple(s0 + r for r in range(k))
+        else:
+            self.seeds = tuple(int(v) for v in seed)
+            if len(self.seeds) != k:
+                raise ValueError("%d seeds for %d ensembles" % (len(self.seeds), k))
+        if k > 1 and (self.comm.size > 1 or
+                      os.environ.get("NAIMA_AMD_FORCE_SHARDED", "0") == "1"):
+            raise NotImplementedError("several ensembles with walkers sharded over several ranks")
+        self.seed = self.seeds[0]
         self._rng = np.random.default_rng(self.seed)
         self._moves = None
         self.naima_style = naima_style
@@ -102,9 +125,33 @@ class EnsembleSampler:
         """the stretch-move random stream (one per sampler, created on first use)"""
         if self._moves is None:
             from ._lib import Moves
-            self._moves = Moves(self.seed, self.nwalkers, self.a, ksteps=32, depth=4,
-                                pinned=pinned)
+            if self.ensembles == 1:
+                self._moves = Moves(self.seed, self.nwalkers, self.a, ksteps=32, depth=4,
+                                    pinned=pinned)
+            else:
+                self._moves = Moves(self.seeds, self.nwalkers_each, self.a, ksteps=32, depth=4,
+                                    pinned=pinned, ensembles=self.ensembles)
         return self._moves
+
+    @property
+    def ensemble_slices(self):
+        """the walkers of each ensemble: ``[slice(r n, (r+1) n) for r in range(ensembles)]``"""
+        n = self.nwalkers_each
+        return [slice(r * n, (r + 1) * n) for r in range(self.ensembles)]
+
+    def split_ensembles(self, x, axis=None):
+        """``x`` with its walker axis (the first of length ``nwalkers``, or ``axis``) reshaped
+        into (ensembles, walkers of each)"""
+        x = np.asarray(x)
+        if axis is None:
+            hits = [i for i, m in enumerate(x.shape) if m == self.nwalkers]
+            if not hits:
+                raise ValueError("no axis of length nwalkers = %d" % self.nwalkers)
+            axis = hits[0]
+        axis = axis % x.ndim
+        if x.shape[axis] != self.nwalkers:
+            raise ValueError("axis %d is not of length nwalkers = %d" % (axis, self.nwalkers))
+        return x.reshape(x.shape[:axis] + (self.ensembles, self.nwalkers_each) + x.shape[axis + 1:])
 
     # ------------------------------------------------------------------ store
     def reset(self):
@@ -174,6 +221,16 @@ class EnsembleSampler:
         from .autocorr import integrated_time
         x = self.get_chain(discard=discard, thin=thin)
         return thin * integrated_time(x, **kwargs)
+
+    def get_rhat(self, discard=0, split=True):
+        """Gelman-Rubin R-hat of each parameter across the independent ensembles
+        (``posterior.rhat`` of ``get_chain(discard=discard)``, the moments computed on the GPU);
+        needs ``ensembles`` >= 2"""
+        from .posterior import rhat
+        if self.ensembles < 2:
+            raise ValueError("R-hat compares independent ensembles: make the sampler with "
+                             "ensembles >= 2")
+        return rhat(self.get_chain(discard=discard), self.ensembles, split=split)
 
     # legacy emcee-2 names that naima's analysis code touches
     @property
@@ -378,7 +435,7 @@ class EnsembleSampler:
 
 
     def run_until_converged(self, initial_state, max_steps, check_every=100, tol=50, rtol=0.01,
-                            c=5, discard=0, thin_by=1, max_lag=1024):
+                            c=5, discard=0, thin_by=1, max_lag=1024, rhat=None):
         """Run until the integrated autocorrelation time has converged (the loop of emcee's
         tutorial "Autocorrelation analysis & convergence"), ``max_steps`` stored rows at the most.
 
@@ -390,6 +447,12 @@ class EnsembleSampler:
         ``run_mcmc``'s.  Returns the last state; ``self.convergence`` says how it went:
         ``converged``, ``rows`` (stored by this call), ``tau``, ``history`` (``(rows, tau)`` of every
         check), ``where``, ``max_lag`` and ``rebuilds``.
+
+        ``rhat`` = a number such as 1.01 (a sampler of ``ensembles`` >= 2): a check also requires
+        ``all(R-hat < rhat)``, the split Gelman-Rubin statistic across the ensembles over the same
+        rows (``posterior.rhat``) -- what tau alone cannot see, an ensemble that has settled
+        somewhere else.  ``convergence["rhat"]`` is then the last check's R-hat and the history
+        entries are ``(rows, tau, rhat)``.  tau is estimated over all walkers as before.
 
         On the device loop (``where == "device"``) the chain stays in HBM: the call allocates ONE
         history block of ``max_steps`` rows -- the memory of ``run_mcmc(max_steps)`` -- that its
@@ -412,21 +475,39 @@ class EnsembleSampler:
         if self.comm.size > 1 or (self.device and
                                   os.environ.get("NAIMA_AMD_FORCE_SHARDED", "0") == "1"):
             raise NotImplementedError("run_until_converged with walkers sharded over several ranks")
+        if rhat is not None:
+            if self.ensembles < 2:
+                raise ValueError("rhat needs a sampler of ensembles >= 2")
+            rhat = float(rhat)
+            if not rhat > 1.0:
+                raise ValueError("rhat must be larger than 1")
         info = dict(converged=False, rows=0, tau=np.full(self.ndim, np.nan), history=[],
                     where="host", max_lag=max_lag, rebuilds=0)
+        if rhat is not None:
+            info["rhat"] = np.full(self.ndim, np.nan)
         self.convergence = info
         old, warned = [np.inf], []
+        from .posterior import rhat as _rhat
 
-        def check(rows, tau):
+        def gelman_rubin(x, rows):
+            """R-hat of the rows behind discard; NaN while each half has fewer than two"""
+            if rows - discard < 4:
+                return np.full(self.ndim, np.nan)
+            return _rhat(x, self.ensembles, discard=discard)
+
+        def check(rows, tau, rh=None):
             """the books of one check -> stop?"""
             tau = np.asarray(tau, dtype=float)
-            info["history"].append((rows, tau))
+            info["history"].append((rows, tau) if rhat is None else (rows, tau, rh))
             info["rows"], info["tau"] = rows, tau
+            if rhat is not None:
+                info["rhat"] = rh
             if np.any(np.isnan(tau)) and not warned:
                 warned.append(True)
                 warnings.warn("the autocorrelation time of a parameter is NaN (a constant walker "
                               "or a non-finite value): the run cannot converge")
-            info["converged"] = autocorr.converged(tau, old[0], rows - discard, tol, rtol)
+            info["converged"] = autocorr.converged(tau, old[0], rows - discard, tol, rtol) and \
+                (rhat is None or bool(np.all(rh < rhat)))  # (a NaN R-hat never passes)
             old[0] = tau
             return info["converged"]
 
@@ -445,7 +526,10 @@ class EnsembleSampler:
                 ra.update(buf, rows, discard)
                 tau = ra.tau()[0]
                 info["max_lag"], info["rebuilds"] = ra.max_lag, ra.rebuilds
-                return check(rows, tau)
+                if rhat is None:
+                    return check(rows, tau)
+                # from the block where it lies: only the moments come to the host
+                return check(rows, tau, gelman_rubin((buf, rows, self.nwalkers, self.ndim), rows))
 
             state = self._dev.sample_monitored(initial_state, max_steps, check_every, thin_by,
                                                on_check)
@@ -455,8 +539,11 @@ class EnsembleSampler:
                 g = min(check_every, max_steps - rows)
                 state = self.run_mcmc(state, g, thin_by=thin_by)
                 rows += g
-                if rows > discard and check(rows, autocorr.integrated_time(
-                        self.get_chain()[it0 + discard:], c=c, tol=0)):
+                if rows <= discard:
+                    continue
+                x = self.get_chain()[it0:]
+                if check(rows, autocorr.integrated_time(x[discard:], c=c, tol=0),
+                         None if rhat is None else gelman_rubin(x, rows)):
                     break
         return state
 
@@ -525,12 +612,21 @@ def _prefit(p0, data, model, prior):
 def get_sampler(data_table=None, p0=None, model=None, prior=None, nwalkers=500, nburn=100,
                 guess=True, interactive=False, prefit=False, labels=None, threads=None,
                 data_sed=None, seed=None, comm=None, verbose=True, store_blobs=True,
-                device=True):
+                device=True, ensembles=1):
     """Generate a new MCMC sampler (signature of core.py:220-233; ``threads`` is
     accepted and ignored -- the walkers of a half-ensemble are one GPU batch;
     ``interactive`` is out of scope).  ``device=True`` (default): the ensemble and the step
     loop live on the GPU (models that cannot keep their parameters in HBM fall back to the
-    host-driven loop with a warning).  Returns (sampler, state)."""
+    host-driven loop with a warning).  Returns (sampler, state).
+
+    ``ensembles`` = k > 1: the ``nwalkers`` walkers are k independent ensembles of nwalkers / k
+    that share every launch (``EnsembleSampler``), for a Gelman-Rubin comparison
+    (``sampler.get_rhat``, ``run_sampler(converge=dict(rhat=1.01))``).  ``p0`` of shape (k, ndim)
+    starts each ensemble from its own row -- dispersed starts, what the comparison is for -- and
+    implies ``ensembles=k``; ``guess`` and ``prefit`` are applied to each row.  A 1-D ``p0`` starts
+    all of them round the same point.  Ensemble r's ball is drawn from
+    ``np.random.default_rng(sampler.seeds[r])``: the ball of a single-ensemble
+    ``get_sampler(seed=seeds[r])`` from the same point."""
     from .core import lnprob, sed_conversion
     from .datatable import validate_data_table
     if data_table is None:
@@ -539,64 +635,87 @@ def get_sampler(data_table=None, p0=None, model=None, prior=None, nwalkers=500, 
     if model is None:
         raise TypeError("Model function is missing!")
     p0 = np.array(p0, dtype=float)
+    if p0.ndim == 2 and len(p0) == 1:  # (one row: the 1-D call, books included)
+        p0 = p0[0]
+    if p0.ndim == 2:
+        if ensembles not in (1, len(p0)):
+            raise ValueError("p0 has %d rows for %d ensembles" % (len(p0), ensembles))
+        ensembles = len(p0)
+    elif p0.ndim != 1:
+        raise ValueError("p0 must be (ndim,) or (ensembles, ndim)")
+    ensembles = int(ensembles)
+    starts = p0 if p0.ndim == 2 else p0[np.newaxis].repeat(max(1, ensembles), axis=0)
+    ndim = starts.shape[1]
     if labels is None:
-        labels = ["norm"] + ["par{0}".format(i) for i in range(1, len(p0))]
-    elif len(labels) < len(p0):
-        labels = list(labels) + ["par{0}".format(i) for i in range(len(labels), len(p0))]
+        labels = ["norm"] + ["par{0}".format(i) for i in range(1, ndim)]
+    elif len(labels) < ndim:
+        labels = list(labels) + ["par{0}".format(i) for i in range(len(labels), ndim)]
 
-    modelout = model(p0, data)
-    spec = modelout[0] if isinstance(modelout, (tuple, list)) else modelout
-    try:  # core.py:352-376: model and data must be convertible to differential flux
-        sed_conversion(data["energy"], spec.unit, False)
-        sed_conversion(data["energy"], data["flux"].unit, False)
-    except u.UnitsError:
-        raise u.UnitsError(
-            "The physical type of the model and data units are not compatible, please modify "
-            "your model or data so they match:\n Model units: {0} [{1}]\n Data units: {2} [{3}]\n"
-            .format(spec.unit, spec.unit.physical_type, data["flux"].unit,
-                    data["flux"].unit.physical_type))
+    def start(p0):
+        """one starting point -> (the point after ``guess`` and ``prefit``, is it an ML point?)"""
+        p0 = p0.copy()
+        modelout = model(p0, data)
+        spec = modelout[0] if isinstance(modelout, (tuple, list)) else modelout
+        try:  # core.py:352-376: model and data must be convertible to differential flux
+            sed_conversion(data["energy"], spec.unit, False)
+            sed_conversion(data["energy"], data["flux"].unit, False)
+        except u.UnitsError:
+            raise u.UnitsError(
+                "The physical type of the model and data units are not compatible, please modify "
+                "your model or data so they match:\n Model units: {0} [{1}]\n Data units: {2} [{3}]\n"
+                .format(spec.unit, spec.unit.physical_type, data["flux"].unit,
+                        data["flux"].unit.physical_type))
 
-    if guess:  # core.py:378-419
-        normNames = ["norm", "ampl", "we", "wp"]
-        normNames += ["log({0}".format(n) for n in normNames[:4]] + \
-                     ["log10({0}".format(n) for n in normNames[:4]]
-        idxs = []
-        for nn in normNames:
-            for l2 in labels:
-                if l2.lower().startswith(nn):
-                    idxs.append(labels.index(l2))
-        if len(idxs) == 1:
-            e = data["energy"]
-            nunit, sedf = sed_conversion(e, spec.unit, False)
-            currFlux = np.trapezoid(e.value * (spec * sedf).to(nunit).value, e.value)
-            nunit, sedf = sed_conversion(e, data["flux"].unit, False)
-            dataFlux = np.trapezoid(e.value * (data["flux"] * sedf).to(nunit).value, e.value)
-            ratio = dataFlux / currFlux
-            if labels[idxs[0]].startswith("log("):
-                p0[idxs[0]] += np.log(ratio)
-            elif labels[idxs[0]].startswith("log10("):
-                p0[idxs[0]] += np.log10(ratio)
-            else:
-                p0[idxs[0]] *= ratio
+        if guess:  # core.py:378-419
+            normNames = ["norm", "ampl", "we", "wp"]
+            normNames += ["log({0}".format(n) for n in normNames[:4]] + \
+                         ["log10({0}".format(n) for n in normNames[:4]]
+            idxs = []
+            for nn in normNames:
+                for l2 in labels:
+                    if l2.lower().startswith(nn):
+                        idxs.append(labels.index(l2))
+            if len(idxs) == 1:
+                e = data["energy"]
+                nunit, sedf = sed_conversion(e, spec.unit, False)
+                currFlux = np.trapezoid(e.value * (spec * sedf).to(nunit).value, e.value)
+                nunit, sedf = sed_conversion(e, data["flux"].unit, False)
+                dataFlux = np.trapezoid(e.value * (data["flux"] * sedf).to(nunit).value, e.value)
+                ratio = dataFlux / currFlux
+                if labels[idxs[0]].startswith("log("):
+                    p0[idxs[0]] += np.log(ratio)
+                elif labels[idxs[0]].startswith("log10("):
+                    p0[idxs[0]] += np.log10(ratio)
+                else:
+                    p0[idxs[0]] *= ratio
 
-    P0_IS_ML = False
-    if prefit:
-        p0, P0_IS_ML = _prefit(p0, data, model, prior)
+        if prefit:
+            return _prefit(p0, data, model, prior)
+        return p0, False
 
-    sampler = EnsembleSampler(nwalkers, len(p0), lnprob, args=[data, model, prior], seed=seed,
+    started = [start(row) for row in (starts if p0.ndim == 2 else starts[:1])]
+    if p0.ndim == 1:
+        started = started * len(starts)
+    p0 = started[0][0] if p0.ndim == 1 else np.array([q for q, _ in started])
+
+    sampler = EnsembleSampler(nwalkers, ndim, lnprob, args=[data, model, prior], seed=seed,
                               comm=comm, naima_style=True, store_blobs=store_blobs,
-                              device=device)
+                              device=device, ensembles=ensembles)
     sampler.data_table = data_table
     sampler.data = data
     sampler.labels = labels
     sampler.modelfn = model
     sampler.run_info = {"n_walkers": nwalkers, "n_burn": nburn,
-                        "p0": [float(p) for p in p0], "guess": guess}
+                        "p0": np.asarray(p0, dtype=float).tolist(), "guess": guess,
+                        "ensembles": ensembles, "seeds": list(sampler.seeds)}
     # ball of 0.5 % (ML start) or 10 % around p0 (core.py:477-481), drawn from the
-    # sampler's replicated stream so that every rank starts from the same ensemble
-    spread = 0.005 if P0_IS_ML else 0.1
-    p0var = spread * p0
-    pos = p0 + p0var * sampler._rng.normal(size=(nwalkers, len(p0)))
+    # sampler's replicated stream so that every rank starts from the same ensemble; several
+    # ensembles: each from the stream of its own seed
+    n = nwalkers // ensembles
+    pos = np.concatenate([
+        q + (0.005 if is_ml else 0.1) * q *
+        (sampler._rng if ensembles == 1 else np.random.default_rng(sd)).normal(size=(n, ndim))
+        for (q, is_ml), sd in zip(started, sampler.seeds)])
     if nburn > 0:
         if verbose and sampler.comm.rank == 0:
             print("Burning in the {0} walkers with {1} steps...".format(nwalkers, nburn))
@@ -614,9 +733,11 @@ def run_sampler(nrun=100, sampler=None, pos=None, verbose=True, thin_by=1, conve
     it.  The burn-in of ``get_sampler`` is not thinned.
 
     ``converge`` = True, or a dict of ``EnsembleSampler.run_until_converged``'s keywords
-    (``check_every``, ``tol``, ``rtol``, ``c``, ``discard``, ``max_lag``): ``nrun`` is then the
-    MAXIMUM, the run stops once the autocorrelation time has converged, and ``run_info`` gains
-    ``converged`` and ``autocorr_time`` (in stored rows)."""
+    (``check_every``, ``tol``, ``rtol``, ``c``, ``discard``, ``max_lag``, ``rhat``): ``nrun`` is then
+    the MAXIMUM, the run stops once the autocorrelation time has converged, and ``run_info`` gains
+    ``converged`` and ``autocorr_time`` (in stored rows).  With ``rhat`` (a sampler of several
+    ensembles) the Gelman-Rubin statistic across them must also lie below it; ``run_info`` gains
+    ``rhat``, the last check's value per parameter."""
     thin_by = int(thin_by)
     if thin_by <= 0:
         raise ValueError("Invalid thinning argument")
@@ -640,10 +761,12 @@ def run_sampler(nrun=100, sampler=None, pos=None, verbose=True, thin_by=1, conve
         conv = sampler.convergence
         sampler.run_info["converged"] = bool(conv["converged"])
         sampler.run_info["autocorr_time"] = [float(t) for t in conv["tau"]]
+        if "rhat" in conv:
+            sampler.run_info["rhat"] = [float(t) for t in conv["rhat"]]
         if verbose and sampler.comm.rank == 0:
             print("{0} after {1} of at most {2} steps; autocorrelation time: {3}".format(
                 "Converged" if conv["converged"] else "Not converged", conv["rows"], int(nrun),
-                conv["tau"]))
+                conv["tau"]) + ("; R-hat: {0}".format(conv["rhat"]) if "rhat" in conv else ""))
     else:
         sampler, pos = _run_mcmc(sampler, pos, nrun, verbose, thin_by)
     sampler.run_info["wall_s"] = time.time() - t0
