@@ -942,6 +942,52 @@ int nh_kde_columns(nh_ctx* ctx, const double* x, long long M, int ncol, long lon
 int nh_group_moments(nh_ctx* ctx, const double* x, long long row0, long long nrows, long long ld,
                      int k, int n, int ndim, int nsplit, long long* counts, double* stats);
 
+/* ---- model comparison: pointwise log-likelihood, WAIC and PSIS-LOO ----------------------------
+ * The matrix L[sample][data point] of a chain's stored spectra and the column reductions the
+ * widely applicable information criterion and Pareto-smoothed importance-sampling leave-one-out
+ * cross-validation (Vehtari, Gelman & Gabry 2017; Vehtari, Simpson, Gelman, Yao & Gabry) need.
+ * Every matrix is a row-major DEVICE matrix [M][ld] with ncol <= ld columns in use; every other
+ * array is a DEVICE array unless marked host; results stay on the device.  Stream-ordered on the
+ * context's stream, no host synchronisation, library scratch, 64-bit row indices.  Deterministic:
+ * integer atomics only; every floating-point sum has an order fixed by the shapes alone.
+ * Every entry point: NH_EINVAL for M == 0, M >= 2^31, ncol < 1, ncol > ld or a null argument.
+ * nh_pointwise_lnl: x [M][ld] holds M spectra at the table's nE energies in the model's unit;
+ *   conv, flux, elo, ehi [nE], ul (int32 [nE]) and cl [nE + 1] are the data columns of the
+ *   likelihood (nh_lnprob).  Writes L [M][ldL]: for a point that is not an upper limit
+ *   -(d*d)/(2*sg*sg) with d = x*conv - flux and sg = d > 0 ? ehi : elo; for an upper limit
+ *   log(1 - cl[nviol]) if x*conv > flux, else 0, nviol being the number of violated limits of the
+ *   ROW (the reference's quirk, core.py:89-92) -- the columns of a row sum to nh_lnprob's
+ *   likelihood of that spectrum.  total [M] (or NULL) receives the row sums (lane order, then a
+ *   butterfly), nbad (int64 [1]) the number of non-finite values written to L.  One wave per row.
+ *   NH_EINVAL also: nE > ldL.
+ * nh_lnl_column_stats: stats [5][ncol] = per column of L its max, mean, unbiased variance
+ *   (ddof = 1; exactly 0 for equal values, NaN for M == 1), lse = max + log sum_s exp(L - max),
+ *   and min.  Two passes in chunk order.  L must be finite (a non-finite value spreads).
+ * nh_psis_columns: per column k, with x_s = min_k - L[s][k] (the negated column, its maximum
+ *   subtracted), Mt the tail length (host: min(M / 5, ceil(3 sqrt(M / reff)))), stats the output
+ *   of nh_lnl_column_stats and lsel [ncol] the order statistic of rank Mt of every column of L
+ *   (nh_column_select): cut = max(min_k - lsel[k], log(DBL_MIN)); the tail is the n <= Mt rows
+ *   with x > cut, sorted by (value, row index).  n <= 4 (always for Mt == 0): pareto_k = +inf and
+ *   nothing is smoothed.  Otherwise the generalised Pareto distribution is fitted to
+ *   t = exp(x) - exp(cut) (Zhang & Stephens 2009 with m = 30 + floor(sqrt(n)) candidates, the
+ *   loo package's weak priors: k = (n k' + 5) / (n + 10)) and, k being finite, tail value i
+ *   becomes min(0, log(sigma expm1(-k log1p(-p_i)) / k + exp(cut))), p_i = (i + 0.5) / n
+ *   (-sigma log1p(-p_i) for |k| < DBL_EPSILON).  With lw = x - logsumexp(x):
+ *   pareto_k [ncol], n_tail (int64 [ncol]) = n, elpd [ncol] = logsumexp_s(lw_s + L[s][k]).
+ *   No weight matrix is written: the rows below the cutoff enter both sums in one chunked pass.
+ *   NH_EINVAL also: Mt outside [0, M), Mt > NH_PSIS_MAX_TAIL (the tail lives in one workgroup's
+ *   LDS: thin the chain). */
+#define NH_PSIS_MAX_TAIL 4096
+int nh_pointwise_lnl(nh_ctx* ctx, const double* x, long long M, int nE, long long ld,
+                     const double* conv, const double* flux, const double* elo, const double* ehi,
+                     const int* ul, const double* cl, double* L, long long ldL, double* total,
+                     long long* nbad);
+int nh_lnl_column_stats(nh_ctx* ctx, const double* L, long long M, int ncol, long long ld,
+                        double* stats);
+int nh_psis_columns(nh_ctx* ctx, const double* L, long long M, int ncol, long long ld, int Mt,
+                    const double* stats, const double* lsel, double* pareto_k, long long* n_tail,
+                    double* elpd);
+
 #ifdef __cplusplus
 }
 #endif

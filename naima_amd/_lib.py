@@ -19,6 +19,7 @@ NH_PD_NPAR = 8
 NH_EBL_ONE, NH_EBL_HIGH, NH_EBL_OUTSIDE = 1, 2, 4  # nh_ebl_table's per-energy codes
 # nh_hist_columns' caps (include/naima_hip.h)
 NH_HIST_MAX_COLS, NH_HIST_MAX_PAIRS, NH_HIST_MAX_BINS_1D, NH_HIST_MAX_BINS_2D = 32, 496, 4096, 100
+NH_PSIS_MAX_TAIL = 4096  # nh_psis_columns' cap on the tail length (include/naima_hip.h)
 NH_K_NAMES = ("particle_weights", "integrate_tables", "synchrotron", "tables", "lnprob",
               "ic_seed_walkers", "glue", "integrate_rows", "half_step")
 PD_KIND = {"PowerLaw": 0, "ExponentialCutoffPowerLaw": 1, "BrokenPowerLaw": 2,
@@ -169,6 +170,9 @@ _SIGS = {
     "nh_group_moments": [_dp, _dp, _ll, _ll, _ll, _i, _i, _i, _i, _dp, _dp],
     "nh_hist_columns": [_dp, _dp, _ll, _i, _ll, _dp, _i, C.POINTER(_i), _i, _dp, _dp],
     "nh_kde_columns": [_dp, _dp, _ll, _i, _ll, _dp, _i, _dp, _dp],
+    "nh_pointwise_lnl": [_dp, _dp, _ll, _i, _ll, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ll, _dp, _dp],
+    "nh_lnl_column_stats": [_dp, _dp, _ll, _i, _ll, _dp],
+    "nh_psis_columns": [_dp, _dp, _ll, _i, _ll, _i, _dp, _dp, _dp, _dp, _dp],
 }
 EXPORTS = tuple(_SIGS) + ("nh_last_error", "nh_version", "nh_ssc_table_bytes")
 

@@ -10,6 +10,7 @@ import numpy as np
 
 from . import units as u
 from .datatable import DataTable
+from .infocrit import InfoCritMixin
 
 __all__ = ["save_run", "read_run", "save_results_table", "find_ML", "save_diagnostic_plots"]
 
@@ -158,8 +159,9 @@ def save_run(filename, sampler, compression=True, clobber=False):
     return filename
 
 
-class _Result:
-    """what read_run returns: chain / log-prob / blobs with emcee's accessor names"""
+class _Result(InfoCritMixin):
+    """what read_run returns: chain / log-prob / blobs with emcee's accessor names, and the
+    sampler's get_pointwise_log_likelihood / waic / loo"""
 
     def __init__(self, chain, log_prob, blobs, blob_units, data, labels, run_info, accf):
         self._chain, self._lp, self._blobs = chain, log_prob, blobs
@@ -326,12 +328,15 @@ def save_diagnostic_plots(outname, sampler, modelidxs=None, pdf=False, sed=True,
 
 
 def save_results_table(outname, sampler, convert_log=True, last_step=False, include_blobs=True,
-                       overwrite=False):
+                       overwrite=False, information_criteria=False):
     """Write ``<outname>_results.ecsv``: median and 16th/84th-percentile distances of every
     parameter (plus the de-logged value for ``log10(x)`` / ``log(x)`` labels and every
     scalar blob), with the run information, the most probable parameters and the BIC as
     metadata (analysis.py:165-363 of the reference; ECSV written directly, astropy is not
-    available).  Returns the table as a dict of columns + ``meta``."""
+    available).  ``information_criteria=True`` adds ``WAIC_elpd``, ``WAIC_p``, ``LOO_elpd``,
+    ``LOO_p``, ``LOO_se`` and ``LOO_max_pareto_k`` of the whole chain's stored spectra (blob 0,
+    ``naima_amd.infocrit``, computed on the GPU) to the metadata; without it the file is what it
+    always was.  Returns the table as a dict of columns + ``meta``."""
     import os
 
     import yaml
@@ -360,6 +365,13 @@ def save_results_table(outname, sampler, convert_log=True, last_step=False, incl
     ndata = len(sampler.data["energy"]) if getattr(sampler, "data", None) is not None else 0
     if ndata:
         meta["BIC"] = float(len(MLp) * np.log(ndata) - 2 * ML)
+    if information_criteria:
+        from .infocrit import loo, sampler_pointwise, waic
+        L = sampler_pointwise(sampler)
+        w, lo = waic(L), loo(L)
+        meta["WAIC_elpd"], meta["WAIC_p"] = w["elpd_waic"], w["p_waic"]
+        meta["LOO_elpd"], meta["LOO_p"], meta["LOO_se"] = lo["elpd_loo"], lo["p_loo"], lo["se"]
+        meta["LOO_max_pareto_k"] = float(np.max(lo["pareto_k"]))
     for k, v in dict(getattr(sampler, "run_info", {})).items():
         meta[k] = v.tolist() if isinstance(v, np.ndarray) else (v.item() if isinstance(
             v, np.generic) else v)

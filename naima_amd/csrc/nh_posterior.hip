@@ -33,43 +33,16 @@
 // No floating-point atomics: every floating-point sum has an order fixed by the shapes alone, so
 // repeated calls give bit-identical results.  Row indices are 64-bit.  Every launch is on the
 // context's stream; nothing synchronises with the host.
-#include "nh_common.h"
-
-#include <algorithm>
+#include "nh_colred.h"
 
 namespace {
 
-constexpr int PO_THREADS = 256;
-constexpr int PO_TARGET_WG = 2048;     // workgroups a launch aims for (a few per CU)
-constexpr int PO_MIN_ROWS = 1024;      // rows a chunk holds at least
 constexpr int PO_CTR_BUDGET = 11264;   // 32-bit LDS counters per histogram workgroup (44 KiB)
 constexpr int PO_KDE_STAGE = 1024;     // values of a column per LDS stage of the KDE kernel
 constexpr unsigned short PO_DROPPED = 0xffffu;
 
-inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
-
-__device__ __forceinline__ bool po_finite(double v) { return fabs(v) < INFINITY; }  // (NaN: false)
-
-// the row chunks of a launch with `ntile` workgroups per chunk: rows per chunk (a multiple of
-// `mult`) and their number, a function of the shapes only
-inline void po_chunks(long long M, long long ntile, long long mult, long long* rows, long long* nch) {
-  long long want = std::max<long long>(1, PO_TARGET_WG / std::max<long long>(1, ntile));
-  long long n = std::min(want, cdiv(M, PO_MIN_ROWS));
-  *rows = cdiv(cdiv(M, n), mult) * mult;
-  *nch = cdiv(M, *rows);
-}
-
 // ---------------------------------------------------------------- moments
-// threads are [R = 256/cw row lanes][cw columns]; v[tid] += v[tid + s*cw] down the row lanes
-template <typename T, typename F>
-__device__ __forceinline__ void po_tree(T* v, int tid, int ty, int cw, F op) {
-  for (int s = (PO_THREADS / cw) >> 1; s > 0; s >>= 1) {
-    __syncthreads();
-    if (ty < s) v[tid] = op(v[tid], v[tid + s * cw]);
-  }
-  __syncthreads();
-}
-
+// (the tiling, the chunks and the LDS tree down the row lanes: nh_colred.h)
 // per (row chunk k, column c): pd[(k*3 + 0|1|2)*ncol + c] = sum, min, max of the finite values,
 // pc[(k*2 + 0|1)*ncol + c] = the number of finite values, of NaNs
 __global__ __launch_bounds__(PO_THREADS) void k_po_sum(const double* __restrict__ x, long long M,
@@ -428,12 +401,6 @@ __global__ void k_po_kde_reduce(const double* __restrict__ part, const long long
     n += pn[(long long)c * nch + k];
   }
   out[(long long)c * G + g] = s / ((double)n * bw[c] * 2.5066282746310002);
-}
-
-inline int po_pow2_at_least(int n, int cap) {
-  int p = 1;
-  while (p < n && p < cap) p <<= 1;
-  return p;
 }
 
 }  // namespace

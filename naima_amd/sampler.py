@@ -19,6 +19,7 @@ import numpy as np
 
 from . import units as u
 from .dist import LocalComm, shard_bounds, shard_counts
+from .infocrit import InfoCritMixin
 
 __all__ = ["EnsembleSampler", "State", "get_sampler", "run_sampler"]
 
@@ -47,7 +48,7 @@ def _split_blob(b):
     return np.asarray(b, dtype=float), None
 
 
-class EnsembleSampler:
+class EnsembleSampler(InfoCritMixin):
     """Stretch-move ensemble sampler over a *batched* log-probability.
 
     log_prob_fn(coords[n, ndim], *args) -> lnp[n]  or  (lnp[n], blob0[n,...], ...)
