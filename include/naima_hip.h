@@ -187,10 +187,14 @@ int nh_synchrotron(nh_ctx* ctx, const double* w, const double* dlw, const double
 
 /* ---- rows 6,7: radiative.py:547-607 + G12/G34 345-367 -------------------- */
 /* Kt[i][k] (1/s per unit ... as _iso/_ani_ic_on_planck return) for temperature
- * T_K; theta_rad < 0 selects the isotropic Eq.14, otherwise Eq.11.
+ * T_K; isotropic != 0 selects the isotropic Eq.14 (theta_rad is not read), otherwise Eq.11
+ * with 1 - cos(theta_rad) as the reference forms it (radiative.py:597) for an angle of ANY sign:
+ * theta and -theta give the same table, theta = 0 a table of NaN.  T_K = 0 passes (the
+ * reference's "positive" admits it) and gives NaN as well.
  * scale[k] = uf*Eph_k/E_eV_k so that integrate_tables gives radiative.py:684-687 */
 int nh_table_ic_planck(nh_ctx* ctx, const double* gam, int nG, const double* E_eV, int nE,
-                       double T_K, double theta_rad, double* Kt, double* dlnKt, int ld);
+                       double T_K, double theta_rad, int isotropic, double* Kt, double* dlnKt,
+                       int ld);
 
 /* ---- row 8: radiative.py:609-655 _iso_ic_on_monochromatic ---------------- */
 /* seed_E_eV[ns]; ns == 1: seed_dens = energy density eV/cm3 (monochromatic);
@@ -421,9 +425,12 @@ int nh_copy(nh_ctx* ctx, void* dev_dst, const void* dev_src, long long bytes);
  *             out[w*ldo + k] in 1/(s eV)
  *   what = 1: InverseCompton on nseed thermal seed fields (radiative.py:547-607), seed s at
  *             out[w*ldo + s*nE + k] = trapz_loglog(nelec sigma_s, gamma); the caller applies
- *             uf * Eph / E (radiative.py:684-687); seed_theta[s] < 0: isotropic.  T and theta
- *             are lazy scalars: a seed temperature / angle may itself be a fit parameter (a
- *             walker with T <= 0 gets the NaN the reference's arithmetic gives)
+ *             uf * Eph / E (radiative.py:684-687); bit s of seed_iso_mask set: seed s is
+ *             isotropic and seed_theta[s] is not read.  An anisotropic seed's angle may have any
+ *             sign -- the reference forms 1 - cos(theta), radiative.py:597: theta and -theta give
+ *             the same spectrum, theta = 0 NaN.  T and theta are lazy scalars: a seed temperature
+ *             / angle may itself be a fit parameter (a walker with T <= 0 gets the NaN the
+ *             reference's arithmetic gives)
  *   what = 2: We = trapz_loglog(gamma nelec, gamma mec2) over the walker's grid, erg
  *             (radiative.py:162-195: We, compute_We with per-walker limits); out[w*ldo]
  *   what = 3: Bremsstrahlung (radiative.py:838-989): out[w*ldo + k] = trapz_loglog(nelec
@@ -432,7 +439,10 @@ int nh_copy(nh_ctx* ctx, void* dev_dst, const void* dev_src, long long bytes);
  * The limits arrive in the unit the caller's Quantity carries, with that unit's value in erg
  * beside them: the kernel forms gamma_min = (Eemin / mec2[erg]) * unit_erg exactly as the host
  * path does (what astropy reduces Eemin / mec2 to), so both paths take log10 of the same double.
- * nEed is a lazy scalar too (nodes per decade per walker).
+ * nEed is a lazy scalar too (nodes per decade per walker), of any sign: a count below 10 is 10.
+ * A walker whose nEed * decades is not finite -- a limit that is negative (NaN) or 0 (+-inf),
+ * where the reference's int() raises ValueError / OverflowError -- gets NaN and leaves status
+ * alone; so does a synchrotron walker with B <= 0, where the reference's arithmetic gives NaN.
  * nmax: grid nodes the workgroup's LDS is sized for (4 nmax doubles); a walker that needs more
  * gets NaN and status[0] (device ints, zeroed by the caller) receives the largest count asked
  * for.  status[1] counts evaluations whose nEed * decades lay within 1e-9 of an integer: there
@@ -442,7 +452,7 @@ int nh_general_electron(nh_ctx* ctx, int kind, const double* rows /*[N][NH_PD_NP
                         const nh_lazy* Eemax /*host*/, double Eemax_unit_erg,
                         const nh_lazy* nEed /*host*/, int what, const nh_lazy* B_G /*host, what = 0*/,
                         const nh_lazy* seed_T_K /*host*/, const nh_lazy* seed_theta /*host*/,
-                        int nseed, const double* E_eV, int nE, double* out, int ldo, int nmax,
+                        int seed_iso_mask, int nseed, const double* E_eV, int nE, double* out, int ldo, int nmax,
                         int* status /*device, 2 ints*/);
 /* the same over every walker's own grid for ONE monochromatic (ns = 1: seed_dens its energy
  * density, eV/cm3) or tabulated (seed_dens in 1/(eV cm3) at the ns energies seed_E, eV) isotropic

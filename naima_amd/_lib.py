@@ -59,7 +59,7 @@ _SIGS = {
     "nh_grid_logratio": [_dp, _dp, _i, _dp],
     "nh_integrate_tables": [_dp, _dp, _dp, _i, _i, _dp, _dp, _dp, _i, _dp, _dp, _i, _i, _i],
     "nh_synchrotron": [_dp, _dp, _dp, _dp, _i, _i, _dp, _dp, _i, _dp, _i, _dp, _i],
-    "nh_table_ic_planck": [_dp, _dp, _i, _dp, _i, _d, _d, _dp, _dp, _i],
+    "nh_table_ic_planck": [_dp, _dp, _i, _dp, _i, _d, _d, _i, _dp, _dp, _i],
     "nh_table_ic_seed": [_dp, _dp, _i, _dp, _i, _dp, _dp, _i, _dp, _dp, _i],
     "nh_ic_seed_walkers": [_dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _i, _dp, _dp, _i, _dp, _i],
     "nh_ssc_table": [_dp, _dp, _i, _dp, _i, _dp, _i, _dp],
@@ -146,8 +146,8 @@ _SIGS = {
     "nh_half_step_run_table_info": [_dp, C.POINTER(_i), C.POINTER(_i)],
     "nh_half_step_run_stamps": [_dp, _dp, _dp],
     "nh_half_step_run_destroy": [_dp, _dp],
-    "nh_general_electron": [_dp, _i, _dp, _i, _dp, _d, _dp, _d, _dp, _i, _dp, _dp, _dp, _i, _dp, _i,
-                            _dp, _i, _i, _dp],
+    "nh_general_electron": [_dp, _i, _dp, _i, _dp, _d, _dp, _d, _dp, _i, _dp, _dp, _dp, _i, _i, _dp,
+                            _i, _dp, _i, _i, _dp],
     "nh_general_electron_seed": [_dp, _i, _dp, _i, _dp, _d, _dp, _d, _dp, _dp, _dp, _i, _dp, _i, _dp,
                                  _i, _i, _dp],
     "nh_general_electron_seed_rows": [_dp, _i, _dp, _i, _dp, _d, _dp, _d, _dp, _dp, _dp, _ll, _i, _dp,

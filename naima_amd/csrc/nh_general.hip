@@ -27,7 +27,8 @@ struct gen_args {
   double emin_erg, emax_erg;  // ... and that unit in erg (astropy's own factor)
   nh_lazy nEed;         // nodes per decade, per walker
   nh_lazy B;            // synchrotron: magnetic field [G]
-  nh_lazy T[NH_MAX_COMP], theta[NH_MAX_COMP];  // IC: seed temperatures [K], angles [rad] (< 0: isotropic)
+  nh_lazy T[NH_MAX_COMP], theta[NH_MAX_COMP];  // IC: seed temperatures [K], angles [rad]
+  int iso_mask;         // IC: bit s set = seed s is isotropic (its theta is not read)
   const double* E_eV; int nE;
   double* out; int ldo;  // out[w*ldo + c*nE + k]
   int nmax;              // LDS capacity in nodes
@@ -71,8 +72,12 @@ __global__ __launch_bounds__(256) void k_general_electron(gen_args A) {
     const double gmax = (nh_lazy_eval(A.emax, wi) / NH_MEC2_ERG_) * A.emax_erg;
     const double l0 = log10(gmin), l1 = log10(gmax);
     const double v = nh_lazy_eval(A.nEed, wi) * (l1 - l0);
-    int n = (int)v;
-    if (!(n >= 10)) n = 10;  // (also NaN limits)
+    // int() of a NaN (a negative limit) or of +-inf (a limit of 0) raises in the reference
+    // (ValueError / OverflowError, radiative.py:152-154): that walker gets a NaN row, and the
+    // status word, which reports grids too long for LDS, stays as it is
+    const bool countable = isfinite(v);
+    int n = countable ? (int)fmax(fmin(v, 2147483647.0), -2147483648.0) : 0;
+    if (!(n >= 10)) n = 10;
     // int() of a float: numpy's log10 and this one may differ in the last place, which decides
     // the count only when v sits within rounding (~1e-13) of an integer.  Such evaluations are
     // counted -- the caller is told (Context.check_general) -- never silently different.
@@ -81,6 +86,7 @@ __global__ __launch_bounds__(256) void k_general_electron(gen_args A) {
       atomicMax(A.status, n);
       n = 0;
     }
+    if (!countable) n = 0;
     s_n = n;
     s_l0 = l0;
     s_l1 = l1;
@@ -91,7 +97,7 @@ __global__ __launch_bounds__(256) void k_general_electron(gen_args A) {
   const double* pr = A.rows + (long long)wi * NH_PD_NPAR;
   const pd_par p = {pr[0], pr[1], pr[2], pr[3], pr[4], pr[5], pr[6]};
   double* orow = A.out + (long long)wi * A.ldo + (long long)comp * A.nE;
-  if (n == 0) {  // grid too long for the workgroup's LDS: NaN, and the status word says so
+  if (n == 0) {  // grid too long for the workgroup's LDS (the status word says so), or no count
     for (int k = tid; k < A.nE; k += blockDim.x) orow[k] = NAN;
     return;
   }
@@ -159,8 +165,11 @@ __global__ __launch_bounds__(256) void k_general_electron(gen_args A) {
         // CS1 = sqrt(3) e^3 B / (2 pi m_e c^2 hbar E), then 1/(s erg) -> 1/(s eV)
         const double cs1 = (1.7320508075688772 * (NH_E_GAUSS * NH_E_GAUSS * NH_E_GAUSS) * Bw) /
                            (2.0 * NH_PI * NH_M_E_G * (NH_C_CGS * NH_C_CGS) * NH_HBAR_CGS * E_erg);
-        orow[k] = (part[lane] + part[64 + lane] + part[128 + lane] + part[192 + lane]) * cs1 *
-                  NH_ERG_PER_EV;
+        // B <= 0: the reference's Gtilde(E / Ec) is NaN (B = 0) or overflows (B < 0) on this grid
+        // and its trapz_loglog returns NaN; the kernel's windowed Gtilde would not
+        orow[k] = Bw > 0.0 ? (part[lane] + part[64 + lane] + part[128 + lane] + part[192 + lane]) *
+                                 cs1 * NH_ERG_PER_EV
+                           : NAN;
       }
       __syncthreads();
     }
@@ -221,15 +230,16 @@ __global__ __launch_bounds__(256) void k_general_electron(gen_args A) {
   } else {
     // ---- InverseCompton on thermal seed `comp` (the caller applies uf * Eph / E) --------
     const double Tp = nh_lazy_eval(A.T[comp], wi) * NH_K_TO_MEC2;
-    const double th = nh_lazy_eval(A.theta[comp], wi);
+    const bool iso = (A.iso_mask >> comp) & 1;
+    const double th = iso ? 0.0 : nh_lazy_eval(A.theta[comp], wi);
     for (int k0 = 0; k0 < A.nE; k0 += 64) {
       const int k = k0 + lane;
       double acc = 0.0;
       if (k < A.nE && s0 < s1) {
         const double eg = A.E_eV[k] / NH_MEC2_EV;
-        double K1 = ic_planck_K(gam[s0], eg, Tp, th);
+        double K1 = ic_planck_K(gam[s0], eg, Tp, th, iso);
         for (int s = s0; s < s1; ++s) {
-          const double K2 = ic_planck_K(gam[s + 1], eg, Tp, th);
+          const double K2 = ic_planck_K(gam[s + 1], eg, Tp, th, iso);
           acc += gen_term(wv[s], wv[s + 1], dw[s], K1, K2, lxs[s]);
           K1 = K2;
         }
@@ -247,15 +257,14 @@ static int general_electron(nh_ctx* c, int kind, const double* rows, int N,
                             const nh_lazy* Eemin, double Eemin_unit_erg,
                             const nh_lazy* Eemax, double Eemax_unit_erg,
                             const nh_lazy* nEed, int what, const nh_lazy* B_G,
-                            const nh_lazy* seed_T, const nh_lazy* seed_theta, int nseed,
-                            const double* seed_E, const double* seed_d, int ns,
+                            const nh_lazy* seed_T, const nh_lazy* seed_theta, int seed_iso_mask,
+                            int nseed, const double* seed_E, const double* seed_d, int ns,
                             const double* E_eV, int nE, double* out, int ldo, int nmax,
                             int* status, long long seed_ld = 0) {
   NH_REQUIRE(c && rows && Eemin && Eemax && nEed && out && status, "NULL pointer");
   NH_REQUIRE(kind >= NH_PD_POWERLAW && kind <= NH_PD_LOGPARABOLA, "unknown particle distribution kind");
   NH_REQUIRE(N >= 0 && nmax >= 10 && Eemin_unit_erg > 0 && Eemax_unit_erg > 0, "bad sizes");
   NH_REQUIRE(what == 2 || (E_eV && nE >= 1), "photon energies missing");
-  NH_REQUIRE(nEed->base || nEed->a > 0.0, "nEed must be positive");
   NH_REQUIRE(what == 0 ? (B_G != nullptr)
                        : (what == 2 || what == 3 || (what == 4 && seed_E && seed_d && ns >= 1) ||
                           (what == 1 && seed_T && seed_theta && nseed >= 1 && nseed <= NH_MAX_COMP)),
@@ -271,10 +280,11 @@ static int general_electron(nh_ctx* c, int kind, const double* rows, int N,
   A.emin_erg = Eemin_unit_erg; A.emax_erg = Eemax_unit_erg;
   if (what == 0) A.B = *B_G;
   for (int s = 0; s < ncomp && what == 1; ++s) {
-    NH_REQUIRE(seed_T[s].base || seed_T[s].a > 0.0, "seed temperature must be positive");
+    NH_REQUIRE(seed_T[s].base || seed_T[s].a >= 0.0, "seed temperature must not be negative");
     A.T[s] = seed_T[s];
     A.theta[s] = seed_theta[s];
   }
+  A.iso_mask = what == 1 ? seed_iso_mask : 0;
   A.E_eV = E_eV; A.nE = nE; A.out = out; A.ldo = ldo; A.nmax = nmax; A.status = status;
   A.seed_E = seed_E; A.seed_d = seed_d; A.ns = ns; A.seed_ld = seed_ld;
   const size_t lds = ((size_t)4 * nmax + 256) * sizeof(double);
@@ -294,13 +304,13 @@ extern "C" int nh_general_electron(nh_ctx* c, int kind, const double* rows, int 
                                    const nh_lazy* Eemin, double Eemin_unit_erg,
                                    const nh_lazy* Eemax, double Eemax_unit_erg,
                                    const nh_lazy* nEed, int what, const nh_lazy* B_G,
-                                   const nh_lazy* seed_T, const nh_lazy* seed_theta, int nseed,
-                                   const double* E_eV, int nE, double* out, int ldo, int nmax,
-                                   int* status) {
+                                   const nh_lazy* seed_T, const nh_lazy* seed_theta,
+                                   int seed_iso_mask, int nseed, const double* E_eV, int nE,
+                                   double* out, int ldo, int nmax, int* status) {
   NH_REQUIRE(what >= 0 && what <= 3, "what = 0 .. 3");
   return general_electron(c, kind, rows, N, Eemin, Eemin_unit_erg, Eemax, Eemax_unit_erg, nEed, what,
-                          B_G, seed_T, seed_theta, nseed, nullptr, nullptr, 0, E_eV, nE, out, ldo,
-                          nmax, status);
+                          B_G, seed_T, seed_theta, seed_iso_mask, nseed, nullptr, nullptr, 0, E_eV,
+                          nE, out, ldo, nmax, status);
 }
 
 // InverseCompton on ONE monochromatic or tabulated isotropic seed field that is the same for
@@ -312,7 +322,7 @@ extern "C" int nh_general_electron_seed(nh_ctx* c, int kind, const double* rows,
                                         const double* seed_dens, int ns, const double* E_eV, int nE,
                                         double* out, int ldo, int nmax, int* status) {
   return general_electron(c, kind, rows, N, Eemin, Eemin_unit_erg, Eemax, Eemax_unit_erg, nEed, 4,
-                          nullptr, nullptr, nullptr, 0, seed_E, seed_dens, ns, E_eV, nE, out, ldo,
+                          nullptr, nullptr, nullptr, 0, 0, seed_E, seed_dens, ns, E_eV, nE, out, ldo,
                           nmax, status);
 }
 
@@ -329,7 +339,7 @@ extern "C" int nh_general_electron_seed_rows(nh_ctx* c, int kind, const double* 
                                              int nmax, int* status) {
   NH_REQUIRE(seed_ld >= ns && ns >= 1, "seed_ld must be at least the number of seed energies");
   return general_electron(c, kind, rows, N, Eemin, Eemin_unit_erg, Eemax, Eemax_unit_erg, nEed, 4,
-                          nullptr, nullptr, nullptr, 0, seed_E, seed_dens, ns, E_eV, nE, out, ldo,
+                          nullptr, nullptr, nullptr, 0, 0, seed_E, seed_dens, ns, E_eV, nE, out, ldo,
                           nmax, status, seed_ld);
 }
 
@@ -375,13 +385,15 @@ __global__ __launch_bounds__(256) void k_general_proton(genp_args A) {
     const double l0 = log10(lo), l1 = log10(hi);
     const double dec = A.count_mode == 0 ? log10(hi / lo) : (l1 - l0);
     const double v = nh_lazy_eval(A.nEpd, wi) * dec;
-    int n = (int)v;
+    const bool countable = isfinite(v);  // (see k_general_electron)
+    int n = countable ? (int)fmax(fmin(v, 2147483647.0), -2147483648.0) : 0;
     if (!(n >= 10)) n = 10;
-    if (v >= 10.0 && fabs(v - rint(v)) < 1e-9) atomicAdd(A.status + 1, 1);  // (see k_general_electron)
+    if (v >= 10.0 && fabs(v - rint(v)) < 1e-9) atomicAdd(A.status + 1, 1);
     if (n > A.nmax) {
       atomicMax(A.status, n);
       n = 0;
     }
+    if (!countable) n = 0;
     s_n = n;
     s_l0 = l0;
     s_l1 = l1;
@@ -467,7 +479,6 @@ extern "C" int nh_general_proton(nh_ctx* c, int kind, const double* rows, int N,
   NH_REQUIRE(what == 2 || (E_eV && nE >= 1 && ldo >= nE), "photon energies missing");
   NH_REQUIRE(what != 0 || (hiE >= NH_PP_GEANT4 && hiE <= NH_PP_QGSJET), "unknown hiEmodel");
   NH_REQUIRE(what != 1 || (tx && ty && cf && ntx >= 8 && nty >= 8), "spline missing");
-  NH_REQUIRE(nEpd->base || nEpd->a > 0.0, "nEpd must be positive");
   if (N == 0) return NH_OK;
   genp_args A;
   memset(&A, 0, sizeof(A));

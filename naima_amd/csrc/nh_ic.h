@@ -19,12 +19,15 @@ __device__ __forceinline__ double ic_G12(double x, double al, double a, double b
 }
 
 
-// sigma(gamma, E_gamma) of Eq. 14 (isotropic, theta < 0) / Eq. 11 (anisotropic) times the
-// (T'/gamma)^2 prefactor; eg = E_gamma / mec2, Tp = T in mec2 (radiative.py:557-574, 586-607)
-__device__ __forceinline__ double ic_planck_K(double g, double eg, double Tp, double theta) {
+// sigma(gamma, E_gamma) of Eq. 14 (``iso``: theta is not read) / Eq. 11 (anisotropic) times the
+// (T'/gamma)^2 prefactor; eg = E_gamma / mec2, Tp = T in mec2 (radiative.py:557-574, 586-607).
+// Isotropy is a flag, not a value of the angle: the reference forms 1 - cos(theta) for an angle of
+// any sign (radiative.py:597), so theta and -theta give the same bits and theta = 0 gives NaN.
+__device__ __forceinline__ double ic_planck_K(double g, double eg, double Tp, double theta,
+                                              bool iso) {
   const double z = eg / g;
   double cs;
-  if (theta < 0.0) {
+  if (iso) {
     double x = z / (1.0 - z) / (4.0 * g * Tp);
     cs = z * z / (2.0 * (1.0 - z)) * ic_G34(x, 0.606, 0.443, 1.481, 0.540, 0.319) +
          ic_G34(x, 0.461, 0.726, 1.457, 0.382, 6.620);

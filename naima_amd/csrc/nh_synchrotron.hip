@@ -84,6 +84,10 @@ __global__ __launch_bounds__(64 * C) void k_synchrotron(
   const int ktiles = (nE + tw - 1) / tw;
   const int tile = blockIdx.x % ktiles, wi = blockIdx.x / ktiles;
   const double Bw = B[(long long)wi * ldB];
+  // B <= 0 (or NaN): the reference's Gtilde(E / Ec) is NaN (B = 0: x = inf) or overflows on the
+  // grid's low nodes (B < 0: exp(|x|)) and its trapz_loglog returns NaN; here q <= 0 would find
+  // every node live, q = inf none.  Such a walker's energies are all dead and read NaN.
+  const bool badB = !(Bw > 0.0);
   // x = E/Ec,  Ec = 3 e hbar B gamma^2 / (2 m_e c)         radiative.py:331-334
   const double qfac = NH_ERG_PER_EV * (2.0 * (NH_M_E_G * NH_C_CGS)) /
                       (3.0 * NH_E_GAUSS * NH_HBAR_CGS * Bw);
@@ -93,7 +97,7 @@ __global__ __launch_bounds__(64 * C) void k_synchrotron(
   if (tid < 64) {
     const int k = tid < tw ? tid * ktiles + tile : nE;
     int i0 = nG;
-    if (k < nE) {
+    if (k < nE && !badB) {
       const double q = E_eV[k] * qfac;
       // first i with q*ig2[i] <= 746 (ig2 decreases with i)
       int lo = 0, hi = nG;
@@ -111,8 +115,8 @@ __global__ __launch_bounds__(64 * C) void k_synchrotron(
       ai0[pos] = i0;  // (from the first LIVE node on: the segment to its left contributes an exact 0)
     }
     if (tid == 0) s_nA = __popcll(m);
-    if (k < nE && !live) out[(long long)wi * ldo + k] = 0.0;
-    if (EPI && k < nE && !live) synv[k] = 0.0;
+    if (k < nE && !live) out[(long long)wi * ldo + k] = badB ? NAN : 0.0;
+    if (EPI && k < nE && !live) synv[k] = badB ? NAN : 0.0;
   }
   __syncthreads();
   const int nA = s_nA;

@@ -47,21 +47,23 @@ static int table_dlog(nh_ctx* c, const double* Kt, int nG, int nE, int ld, doubl
 // rows 6,7: Khangulyan+14 Eq. 14 / Eq. 11: nh_ic.h
 __global__ __launch_bounds__(256) void k_table_ic_planck(const double* __restrict__ gam, int nG,
                                                           const double* __restrict__ E_eV,
-                                                          int nE, double T_K, double theta,
+                                                          int nE, double T_K, double theta, int iso,
                                                           double* __restrict__ Kt, int ld) {
   NH_TAB_PROLOGUE
-  Kt[NH_TAB_AT] = ic_planck_K(gam[i], E_eV[k] / NH_MEC2_EV, T_K * NH_K_TO_MEC2, theta);
+  Kt[NH_TAB_AT] = ic_planck_K(gam[i], E_eV[k] / NH_MEC2_EV, T_K * NH_K_TO_MEC2, theta, iso != 0);
 }
 
 extern "C" int nh_table_ic_planck(nh_ctx* c, const double* gam, int nG, const double* E_eV,
-                                  int nE, double T_K, double theta_rad, double* Kt,
-                                  double* lnKt, int ld) {
+                                  int nE, double T_K, double theta_rad, int isotropic,
+                                  double* Kt, double* lnKt, int ld) {
   NH_REQUIRE(c && gam && E_eV && Kt && lnKt && nG >= 2 && nE >= 1, "bad argument");
-  NH_REQUIRE(T_K > 0.0, "seed temperature must be positive");
+  // (T = 0 passes the reference's "positive" check, validator.py:33-35, and its arithmetic
+  // gives NaN at every energy: so does the kernel's)
+  NH_REQUIRE(T_K >= 0.0, "seed temperature must not be negative");
   nh_prof_scope ps(c, NH_K_TABLES);
   long long tot = (long long)nG * nE;
   hipLaunchKernelGGL(k_table_ic_planck, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,
-                     c->stream, gam, nG, E_eV, nE, T_K, theta_rad, Kt, ld);
+                     c->stream, gam, nG, E_eV, nE, T_K, theta_rad, isotropic, Kt, ld);
   NH_CHECK_HIP(hipGetLastError());
   return table_dlog(c, Kt, nG, nE, ld, lnKt);
 }

@@ -461,11 +461,13 @@ class BaseElectron(BaseRadiative):
         T = (nh_lazy * max(ncomp, 1))()
         th = (nh_lazy * max(ncomp, 1))()
         keep = []
+        iso_mask = 0  # (isotropy is a flag: an angle may have any sign, radiative.py:597)
         for j, (Tq, thq) in enumerate(seeds):
             T[j], k = lazy_of(Tq, "K")
             keep.append(k)
             if thq is None:
-                th[j] = lazy_const(-1.0)
+                th[j] = lazy_const(0.0)
+                iso_mask |= 1 << j
             else:
                 th[j], k = lazy_of(thq, "rad")
                 keep.append(k)
@@ -492,7 +494,7 @@ class BaseElectron(BaseRadiative):
             ctx.call("nh_general_electron", PD_KIND[pd.kind], rows, N, C.addressof(emin),
                      float(_erg_factor(qmin)), C.addressof(emax), float(_erg_factor(qmax)),
                      C.addressof(ned), what, C.addressof(Bl) if Bl is not None else None, T, th,
-                     ncomp, ctx.const(E_eV) if what != 2 else None, nE, out, ncomp * nE,
+                     iso_mask, ncomp, ctx.const(E_eV) if what != 2 else None, nE, out, ncomp * nE,
                      ctx.general_nmax, status)
         del k1, k2, k3, k4, rows, keep
         if not self.on_device:
@@ -659,6 +661,9 @@ class InverseCompton(BaseElectron):
     fields; Aharonian & Atoyan 1981 for monochromatic / tabulated ones);
     radiative.py:370-791.  ``seed_photon_fields`` follows naima's grammar:
     'CMB' | 'FIR' | 'NIR' | [name, T, u] | [name, T, u, theta] | [name, E, density].
+    A field given with ``theta`` is anisotropic for an angle of any sign (1 - cos(theta),
+    radiative.py:597: -theta gives the spectrum of theta, theta = 0 NaN); the three-element form
+    alone is isotropic.
     """
 
     def __init__(self, particle_distribution, seed_photon_fields=["CMB"], **kwargs):
@@ -875,8 +880,8 @@ class InverseCompton(BaseElectron):
 
     def _static_seed_key(self, seed):
         if seed["type"] == "thermal":
-            return ("T", float(seed["T"].to("K").value),
-                    -1.0 if seed["isotropic"] else float(seed["theta"].to("rad").value))
+            return ("T", float(seed["T"].to("K").value), bool(seed["isotropic"]),
+                    0.0 if seed["isotropic"] else float(seed["theta"].to("rad").value))
         se = seed["energy"].to("eV").value
         if se.size == 1:
             sd = np.atleast_1d(seed["photon_density"].to("eV/cm3").value)
@@ -893,8 +898,10 @@ class InverseCompton(BaseElectron):
             kt, lkt = Kt.ptr + 8 * j * nE, dlnKt.ptr + 8 * j * nE
             if seed["type"] == "thermal":
                 T = seed["T"].to("K").value
-                theta = -1.0 if seed["isotropic"] else seed["theta"].to("rad").value
-                ctx.call("nh_table_ic_planck", gd, nG, Ed, nE, float(T), float(theta), kt, lkt, nK)
+                iso = bool(seed["isotropic"])
+                theta = 0.0 if iso else seed["theta"].to("rad").value
+                ctx.call("nh_table_ic_planck", gd, nG, Ed, nE, float(T), float(theta), int(iso),
+                         kt, lkt, nK)
             else:
                 se = seed["energy"].to("eV").value
                 if se.size == 1:

@@ -294,8 +294,11 @@ def ic_seed_spectrum(E_eV, gam, nelec, seed):
     E_eV = np.asarray(E_eV, dtype=float)
     Eph = E_eV / MEC2_EV
     if seed["type"] == "thermal":
-        T = seed["T"]
-        uf = seed["u"] / (AR_CGS * T ** 4)
+        # radiative.py:666-667: uf = (u / (ar * T**4)).decompose() is array arithmetic in the
+        # reference -- T = 0 gives a division warning and inf (then NaN at :684), no exception
+        T = np.float64(seed["T"])
+        with np.errstate(all="ignore"):
+            uf = np.float64(seed["u"]) / (AR_CGS * T ** 4)
         K = ic_planck_kernel(gam, T, Eph, seed.get("theta"))
     else:
         uf = 1.0
