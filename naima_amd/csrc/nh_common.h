@@ -72,6 +72,63 @@ static inline hipError_t nh_put_now(nh_ctx* c, void* dst, const void* src, size_
   return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
 }
 
+// The device and page-locked allocations of one object (a half-step plan, a resident loop):
+// what is taken through the owner is released when the owner goes -- on the failure path of a
+// create and in the destroy alike -- each kind with its own free call.  The first failure sticks
+// and every later call does nothing, so a sequence of allocations, fills and uploads is
+// straight-line code with one test at its end.
+struct nh_owned {
+  struct rec { void* p; bool host; };
+  std::vector<rec> recs;
+  hipError_t err = hipSuccess;
+  nh_owned() = default;
+  nh_owned(const nh_owned&) = delete;
+  nh_owned& operator=(const nh_owned&) = delete;
+  ~nh_owned() {
+    for (const rec& r : recs) (void)(r.host ? hipHostFree(r.p) : hipFree(r.p));
+  }
+  bool ok() const { return err == hipSuccess; }
+  void check(hipError_t e) { if (ok()) err = e; }
+  template <class T> T* keep(void* p, bool host) {
+    if (ok() && p) recs.push_back(rec{p, host});
+    return ok() ? static_cast<T*>(p) : nullptr;
+  }
+  template <class T> T* dev(size_t bytes) {  // hipMalloc
+    void* p = nullptr;
+    if (ok()) err = hipMalloc(&p, bytes);
+    return keep<T>(p, false);
+  }
+  template <class T> T* dev_with_flags(size_t bytes, unsigned flags) {  // fine-grained / uncached device memory
+    void* p = nullptr;
+    if (ok()) err = hipExtMallocWithFlags(&p, bytes, flags);
+    return keep<T>(p, false);
+  }
+  template <class T> T* host(size_t bytes) {  // page-locked host memory
+    void* p = nullptr;
+    if (ok()) err = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+    return keep<T>(p, true);
+  }
+  void fill(nh_ctx* c, void* p, int byte, size_t n) { if (ok()) err = nh_fill_now(c, p, byte, n); }
+  void put(nh_ctx* c, void* dst, const void* src, size_t n) { if (ok()) err = nh_put_now(c, dst, src, n); }
+};
+
+// the device's CU count as the half-step loops plan with it; `fallback` where the runtime does not
+// tell (0: the caller treats that as an error).  Several ranks rehearsing a multi-GPU run on ONE
+// device -- bench.py --gpus N under NAIMA_AMD_DEVICE -- each plan for their share of its CUs
+// (NAIMA_AMD_CU_SHARE): resident workgroups of all ranks have to fit the chip together.
+static inline int nh_cu_count(int fallback) {
+  int ncu = 0, devid = 0;
+  if (hipGetDevice(&devid) != hipSuccess ||
+      hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, devid) != hipSuccess || ncu <= 0) {
+    (void)hipGetLastError();
+    ncu = fallback;
+  }
+  const char* e = getenv("NAIMA_AMD_CU_SHARE");
+  const int share = e ? atoi(e) : 1;
+  if (share > 1 && ncu > 0) ncu = ncu / share > 1 ? ncu / share : 1;
+  return ncu;
+}
+
 // device scratch of at least `bytes`; contents are only valid within one entry point
 int nh_scratch(nh_ctx* c, size_t bytes, void** out);
 

@@ -28,8 +28,8 @@
 // (before its own accept) and, for the complementary half, by the workgroup with the same
 // index (nobody writes those rows).  The kernel boundary is the ensemble-wide barrier
 // between half-steps.
-#include "nh_hs.h"
-#include "nh_syn2.h"
+#include "nh_hs_plan.h"
+#include <memory>
 
 // The first arguments are what the proposal's chain of dependent reads starts from: scalar
 // kernel arguments can be preloaded into SGPRs at dispatch (-amdgpu-kernarg-preload-count),
@@ -73,7 +73,6 @@ static_assert(sizeof(hs_first) == 256 && offsetof(hs_first, qT) == 224 &&
 //   nG Lambda (ln gamma / 3 + ln scale) | nG + 2 GUARD Lambda ln w | 4 nE per-energy constants |
 //   nE comb indices (ints); 1 / gamma^2 with its guards: where the direct form keeps dig2 | ig23
 // the header, the table and the node constants behind the grid's three arrays in F.syn_c.
-#define HS_S2_HDR 16
 __device__ __attribute__((noinline)) double hs_log_ool(double x) { return log(x); }
 template <bool SYN, bool S2 = false>
 __global__ __launch_bounds__(1024) void k_half_step(const int* __restrict__ done_,
@@ -1239,449 +1238,153 @@ extern "C" int nh_hist_append(nh_ctx* c, const double* coords, const double* log
   return NH_OK;
 }
 
-static int hs_create(nh_ctx* c, const nh_hs_desc* d, nh_halfstep_plan** out, int kmax,
-                     int segscale, bool* lds_overflow) {
-  NH_REQUIRE(c && d && out, "NULL pointer");
-  NH_REQUIRE(d->coords && d->logp && d->blk && d->cursor && d->qT && d->factors && d->params &&
-                 d->total, "NULL pointer in the descriptor");
-  NH_REQUIRE(d->ns >= 1 && d->ndim >= 1 && d->ndim <= 64 && d->lo >= 0 && d->nloc >= 1 &&
-                 d->lo + d->nloc <= d->ns, "bad proposal block");
-  NH_REQUIRE(!d->do_accept || (d->lo == 0 && d->nloc == d->ns && d->accepted),
-             "the in-kernel accept needs every walker of the slice in this launch");
-  NH_REQUIRE(d->npacks >= 1 && d->npacks <= NH_MAX_PACK, "bad pack plan");
-  NH_REQUIRE(d->kind >= NH_PD_POWERLAW && d->kind <= NH_PD_LOGPARABOLA, "unknown particle distribution kind");
-  NH_REQUIRE(d->ngrids >= 1 && d->ngrids <= NH_MAX_GRIDS, "bad grid count");
-  NH_REQUIRE(d->nmoms >= 0 && d->nmoms <= NH_MAX_MOMENT, "bad reductions");
-  NH_REQUIRE(d->ntab >= 0 && d->ntab <= NH_HS_MAX_TAB && (d->ntab > 0 || d->syn.grid >= 0),
-             "a half-step needs at least one emission component");
-  NH_REQUIRE(d->ncomp >= 1 && d->ncomp <= NH_MAX_COMP && d->nE >= 1, "bad likelihood components");
-  NH_REQUIRE(d->conv && d->flux && d->err_lo && d->err_hi && d->ul && d->cl, "NULL data column");
-  NH_REQUIRE(d->nterms >= 0 && d->nterms <= NH_MAX_PRIOR, "bad prior terms");
-  static_assert(NH_HS_MAX_TAB == HS_MAX_TAB, "table count");
-  static_assert(sizeof(hs_hot) <= 3800, "the by-value kernel argument must fit the 4 KB segment");
-  hs_hot H;
-  memset(&H, 0, sizeof(H));
-  hs_dev& C = H.C;
-  nh_pack packs_host[NH_MAX_PACK];
-  memset(packs_host, 0, sizeof(packs_host));
-  H.coords = d->coords; H.logp = d->logp; H.blk = d->blk; H.cursor = d->cursor;
-  H.qT = d->qT; H.factors = d->factors; H.hist = d->hist;
-  H.ns = d->ns; H.ndim = d->ndim; H.lo = d->lo; H.nloc = d->nloc;
-  C.npk = d->npacks; C.kind = d->kind; C.params = d->params;
-  bool have_params = false;
-  for (int q = 0; q < d->npacks; ++q) {
-    const nh_pack& pk = d->packs[q];
-    NH_REQUIRE(pk.out && pk.ncols >= 1 && pk.ncols <= NH_MAX_LAZY && pk.ld >= pk.ncols,
-               "bad pack request");
-    for (int k = 0; k < pk.ncols; ++k) {
-      const double* b = pk.cols[k].base;
-      NH_REQUIRE(b == nullptr || (b >= d->qT && b < d->qT + (long long)d->ndim * d->nloc &&
-                                  (b - d->qT) % d->nloc == 0 && pk.cols[k].stride == 1),
-                 "a pack column must read one proposal coordinate (or be a constant)");
-    }
-    if (pk.out == d->params) {
-      NH_REQUIRE(pk.ncols >= 7, "the particle rows need 7 columns");
-      have_params = true;
-    }
-    packs_host[q] = pk;
-  }
-  NH_REQUIRE(have_params, "params must be the output of one of the packs");
-  NH_REQUIRE(d->ndim < 255, "at most 254 fit parameters");
-  for (int t = 0; t < d->ntab; ++t) {  // (checked before anything indexes grids[] with it)
+// every environment override of the two creates (tuning experiments, test hooks): read here, once
+// per create, and nowhere else (nh_hs_plan.h: hs_knobs)
+static hs_opt hs_env_opt(const char* name) {
+  const char* e = getenv(name);
+  hs_opt o;
+  o.set = e != nullptr;
+  o.v = e ? atoi(e) : 0;
+  return o;
+}
+hs_knobs hs_knobs_read() {
+  hs_knobs k = hs_knobs_default();
+  k.test_reject = getenv("NH_HS_TEST_REJECT") != nullptr;
+  if (const char* e = getenv("NH_HS_SPLIT")) k.kmax = atoi(e) > 0 ? atoi(e) : 1;
+  k.part_kb = nh_env_int("NH_HS_PART_KB", k.part_kb);
+  k.threads = hs_env_opt("NH_HS_THREADS");
+  k.split_min_work = nh_env_int("NH_HS_SPLIT_MIN_WORK", k.split_min_work);
+  k.rowsplit = nh_env_int("NH_HS_ROWSPLIT", k.rowsplit);
+  k.rt = nh_env_int("NH_HS_RT", k.rt);
+  k.syn2 = nh_env_int("NH_HS_SYN2", k.syn2);
+  k.rt_debug = getenv("NH_HS_RT_DEBUG") != nullptr;
+  k.seg = hs_env_opt("NH_HS_SEG");
+  k.syn_nodes = hs_env_opt("NH_HS_SYN_NODES");
+  k.debug = nh_env_int("NH_HS_DEBUG", 0) != 0;
+  k.run_rt = nh_env_int("NH_RUN_RT", k.run_rt);
+  k.run_grids_in_lds = nh_env_int("NH_RUN_GRIDS_IN_LDS", k.run_grids_in_lds);
+  k.run_ut = nh_env_int("NH_RUN_UT", k.run_ut);
+  k.run_rowsplit = nh_env_int("NH_RUN_ROWSPLIT", k.run_rowsplit);
+  k.run_syn2 = nh_env_int("NH_RUN_SYN2", k.run_syn2);
+  k.run_il = nh_env_int("NH_RUN_IL", k.run_il);
+  k.run_rebalance = hs_env_opt("NH_RUN_REBALANCE");
+  k.run_tcompact_min = nh_env_int("NH_RUN_TCOMPACT_MIN", k.run_tcompact_min);
+  k.run_syn_nodes = hs_env_opt("NH_RUN_SYN_NODES");
+  k.run_pipeline = nh_env_int("NH_RUN_PIPELINE", k.run_pipeline);
+  k.run_fail_at = nh_env_int("NH_RUN_FAIL_AT", 0);
+  k.run_grid = hs_env_opt("NH_RUN_GRID");
+  k.run_max_per_wg = hs_env_opt("NH_RUN_MAX_PER_WG");
+  k.run_shared_alloc = nh_env_int("NH_RUN_SHARED_ALLOC", k.run_shared_alloc);
+  k.run_spin_limit = hs_env_opt("NH_RUN_SPIN_LIMIT");
+  k.run_publish_delay = nh_env_int("NH_RUN_PUBLISH_DELAY", 0);
+  return k;
+}
+
+// host copy of a grid's nodes, behind one synchronisation of the context's stream
+bool hs_read_grid(const double* xg, int nG, std::vector<double>& out) {
+  out.assign((size_t)nG, 0.0);
+  if (hipMemcpy(out.data(), xg, (size_t)nG * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess) return true;
+  (void)hipGetLastError();
+  return false;
+}
+
+// What the planner asks of the device, read ONCE per create: the CU count; behind one
+// synchronisation the synchrotron grid's nodes (for the log-domain form) and, where table items
+// can stay in registers at all, every table's first row that holds a non-zero.  Nothing here is an
+// error: what could not be read the planner takes as "not log-uniform" / "does not fit registers".
+// (the descriptor has not been validated yet: only what is in range is touched)
+static void hs_gather(nh_ctx* c, const nh_hs_desc* d, const hs_knobs& k, hs_facts& f, std::vector<double>& xg) {
+  f.ncu = nh_cu_count(256);
+  f.syn_xg = nullptr;
+  for (int t = 0; t < HS_MAX_TAB; ++t) f.r0[t] = -1;
+  if (d->ngrids < 1 || d->ngrids > NH_MAX_GRIDS) return;
+  const bool want_xg = d->syn.grid >= 0 && d->syn.grid < d->ngrids && k.syn2 != 0 &&
+                       d->grids[d->syn.grid].xg && d->grids[d->syn.grid].nG >= 2;
+  const bool want_rows = hs_plan_reads_rows(d, k, f.ncu);
+  if ((!want_xg && !want_rows) || nh_sync(c) != NH_OK) return;
+  if (want_xg && hs_read_grid(d->grids[d->syn.grid].xg, d->grids[d->syn.grid].nG, xg)) f.syn_xg = xg.data();
+  for (int t = 0; t < d->ntab && want_rows; ++t) {
     const nh_hs_table& tb = d->tab[t];
-    NH_REQUIRE(tb.grid >= 0 && tb.grid < d->ngrids && tb.KD && tb.out && tb.nK >= 1 &&
-                   tb.ldo >= tb.nK, "bad table reduction");
-  }
-  if (getenv("NH_HS_TEST_REJECT"))  // (test hook: a plan this function turns down)
-    return nh_set_error(NH_EINVAL, "half-step plan rejected (NH_HS_TEST_REJECT)");
-  H.ngrids = d->ngrids;
-  int off = HS_O_FREE;
-  for (int g = 0; g < d->ngrids; ++g) {
-    const nh_grid& gr = d->grids[g];
-    NH_REQUIRE(gr.e_eV && gr.xg && gr.nG >= 2 && (!d->write_weights || (gr.w && gr.dlw)),
-               "bad grid descriptor");
-    NH_REQUIRE(gr.ln_e && gr.lx, "the half-step kernel needs the grids' ln_e and lx arrays");
-    H.e[g] = gr.e_eV; H.xg[g] = gr.xg; H.lne[g] = gr.ln_e; H.lx[g] = gr.lx;
-    H.scale[g] = gr.unit_scale; H.nG[g] = gr.nG;
-    C.w[g] = gr.w; C.dlw[g] = gr.dlw;
-    H.o_w[g] = off; off += gr.nG;
-    H.o_d[g] = off; off += gr.nG;
-    H.o_lx[g] = off; off += gr.nG;
-    H.o_dp[g] = H.o_th[g] = -1;
-    for (int t = 0; t < d->ntab; ++t)
-      if (d->tab[t].grid == g && d->tab[t].nonnegative) {
-        H.o_dp[g] = off; off += gr.nG;
-        H.o_th[g] = off; off += gr.nG;
-        break;
-      }
-  }
-  H.o_mkt = off;
-  H.nmom = d->nmoms;
-  for (int m = 0; m < d->nmoms; ++m) {
-    NH_REQUIRE(d->moms[m].grid >= 0 && d->moms[m].grid < d->ngrids && d->moms[m].Kt &&
-                   d->moms[m].dlnKt && d->moms[m].out, "bad reduction");
-    H.mKt[m] = d->moms[m].Kt; H.mdK[m] = d->moms[m].dlnKt; H.mgrid[m] = d->moms[m].grid;
-    C.mom_out[m] = d->moms[m].out;
-    off += 2 * d->grids[d->moms[m].grid].nG;
-  }
-  C.accepted = d->accepted; C.naccepted = d->naccepted; C.sel = d->sel;
-  C.do_accept = d->do_accept; C.write_weights = d->write_weights;
-  // ---- synchrotron ----
-  H.syn_grid = -1;
-  int nspec = 0;
-  int syn_nE = 0;
-  if (d->syn.grid >= 0) {
-    const nh_hs_syn& s = d->syn;
-    NH_REQUIRE(s.grid < d->ngrids && s.E_eV && s.out && s.nE >= 1 && s.ldo >= (s.out2 ? s.n1 : s.nE) &&
-                   (s.bcol >= 0 ? s.bcol < NH_PD_NPAR : (s.B != nullptr && s.ldB >= 1)),
-               "bad synchrotron component");
-    const int nG = d->grids[s.grid].nG;
-    NH_REQUIRE(s.nE <= 512, "at most 512 photon energies for the synchrotron component");
-    H.syn_grid = s.grid; H.syn_E = s.E_eV; H.syn_nE = syn_nE = s.nE;
-    C.synB = s.B; C.syn_out = s.out; C.syn_ldo = s.ldo; C.syn_bcol = s.bcol; C.syn_ldB = s.ldB;
-    NH_REQUIRE(s.out2 == nullptr || (s.n1 >= 1 && s.n1 < s.nE && s.ldo >= s.n1 && s.ldo2 >= s.nE - s.n1),
-               "bad split of the synchrotron component's output");
-    NH_REQUIRE(s.out2 == nullptr || (s.out2 == s.out + (long long)d->nloc * s.ldo && s.ldo2 == s.nE - s.n1 &&
-                                     s.ldo < (1 << 20) && s.n1 < (1 << 11)),
-               "the synchrotron component's second array must follow its first (out + nloc * ldo), rows of nE - n1");
-    if (s.out2) C.syn_ldo = s.ldo | (s.n1 << 20);
-    H.o_ig2 = off; off += nG;
-    H.o_dig2 = off; off += nG;
-    H.o_ig23 = off; off += nG;
-    H.o_sq = off; off += 3 * s.nE;
-    H.o_amap = off; off += s.nE + 1;  // 2 nE ints
-    int cdmax = (int)(((size_t)nh_env_int("NH_HS_PART_KB", 40) * 1024) / ((size_t)s.nE * 8));  // (partial sums: 40 KB of LDS at most)
-    cdmax = cdmax > 32 ? 32 : (cdmax < 1 ? 1 : cdmax);
-    C.syn_cdmax = cdmax;
-    H.o_part_s = off; off += cdmax * s.nE;
-    H.syn_spec_off = nspec;
-    nspec += s.nE;
-  }
-  // workgroup size: small reductions are bound by the dependent round trips, not by lanes
-  int maxnG = 0;
-  for (int g = 0; g < d->ngrids; ++g) maxnG = d->grids[g].nG > maxnG ? d->grids[g].nG : maxnG;
-  long long work = 0;
-  for (int t = 0; t < d->ntab; ++t)
-    work += (long long)((d->tab[t].nK + 63) / 64) * 64 * d->grids[d->tab[t].grid].nG * 12;
-  if (d->syn.grid >= 0) work += (long long)d->syn.nE * d->grids[d->syn.grid].nG * 110 / 3;
-  int threads = work >= (1 << 20) ? 1024 : (work >= (1 << 18) ? 512 : 256);
-  if (threads < 1024 && maxnG > threads) threads = maxnG > 512 ? 1024 : 512;
-  int ncu = 256;
-  {
-    hipDeviceProp_t prop;
-    int devid = 0;
-    if (hipGetDevice(&devid) == hipSuccess && hipGetDeviceProperties(&prop, devid) == hipSuccess &&
-        prop.multiProcessorCount > 0)
-      ncu = prop.multiProcessorCount;
-  }
-  // (several ranks rehearsing a multi-GPU run on ONE device -- bench.py --gpus N under
-  // NAIMA_AMD_DEVICE -- each plan for their share of its CUs: resident workgroups of all ranks
-  // have to fit the chip together)
-  {
-    const int share = nh_env_int("NAIMA_AMD_CU_SHARE", 1);
-    if (share > 1) ncu = ncu / share > 1 ? ncu / share : 1;
-  }
-  // A table-only model's launch is half prologue and tail (dependent round trips, single-wave
-  // phases: 9 of cfg5's 16 us) with the CU's other waves idle.  When a launch holds more
-  // walkers than the chip has CUs, smaller workgroups put several walkers on a CU at once and
-  // one walker's prologue runs beside another's items: cfg5 at 1024 walkers per launch 66.8 us
-  // (1024 threads, four rounds) -> 51.6 (512) -> 37.0 (256 threads, four workgroups per CU).
-  // Launches of at most one walker per CU keep the large workgroup (256 walkers: 15.6 us at
-  // 1024 threads, 16.7 at 512, 24.5 at 256).
-  if (d->syn.grid < 0)
-    while (threads > 256 && (long long)d->nloc * threads > 1024LL * ncu) threads >>= 1;
-  if (const char* e = getenv("NH_HS_THREADS")) threads = atoi(e);
-  NH_REQUIRE(threads >= 128 && threads <= 1024 && threads % 64 == 0, "bad workgroup size");
-  if (d->syn.grid >= 0 && threads / 64 < (d->syn.nE + 63) / 64 + 2) threads = 1024;
-  while (threads < 1024 && threads / 64 <= d->nmoms + 1) threads <<= 1;  // (a wave per single-row reduction)
-  NH_REQUIRE(threads / 64 > d->nmoms + 1, "more single-row reductions than waves");
-  // ---- a launch of fewer walkers than the chip has CUs: K workgroups per walker ----
-  // (each repeats the prologue -- on CUs that would otherwise idle -- and takes every K-th
-  // work item; the items are cut finer so that every wave of every workgroup still gets some)
-  int split = 1;
-  {
-    // (worth it where the work items are most of a launch: measured on cfg2 / cfg3 at 128
-    // walkers per launch 42.3 -> 32.7 us and 33.8 -> 28.0 us; the hand-off costs ~3.5 us, which
-    // the table-only models cfg1 / cfg5 -- 7 us of items in a 17 us launch -- do not get back)
-    if (work >= nh_env_int("NH_HS_SPLIT_MIN_WORK", 1 << 20))
-      while (split * 2 <= kmax && (long long)d->nloc * split * 2 <= ncu) split *= 2;
-  }
-  // ---- a table-only model with ONE table, at most half as many walkers per launch as
-  // CUs (BASELINE's PionDecay fit at one GPU's share of its 2048 walkers): two workgroups per
-  // walker that split the grid's ROWS -- each forms the weights of its half, reduces its half of
-  // the table (from registers: half the rows fit a lane's) and of the single-row reductions, and
-  // the second hands its partial spectrum to the first (the resident loop: hs_run.rowsplit; the
-  // per-launch kernel runs the same plan with its items interleaved, as any split launch)
-  bool rowsplit = false;
-  if (split == 1 && d->syn.grid < 0 && d->ntab == 1 && kmax >= 2 &&
-      (long long)d->nloc * 2 <= ncu && nh_env_int("NH_HS_ROWSPLIT", 1) != 0) {
-    split = 2;
-    rowsplit = true;
-  }
-  // ---- a table-only model whose items' rows fit a lane's registers: workgroups of 512 threads
-  // (256 vector registers per lane), for the resident loop's register-resident items (nh_hs.h:
-  // hs_rt_item; k_half_step_run<false, ., false, RT>).  The rows an item walks start at the first
-  // one in which a column is non-zero (the resident loop's sorted copies: at least that far up).
-  bool rt_plan = false;
-  // (launches of at most one workgroup per CU: a workgroup of this instance has a CU to itself)
-  if (d->syn.grid < 0 && d->ntab > 0 && threads >= 256 && (long long)d->nloc * split <= ncu &&
-      nh_env_int("NH_HS_RT", 1) != 0) {
-    bool fits = true;
-    int tiles = 0;
-    for (int t = 0; t < d->ntab; ++t) {
-      tiles += (d->tab[t].nK + 63) / 64;
-    }
-    const int t_rt = threads > 512 ? 512 : threads;
-    const int free_waves = (t_rt / 64 - d->nmoms) * split;
-    fits = fits && free_waves >= 1 && tiles <= free_waves;
-    const int per_tile = fits ? free_waves / tiles : 1;
-    if (fits && nh_sync(c) != NH_OK) fits = false;
-    for (int t = 0; t < d->ntab && fits; ++t) {
-      const nh_hs_table& tb = d->tab[t];
-      const int nG = d->grids[tb.grid].nG, nK = tb.nK;
-      if ((size_t)nG * nK * 16 > ((size_t)64 << 20)) {  // (nothing of that size fits a lane's registers)
-        fits = false;
-        break;
-      }
-      std::vector<double> kd((size_t)nG * nK * 2);
-      if (hipMemcpy(kd.data(), tb.KD, kd.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
-        (void)hipGetLastError();
-        fits = false;
-        break;
-      }
-      int r0 = nG - 1;
-      for (int i = 0; i < nG - 1 && r0 == nG - 1; ++i)
-        for (int k = 0; k < nK; ++k)
-          if (kd[((size_t)i * nK + k) * 2] != 0.0) { r0 = i; break; }
-      const int sub = nK <= 32 ? (nK <= 16 ? (nK <= 8 ? (nK <= 4 ? (nK <= 2 ? (nK <= 1 ? 64 : 32) : 16) : 8) : 4) : 2) : 1;
-      const int per = (nG - 1 - r0 + per_tile - 1) / per_tile;
-      fits = (per + sub - 1) / sub + 1 <= HS_RT_NODES;
-      if (getenv("NH_HS_RT_DEBUG"))
-        fprintf(stderr, "RT: table %d nG %d nK %d r0 %d per_tile %d per %d sub %d nodes %d fits %d\n", t, nG, nK, r0,
-                per_tile, per, sub, (per + sub - 1) / sub + 1, (int)fits);
-    }
-    if (getenv("NH_HS_RT_DEBUG")) fprintf(stderr, "RT: fits %d threads %d nmoms %d split %d\n", (int)fits, threads, d->nmoms, split);
-    if (fits) {
-      threads = t_rt;
-      rt_plan = true;
-    }
-  }
-  // ---- table reductions: work items of `seg` segments x 64 columns ----
-  // With a synchrotron component the items interleave with its (issue-bound) items and 32
-  // segments keep the waves evenly loaded; without one, ONE round of equal items over the
-  // waves that are free from the start (not on a single-row reduction) ends soonest.
-  C.ntab = d->ntab;
-  // (48 segments per item where a walker has one workgroup: with the synchrotron items in the log
-  // domain -- half the instructions they were -- the table items are the larger share of the
-  // resident loop's work, and a third fewer of them means a third less set-up: cfg3 10.6 -> 11.0 M
-  // walker-steps/s together with 48-node synchrotron items; 64: 10.9, 96: 10.7, 128: 10.3.  The
-  // per-launch kernel loses 2 % to it.)
-  int seg = split >= 4 ? 8 : (split == 2 ? 16 : (d->syn.grid >= 0 ? 48 : 32));
-  if (split > 1) seg *= segscale;  // (coarser items: fewer partial sums in LDS)
-  C.syn_nodes = HS_SYN_NODES / split > 3 ? HS_SYN_NODES / split : 3;
-  if (const char* e = getenv("NH_HS_SEG")) seg = atoi(e) >= 4 ? atoi(e) : seg;  // (tuning experiments)
-  if (const char* e = getenv("NH_HS_SYN_NODES")) C.syn_nodes = atoi(e) >= 1 ? atoi(e) : C.syn_nodes;
-  if (d->syn.grid < 0 && d->ntab > 0) {
-    int tiles = 0, maxseg = 0;
-    for (int t = 0; t < d->ntab; ++t) {
-      tiles += (d->tab[t].nK + 63) / 64;
-      const int nseg = d->grids[d->tab[t].grid].nG - 1;
-      maxseg = nseg > maxseg ? nseg : maxseg;
-    }
-    const int free_waves = (threads / 64 - d->nmoms) * split;
-    int per_tile = free_waves / tiles > 1 ? free_waves / tiles : 1;
-    seg = (maxseg + per_tile - 1) / per_tile;
-    if (seg < 8) seg = 8;
-  }
-  auto chunking = [&](int nseg) { return (nseg + seg - 1) / seg; };
-  for (;;) {
-    int nT = 0;
-    for (int t = 0; t < d->ntab; ++t) {
-      const int tiles = (d->tab[t].nK + 63) / 64;
-      nT += tiles * chunking(d->grids[d->tab[t].grid].nG - 1);
-    }
-    if (nT <= (split > 1 ? 160 : 96)) break;
-    seg *= 2;
-  }
-  C.seg = seg;
-  int nT = 0;
-  for (int t = 0; t < d->ntab; ++t) {
-    const nh_hs_table& tb = d->tab[t];
-    const int nG = d->grids[tb.grid].nG;
-    NH_REQUIRE((long long)nG * tb.nK < (1LL << 27), "table too large for 32-bit offsets");
-    hs_tab& o = C.tab[t];
-    o.KD = tb.KD; o.scale = tb.scale;
-    H.tscale[t] = tb.scale; H.tnK[t] = tb.nK; o.out = tb.out; o.grid = tb.grid;
-    o.nK = tb.nK; o.ldo = tb.ldo; o.nonneg = tb.nonnegative;
-    o.tiles = (tb.nK + 63) / 64;
-    o.nKp = 64;
-    o.sub = 1;
-    if (tb.nK <= 32) {
-      o.nKp = 32;
-      while (o.nKp / 2 >= tb.nK && o.nKp > 1) o.nKp /= 2;
-      o.sub = 64 / o.nKp;
-    }
-    const int nchunks = chunking(nG - 1);
-    NH_REQUIRE(nchunks < 256 && seg < 32768, "table cut into too many chunks");
-    o.chunks = nchunks | (nchunks << 8) | (seg << 16);  // (chunks | chunks of length seg | seg)
-    o.item0 = nT;
-    nT += o.tiles * nchunks;
-    o.spec_off = nspec;
-    H.tspec[t] = nspec;
-    nspec += tb.nK;
-  }
-  C.nT = nT;
-  H.o_part_t = off; off += nT * 64;
-  H.o_spec = off; off += nspec;
-  C.nspec = nspec;
-  H.o_lik = off; off += 5 * d->nE;
-  H.o_scale = off; off += nspec;
-  H.o_synE = off; off += syn_nE;
-  H.o_pri = off; off += (int)(sizeof(nh_prior_pack) / sizeof(double)) + 1;
-  H.ntab = d->ntab;
-  NH_REQUIRE(d->nblobs >= 0 && d->nblobs <= NH_HS_MAX_BLOB, "bad blob count");
-  C.nblob = d->nblobs;
-  C.sendw = d->do_accept ? 0 : d->send_width;
-  if (C.sendw > 0) {
-    int wsum = 1;
-    for (int b = 0; b < d->nblobs; ++b) wsum += d->blobs[b].m;
-    NH_REQUIRE(C.sendw >= wsum, "send_width smaller than 1 + the blobs' lengths");
-  }
-  C.o_mrow = off; off += d->nE + NH_MAX_MOMENT;
-  for (int b = 0; b < d->nblobs; ++b) {
-    const nh_hs_blob& bl = d->blobs[b];
-    NH_REQUIRE(d->do_accept || d->send_width > 0,
-               "blobs in the launch need the in-launch accept or an exchange row");
-    NH_REQUIRE(bl.cur && ((bl.kind == 0 && bl.m == d->nE) ||
-                          (bl.kind == 1 && bl.m == 1 && bl.mom >= 0 && bl.mom < d->nmoms)),
-               "bad blob");
-    C.blob[b] = bl;
-  }
-  // ---- likelihood: where does each component of the model live? ----
-  C.ncomp = d->ncomp; H.nE = d->nE;
-  for (int q = 0; q < d->ncomp; ++q) {
-    const nh_comp& cp = d->comps[q];
-    NH_REQUIRE(cp.ptr && cp.ld >= d->nE, "bad component");
-    hs_comp& o = C.comp[q];
-    o.ptr = cp.ptr; o.ld = cp.ld; o.scale = cp.scale; o.off = -1;
-    for (int t = 0; t < d->ntab && o.off < 0; ++t) {
-      const long long dd = cp.ptr - d->tab[t].out;
-      if (dd >= 0 && dd + d->nE <= d->tab[t].nK && cp.ld == d->tab[t].ldo)
-        o.off = C.tab[t].spec_off + (int)dd;
-    }
-    if (o.off < 0 && d->syn.grid >= 0) {
-      const long long dd = cp.ptr - d->syn.out;
-      if (dd >= 0 && dd + d->nE <= syn_nE && cp.ld == d->syn.ldo) o.off = H.syn_spec_off + (int)dd;
-    }
-  }
-  H.conv = d->conv; H.flux = d->flux; H.elo = d->err_lo; H.ehi = d->err_hi; H.ul = d->ul;
-  H.cl = d->cl;
-  C.lp = d->lp; C.model_out = d->model_out; C.total = d->total;
-  C.pri.n = d->nterms;
-  for (int t = 0; t < d->nterms; ++t) C.pri.t[t] = d->terms[t];
-  // ---- the synchrotron items in the log domain (nh_syn2.h), as the resident loop runs them: a
-  // log-uniform grid (np.logspace, radiative.py:147-154), its table and node constants behind the
-  // grid's three arrays in syn_c, their block in LDS behind o_s2 (k_half_step<true, true>)
-  hs_s2_host s2h;
-  H.o_s2 = 0;
-  const size_t lds_core = (size_t)off * sizeof(double);  // (what the resident loop builds on: it has a block of its own)
-  if (d->syn.grid >= 0 && nh_env_int("NH_HS_SYN2", 1) != 0) {
-    const int sg = d->syn.grid, nGs = d->grids[sg].nG;
-    std::vector<double> gam((size_t)nGs);
-    bool ok = nh_sync(c) == NH_OK;
-    if (ok && hipMemcpy(gam.data(), d->grids[sg].xg, (size_t)nGs * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
+    if (tb.grid < 0 || tb.grid >= d->ngrids || !tb.KD || tb.nK < 1 || d->grids[tb.grid].nG < 2) break;
+    const int nG = d->grids[tb.grid].nG, nK = tb.nK;
+    if ((size_t)nG * nK * 16 > ((size_t)64 << 20)) break;  // (nothing of that size fits a lane's registers)
+    std::vector<double> kd((size_t)nG * nK * 2);
+    if (hipMemcpy(kd.data(), tb.KD, kd.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
       (void)hipGetLastError();
-      ok = false;
+      break;
     }
-    ok = ok && hs_s2_prepare(gam.data(), nGs, d->grids[sg].unit_scale, s2h);
-    if (getenv("NH_HS_RT_DEBUG"))
-      fprintf(stderr, "S2: grid %d nG %d nE %d log-uniform %d off %d (%.1f KB) split %d\n", sg, nGs, d->syn.nE, (int)ok, off,
-              off * 8.0 / 1024, split);
-    if (ok) {
-      const int o = off + (off & 1);  // (the pieces are read as ds_read_b128)
-      const int need = HS_S2_HDR + (s2h.par.P + 1) * HS_S2_STRIDE + HS_S2_TN + nGs + (nGs + 2 * HS_S2_GUARD) +
-                       4 * d->syn.nE + (d->syn.nE + 1) / 2 + 1;
-      if ((size_t)(o + need) * sizeof(double) <= 160 * 1024) {  // (a CU's LDS; the plan's own layout keeps to 150 KB)
-        H.o_s2 = o;
-        off = o + need;
-        // (items that start on a piece boundary with a node and six coefficients of their own:
-        // short ones pay for that -- the resident loop's lengths)
-        // (cfg3 / 512, one launch per half-step: 30.6 us at 16 or 24 nodes per item, 31.1 at 32,
-        // 33.9 at 48, 32.7 in the direct form)
-        if (!getenv("NH_HS_SYN_NODES")) C.syn_nodes = split == 1 ? 24 : (C.syn_nodes < 16 ? 16 : C.syn_nodes);
-      }
-    }
+    int r0 = nG - 1;
+    for (int i = 0; i < nG - 1 && r0 == nG - 1; ++i)
+      for (int q = 0; q < nK; ++q)
+        if (kd[((size_t)i * nK + q) * 2] != 0.0) { r0 = i; break; }
+    f.r0[t] = r0;
   }
-  const size_t lds = (size_t)off * sizeof(double);
-  if (lds_core > 150 * 1024) *lds_overflow = true;
-  NH_REQUIRE(lds_core <= 150 * 1024, "the model's grids and tables do not fit in LDS");
-  C.dbg = nullptr;
-  if (const char* e = getenv("NH_HS_DEBUG"))
-    if (atoi(e) != 0) {
-      NH_CHECK_HIP(hipMalloc(&C.dbg, 67840 * sizeof(long long)));
-      NH_CHECK_HIP(nh_fill_now(c, C.dbg, 0, 67840 * sizeof(long long)));
-    }
-  nh_halfstep_plan* P = new nh_halfstep_plan();
-  P->dbg = C.dbg;
+}
+
+static int hs_create(nh_ctx* c, const nh_hs_desc* d, nh_halfstep_plan** out) {
+  NH_REQUIRE(c && d && out, "NULL pointer");
+  // ---- 1. the device's facts, 2. the plan (nh_hs_plan.h) ----
+  const hs_knobs k = hs_knobs_read();
+  hs_facts facts;
+  std::vector<double> xg;
+  hs_gather(c, d, k, facts, xg);
+  std::unique_ptr<nh_halfstep_plan> P(new nh_halfstep_plan());
+  hs_hot& H = P->hot;
+  hs_shape S;
+  const int rc = hs_plan(d, k, facts, H, S);
+  if (rc != NH_OK) return rc;
   P->span = 3;
-  P->lds_bytes = lds;
-  P->lds_core = lds_core;
-  P->threads = threads;
+  P->lds_bytes = S.lds_bytes;
+  P->lds_core = S.lds_core;
+  P->threads = S.threads;
   P->blocks = d->nloc;
-  P->split = split;
-  P->rowsplit = rowsplit ? 1 : 0;
-  P->rt = rt_plan ? 1 : 0;
-  P->dev = nullptr;
-  P->words = nullptr;
-  P->syn_c = nullptr;
-  P->xspec = nullptr;
-  P->tick = nullptr;
-  hipError_t e = hipMalloc(&P->dev, sizeof(packs_host));
-  if (e == hipSuccess && H.syn_grid >= 0) {
+  P->split = S.split;
+  P->rowsplit = S.rowsplit ? 1 : 0;
+  P->rt = S.rt ? 1 : 0;
+  // ---- 3. the plan's device memory ----
+  nh_owned& m = P->mem;
+  const int nspec = H.C.nspec;
+  if (k.debug) {
+    P->dbg = m.dev<long long>(67840 * sizeof(long long));
+    m.fill(c, P->dbg, 0, 67840 * sizeof(long long));
+  }
+  P->dev = m.dev<nh_pack>(sizeof(S.packs));
+  if (H.syn_grid >= 0) {
     const int nGs = H.nG[H.syn_grid];
-    const size_t ns2 = H.o_s2 ? HS_S2_HDR + s2h.data.size() : 0;
-    e = hipMalloc(&P->syn_c, (3 * (size_t)nGs + ns2) * sizeof(double));
-    if (e == hipSuccess) {
+    const size_t ns2 = H.o_s2 ? HS_S2_HDR + S.s2.data.size() : 0;
+    P->syn_c = m.dev<double>((3 * (size_t)nGs + ns2) * sizeof(double));
+    if (m.ok()) {
       hipLaunchKernelGGL(k_syn_consts, dim3((unsigned)((nGs + 255) / 256)), dim3(256), 0, c->stream,
                          H.xg[H.syn_grid], H.lx[H.syn_grid], nGs, P->syn_c);
-      e = hipGetLastError();
+      m.check(hipGetLastError());
     }
-    if (e == hipSuccess && ns2) {
+    if (m.ok() && ns2) {
+      const hs_s2_host& s2h = S.s2;
       std::vector<double> up(ns2, 0.0);
       up[0] = s2h.par.ilx; up[1] = s2h.par.th; up[2] = s2h.par.im; up[3] = s2h.par.lml;
       up[4] = s2h.invd; up[5] = s2h.z0;
       int* iv = reinterpret_cast<int*>(&up[6]);
       iv[0] = s2h.par.lm; iv[1] = s2h.par.P; iv[2] = s2h.par.nG; iv[3] = 0;
       for (size_t q = 0; q < s2h.data.size(); ++q) up[HS_S2_HDR + q] = s2h.data[q];
-      e = nh_put_now(c, P->syn_c + 3 * (size_t)nGs, up.data(), ns2 * sizeof(double));
+      m.put(c, P->syn_c + 3 * (size_t)nGs, up.data(), ns2 * sizeof(double));
     }
   }
-  if (e == hipSuccess && split > 1) {
-    e = hipMalloc(&P->xspec, (size_t)d->nloc * split * nspec * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&P->tick, (size_t)d->nloc * sizeof(int));
-    if (e == hipSuccess) e = nh_fill_now(c, P->tick, 0, (size_t)d->nloc * sizeof(int));
+  if (S.split > 1) {
+    P->xspec = m.dev<double>((size_t)d->nloc * S.split * nspec * sizeof(double));
+    P->tick = m.dev<int>((size_t)d->nloc * sizeof(int));
+    m.fill(c, P->tick, 0, (size_t)d->nloc * sizeof(int));
   }
-  if (e == hipSuccess) e = hipMalloc(&P->words, 4 * sizeof(int));  // done | hbase | NaN proposals | -
-  if (e == hipSuccess) e = nh_put_now(c, P->dev, packs_host, sizeof(packs_host));
-  if (e == hipSuccess) e = nh_fill_now(c, P->words, 0, 4 * sizeof(int));
-  if (e == hipSuccess && lds > 64 * 1024)
-    e = H.syn_grid >= 0
-            ? (H.o_s2 ? hipFuncSetAttribute((const void*)k_half_step<true, true>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                      : hipFuncSetAttribute((const void*)k_half_step<true>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
-            : hipFuncSetAttribute((const void*)k_half_step<false>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) {
-    if (P->dev) (void)hipFree(P->dev);
-    if (P->words) (void)hipFree(P->words);
-    if (P->syn_c) (void)hipFree(P->syn_c);
-    if (P->xspec) (void)hipFree(P->xspec);
-    if (P->tick) (void)hipFree(P->tick);
-    if (P->dbg) (void)hipFree(P->dbg);
-    delete P;
-    return nh_set_error(NH_EHIP, "half-step plan: %s", hipGetErrorString(e));
-  }
+  P->words = m.dev<int>(4 * sizeof(int));  // done | hbase | NaN proposals | -
+  m.put(c, P->dev, S.packs, sizeof(S.packs));
+  m.fill(c, P->words, 0, 4 * sizeof(int));
+  if (S.lds_bytes > 64 * 1024)
+    m.check(hipFuncSetAttribute(H.syn_grid >= 0 ? (H.o_s2 ? (const void*)k_half_step<true, true>
+                                                          : (const void*)k_half_step<true>)
+                                                : (const void*)k_half_step<false>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_bytes));
+  if (!m.ok()) return nh_set_error(NH_EHIP, "half-step plan: %s", hipGetErrorString(m.err));
+  // ---- 4. publish: the plan's own pointers, the first scalar trip's block ----
+  H.C.dbg = P->dbg;
   H.C.pk = P->dev;
   H.C.xspec = P->xspec;
   H.C.tick = P->tick;
@@ -1698,7 +1401,7 @@ static int hs_create(nh_ctx* c, const nh_hs_desc* d, nh_halfstep_plan** out, int
                ((d->kind == NH_PD_ECPL || d->kind == NH_PD_ECBPL) ? 2 : 0);
     F.ppk = -1;
     for (int q = 0; q < d->npacks; ++q)
-      if (packs_host[q].out == d->params) F.ppk = q;
+      if (S.packs[q].out == d->params) F.ppk = q;
     for (int g = 0; g < H.ngrids; ++g) {
       F.nG[g] = H.nG[g];
       F.e[g] = H.e[g]; F.xg[g] = H.xg[g]; F.lne[g] = H.lne[g]; F.lx[g] = H.lx[g];
@@ -1706,31 +1409,19 @@ static int hs_create(nh_ctx* c, const nh_hs_desc* d, nh_halfstep_plan** out, int
     for (int t = 0; t < 32; ++t) {
       unsigned b = 0xFFu;
       const int q = t / NH_MAX_LAZY, col = t % NH_MAX_LAZY;
-      if (q < d->npacks && col < packs_host[q].ncols && packs_host[q].cols[col].base) {
-        const long long off = packs_host[q].cols[col].base - H.qT;
+      if (q < d->npacks && col < S.packs[q].ncols && S.packs[q].cols[col].base) {
+        const long long off = S.packs[q].cols[col].base - H.qT;
         b = (unsigned)(off / H.nloc);  // (a proposal coordinate: checked above)
       }
       F.pkd[t >> 2] |= b << (8 * (t & 3));
     }
   }
-  P->hot = H;
-  *out = P;
+  *out = P.release();
   return NH_OK;
 }
 
-// (a split launch cuts the work items finer and needs more LDS for their partial sums: where
-// that does not fit, fewer workgroups per walker)
 extern "C" int nh_half_step_create(nh_ctx* c, const nh_hs_desc* d, nh_halfstep_plan** out) {
-  int kmax = 8;
-  if (const char* e = getenv("NH_HS_SPLIT")) kmax = atoi(e) > 0 ? atoi(e) : 1;
-  for (;; kmax >>= 1) {
-    for (int segscale = 1; segscale <= 4; segscale *= 2) {  // coarser items before fewer workgroups
-      bool lds_overflow = false;
-      const int rc = hs_create(c, d, out, kmax, segscale, &lds_overflow);
-      if (rc == NH_OK || !lds_overflow) return rc;
-      if (kmax <= 1) return rc;
-    }
-  }
+  return hs_create(c, d, out);
 }
 
 // A new block of moves has been uploaded to `blk`: the next launch proposes its slice
@@ -1850,12 +1541,6 @@ extern "C" int nh_half_step_destroy(nh_ctx* c, nh_halfstep_plan* P) {
   NH_REQUIRE(c, "ctx is NULL");
   if (!P) return NH_OK;
   int rc = nh_sync(c);
-  if (P->dev) (void)hipFree(P->dev);
-  if (P->syn_c) (void)hipFree(P->syn_c);
-  if (P->xspec) (void)hipFree(P->xspec);
-  if (P->tick) (void)hipFree(P->tick);
-  if (P->words) (void)hipFree(P->words);
-  if (P->dbg) (void)hipFree(P->dbg);
-  delete P;
+  delete P;  // (its device memory goes with it: nh_owned)
   return rc;
 }

@@ -17,7 +17,7 @@ struct hs_tab {
   int grid, nK, ldo, nonneg, spec_off, tiles, item0, chunks;
   int sub, nKp;  // nK <= 32: sub = 64 / nKp sub-ranges of an item share a wave (nKp = 32, 16, ...)
   // `chunks` packs three numbers: chunks | nfull << 8 | seg2 << 16.  Chunks [0, nfull) hold `seg`
-  // segments each, the rest seg2 (<= seg).  hs_create sets nfull = chunks and seg2 = seg: every
+  // segments each, the rest seg2 (<= seg).  hs_plan sets nfull = chunks and seg2 = seg: every
   // chunk holds `seg` segments, the last one what is left.  (Packed into the existing word: a wider
   // struct made the compiler copy the whole by-value descriptor to scratch in k_half_step.)
 };
@@ -136,6 +136,7 @@ struct hs_hot {
 
 struct nh_halfstep_plan {
   hs_hot hot;
+  nh_owned mem;      // the plan's device memory: what the pointers below point into
   nh_pack* dev;      // device copy of the parameter packs
   int* words;        // device: done counter | hbase
   double* syn_c;     // device: the synchrotron grid's constants (k_syn_consts), or NULL

@@ -42,139 +42,15 @@
 // current-blob array when no history is kept); k_run_epilogue fills the blob rows of rejected
 // proposals forward from the previous step and adds the accept flags to the acceptance
 // counters.
-#include "nh_hs.h"
-#include "nh_syn2.h"
+#include "nh_hs_plan.h"
+#include <memory>
 #include <vector>
 #include <chrono>
 #include <unistd.h>
 
-#define HS_RUN_MAX_STEPS 32  // steps per launch (one block of moves); ring rows = this + 1
-#define HS_RUN_ERR_TIMEOUT 1
-#define HS_RUN_ERR_PEER 2
-#define HS_RUN_ERR_LAST_ROW 3  // (epilogue of a shared ensemble: a rank's last records never came)
-#define HS_RUN_MAX_RANKS 8     // GPUs of one node that may share an ensemble
-#define HS_RUN_HEAD 512        // granules ahead of the rings in a shared allocation (probe slots)
-#define HS_O_HX 56           // two ints of the small block: HX_PRE, HX_SPECRD (two walkers in flight)
-enum { HX_PRE = 0, HX_SPECRD = 1 };
-#define HS_O_LNA 48          // in the small per-walker block (proposal coordinates: <= 15 of its first 64 doubles)
-#define HS_RUN_TRAIL 16        // ints of first-row entries per table in LDS (>= tiles of any table)
-#define HS_RUN_PKW 8           // doubles per parameter-pack column in LDS
 #ifndef HS_RUN_PK
 #define HS_RUN_PK 5      // nodes per trip of a narrow table's items in the table-only instances (nh_hs.h): 6 spilled 8 VGPRs (cfg5 9.12 M walker-steps/s, 9.77 M at 5; cfg1 1.49 -> 1.46 M)
 #endif
-
-// the weights' unit table (hs_run.o_ut): ints per unit
-enum { HSU_FL = 0, HSU_NL, HSU_G, HSU_W, HSU_D, HSU_DP, HSU_IL, HSU_TH, HSU_LX, HSU_LNE, HSU_GX, HSU_GE,
-       HSU_S2LW, HSU_S2LG, HSU_SC_LO, HSU_SC_HI, HSU_N };
-// HSU_FL: bits 0-1 = 0 plain | 1 the log-domain synchrotron items read ln w of this grid too | 2 and
-// nothing else of it; bit 2: the non-negative table items' pre-divided log-ratios are kept; bit 3:
-// ... with 1 / lx and the thresholds in LDS since the launch began; bit 4: the unit is its grid's last
-static_assert(HSU_N == 16, "a unit's descriptor is four 16-byte reads");
-
-// the table items' descriptors (hs_run.o_it): HS_MAX_TAB x 16 ints per TABLE (HST_*), then 4 ints
-// per ITEM { table | tile << 4, first row, end row, the same two ignoring the leading zero rows (16
-// bits each) }
-enum { HST_KD_LO = 0, HST_KD_HI, HST_NK, HST_NG, HST_AW, HST_AD, HST_AL, HST_FLAGS, HST_SUB, HST_NKP,
-       HST_N = 16 };
-#define HSI_N 4
-
-struct hs_run {
-  unsigned long long* ring;  // [HS_RUN_MAX_STEPS + 1][N][gr] granules
-  int* status;               // device word: 0, or HS_RUN_ERR_* of the first workgroup that gave up
-  int* accw;                 // [HS_RUN_MAX_STEPS][N]: 1 where the step's proposal was accepted
-  double* hcoords; double* hlogp;  // chain history of this call (or NULL) ...
-  double* hblob[NH_HS_MAX_BLOB];   // ... and the blobs' (or NULL)
-  long long hrow0, hcap;     // history row of the launch's first step; rows the history holds
-  long long* dbg;            // NH_HS_DEBUG: [256][64][8] wall-clock stamps, or NULL
-  // gridDim.y = K > 1 workgroups share a walker (a half-step of fewer walkers than CUs, as in
-  // k_half_step): partial spectra of slice s at xspec[s][walker][K][nspec], arrival tickets at
-  // tick[s][walker] (zeroed before the launch) -- per slice, because nothing stops one of a
-  // walker's workgroups from running slices ahead of another
-  double* xspec; int* tick;
-  int slice0, nslices;       // slices [slice0, slice0 + nslices) of the block of moves; slice0 even
-  unsigned seq;              // launch sequence number (tags)
-  int gr, N;                 // granules per record (a multiple of 16: one record = whole lines)
-  int o_gx[NH_MAX_GRIDS], o_lne[NH_MAX_GRIDS], o_ge[NH_MAX_GRIDS];  // LDS: grid nodes, ln E, E
-  int o_pk, o_small1, o_olds;  // LDS: pack descriptors, the second small block, old coordinates
-  int o_lcl;                   // LDS: ln(1 - cl[n]), n <= nE
-  int o_trail;                 // LDS: the tables' trailers (ints)
-  // the loop's own copies of the plan's tables with their columns sorted (nh_hs.h; NULL: the
-  // plan's table as it is)
-  const double* kds[HS_MAX_TAB];
-  int spin_limit;
-  // synchrotron nodes per thread and work item.  The plan's 10 suit a launch per half-step and
-  // workgroups that share a walker; one resident workgroup per walker runs fastest on items
-  // three times that long (cfg3, us per 40 half-steps: 1 015 at 10, 981 at 16, 975 at 24, 959
-  // at 30 and at 40; two workgroups per walker -- cfg2 -- 901 at 5, 885 at 10, 914 at 16)
-  int syn_nodes;
-  int rebalance;  // a tile's chunks divide the rows above its first non-zero one (table-only models)
-  // what the host learns about a launch without a round trip of its own: k_run_epilogue stores
-  // { status, NaN proposals, forbidden proposals, launch number } (the number last) into one of
-  // two slots of page-locked host memory (nh_half_step_run_report)
-  int* report;
-  int report_launch;
-  // NaN / forbidden proposals THIS launch has met (two device ints, a pair per launch parity):
-  // k_run_epilogue adds them to the plan's counters only when the launch ended well, so that a
-  // launch that gave up part of the way leaves the counters as it found them whoever of its
-  // workgroups had already counted (what a replay of its block of moves starts from)
-  int* lcnt;
-  int o_il[NH_MAX_GRIDS];  // LDS: 1 / lx per node of a grid a non-negative table is reduced over (-1: none)
-  // LDS: the weights' units -- 64 consecutive nodes of one grid each -- as 16 ints per unit
-  // (HSU_*: grid, first node, node count, where the node's inputs and outputs sit in LDS, the
-  // grid's scale), built once per launch; -1: the grids' nodes are not in LDS (small workgroups)
-  int o_ut;
-  // LDS: the table work items -- which table, column tile and rows, where the walker's arrays
-  // sit -- as 16 ints per item (HSI_*), built once per launch: a work item read its table's
-  // descriptor out of the kernel-argument segment field by field (dependent vector loads: the
-  // table index is not a constant) and re-derived its rows -- ~300 vector instructions before its
-  // first segment, as many as the segments of a 32-row item cost; -1: not used
-  int o_it;
-  // LDS: per column of the tables' (sorted) spectra 4 ints { first partial sum | stride | chunks |
-  // where it goes in spec } + its scale's index rides with `where`; and the model's components as
-  // NH_MAX_COMP x { offset in spec (int, as a double's low word) | scale }: the phases behind
-  // barrier 3 -- one or a few waves, everybody else waiting -- took these out of the
-  // kernel-argument segment one dependent scalar load at a time (four round trips per component)
-  int o_sum, o_cmp;
-  int o_pci;  // LDS: per prior term the proposed coordinate it reads, or -1 (ints)
-  int o_mt;     // LDS: per single-row reduction { w, dlw, lx, K | dlnK (LDS byte addresses), nG, first row, last row } (ints)
-  int o_lnt;    // LDS: 128 x { 1 / c_j, ln c_j }, c_j the centres of [1/2, 1)'s 128 bins (hsr_ln_tab; log-domain instances)
-  int o_synce;  // LDS: CS1 / B per photon energy (walker-independent: a division per live energy and slice otherwise)
-  // K workgroups of a table-only walker split the grid's ROWS (nh_halfstep.hip: the plan's
-  // rowsplit): workgroup `part` owns the nodes [b_part, b_part+1] -- the boundaries sit between
-  // two of the table's chunks -- forms the weights there, reduces its chunks and its part of the
-  // single-row reductions, and hands its partial sums to workgroup 0 of the walker
-  int rowsplit;
-  int tcompact;  // K > 1: a table item's partial sums in the slot of its group (hs_run_create)
-  int o_rs;   // LDS: this workgroup's nodes per grid and its units (rowsplit)
-  int nxmax;  // doubles a workgroup hands over at most (spectrum + single-row reductions)
-  int sum_cols;  // columns of all the tables together (the sum phase's loop bound)
-  // ---- an ensemble shared by several GPUs (nrank > 1; see "The ensemble across GPUs" below):
-  // `ring` is this launch's ring in THIS rank's memory, peer[p] the same ring in rank p's
-  // (peer[rank] == ring); a mover stores its walker's record into every one of them
-  int nrank, rank;
-  unsigned long long* peer[HS_RUN_MAX_RANKS];
-  int* nacc_own;   // acceptance counters of the moves THIS rank made (the plan's are replicated)
-  int* hacc;       // with a history: [hcap][N] -1 | 0 | 1 = not moved by this rank | rejected | accepted
-  int* curstamp;   // with blobs: [N] stamp of the last move this rank accepted for the walker
-  int stamp0;         // stamp of the launch's first step (counts the steps of all launches)
-  // NH_RUN_PUBLISH_DELAY (100 MHz ticks; experiments): a mover waits this long before it stores a
-  // record -- every hand-off of the shared loop then pays what a slower link would add
-  int publish_delay;
-  // ---- the synchrotron items in the log domain, on the grid's comb (nh_syn2.h; syn2 != 0) ----
-  int syn2, s2_own;  // s2_own: nobody else reads the synchrotron grid's w / dlw (its LDS is reused)
-  int o_s2tab, o_s2lw, o_s2ig, o_s2lg, o_s2q, o_s2z, o_s2t;  // LDS: table | Lambda ln w (guards either side) |
-                                                      // 1/gamma^2 (guards) | Lambda (ln gamma / 3 +
-                                                      // ln scale) | per live energy 4 doubles | comb index | 2^(j/128)
-  const double* s2_dev;  // device: the table's (P + 1) x 6 doubles, then the grid's nG values of the above
-  hs_syn2_par s2;
-  double s2_z0, s2_invd;  // z = s2_z0 - ln(q) s2_invd: where node 0 sits on the comb below T_top
-  double s2_r746;         // (T_top - ln 746) s2_invd - s2_z0: the first live node is ceil(ln(q) s2_invd + this)
-  double s2_lnw0;         // ln |n| + ln(E / eV) above this: the weight gamma n scale is not 0 in double
-  int pipeline;           // two walkers in flight (a workgroup with several walkers of a slice): NH_RUN_PIPELINE
-  long long* clk;         // the context's span clock (nh_common.h): this launch opens a span, k_run_epilogue closes it
-};
-
-static_assert(sizeof(hs_hot) + sizeof(hs_run) <= 4000, "both argument blocks fit the kernarg segment");
 
 __device__ __forceinline__ unsigned long long hs_ld_sc1(const unsigned long long* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2016,12 +1892,12 @@ __global__ void k_run_epilogue(const hs_epi R, int nsteps) {
 // ---------------------------------------------------------------------------------------------
 struct nh_halfstep_run {
   hs_run R;
-  unsigned long long* ring;
+  nh_owned mem;  // the loop's device and page-locked memory: what the pointers below point into
+  unsigned long long* ring;  // one GPU: the ring; a shared ensemble: the launch's ring inside `base`
   int* status;
   int* accw;
   long long* dbg;
   double* xspec;
-  int* tick;
   int split;
   size_t lds_bytes;
   int grid, threads;
@@ -2065,268 +1941,31 @@ static int hs_run_create(nh_ctx* c, nh_halfstep_plan* P, int rank, int nrank, nh
   NH_REQUIRE(c && P && out, "bad argument");
   const hs_hot& H = P->hot;
   const bool shared = nrank > 1;
-  NH_REQUIRE(shared || H.C.do_accept, "the resident loop needs the in-launch accept");
-  NH_REQUIRE(H.ndim <= 15, "at most 15 fit parameters in a record (32 granules per wave half)");
-  NH_REQUIRE(shared || (H.lo == 0 && H.nloc == H.ns), "the resident loop moves whole half-ensembles");
-  NH_REQUIRE(!shared || (nrank <= HS_RUN_MAX_RANKS && rank >= 0 && rank < nrank && H.nloc >= 1 &&
-                         H.lo >= 0 && H.lo + H.nloc <= H.ns),
-             "a shared ensemble: at most 8 ranks, each with at least one walker of every half-step");
-  NH_REQUIRE(H.C.lp == nullptr, "a prior evaluated by a launch of its own cannot ride in the resident loop");
-  for (int b = 0; b < H.C.nblob; ++b)
-    NH_REQUIRE(2LL * H.ns * H.C.blob[b].m < (1LL << 31), "a blob's rows of one step: too large for 32-bit element offsets");
-  for (int q = 0; q < H.C.ncomp; ++q)
-    NH_REQUIRE(H.C.comp[q].off >= 0, "every component of the model must be produced inside the launch");
-  hs_run R;
-  memset(&R, 0, sizeof(R));
-  R.N = 2 * H.ns;
-  R.gr = ((2 * (H.ndim + 1) + 15) / 16) * 16;
-  // LDS: the plan's layout, then what stays resident on top of it
-  int off = (int)(P->lds_core / sizeof(double));
-  // Workgroups of 1024 threads own their CU: the grids' nodes, ln E (and E where the particle
-  // distribution has a break) stay in LDS for the whole launch.  Smaller workgroups (a half-step
-  // of more walkers than CUs, k_half_step item 14) share a CU, and LDS decides how many fit:
-  // they read the nodes from L2 every slice, as k_half_step does, while a neighbour computes.
-  // RT: a table-only model in workgroups of <= 512 threads (256 vector registers per lane) keeps
-  // its table items' rows in registers (nh_hs.h: hs_rt_item); a workgroup owns its CU then, too
-  bool rt = P->rt != 0 && H.syn_grid < 0 && H.ntab > 0 && P->threads <= 512 && nh_env_int("NH_RUN_RT", 1) != 0;
-  rt = rt && H.C.nT <= (P->threads / 64) * P->split;  // (one item per wave)
-  const bool grids_in_lds = (P->threads >= 1024 || rt) && nh_env_int("NH_RUN_GRIDS_IN_LDS", 1) != 0;
-  for (int g = 0; g < NH_MAX_GRIDS; ++g) R.o_gx[g] = R.o_lne[g] = R.o_ge[g] = -1;
-  for (int g = 0; g < H.ngrids && grids_in_lds; ++g) {
-    R.o_gx[g] = off; off += H.nG[g];
-    R.o_lne[g] = off; off += H.nG[g];
-    R.o_ge[g] = off;
-    if (H.F.broken & 1) off += H.nG[g];
-  }
-  // ---- the table grids' 1 / lx in LDS, and the weights' units (below)
-  for (int g = 0; g < NH_MAX_GRIDS; ++g) R.o_il[g] = -1;
-  R.rebalance = nh_env_int("NH_RUN_REBALANCE", H.syn_grid < 0 ? 1 : 0);
-  const bool units_tab = grids_in_lds && nh_env_int("NH_RUN_UT", 1) != 0;
-  // (the plan chose two workgroups per walker for a table-only model with one table: they halve
-  // the grids' rows when the units' table is there -- the grids' nodes in LDS -- the chunks divide
-  // the walked rows and come in a whole number per workgroup; else they interleave the items)
-  R.rowsplit = (P->rowsplit && P->split >= 2 && units_tab && R.rebalance && H.ntab == 1 &&
-                HS_CHUNKS(H.C.tab[0].chunks) % P->split == 0 && H.C.nT % P->split == 0 &&
-                nh_env_int("NH_RUN_ROWSPLIT", 1) != 0) ? 1 : 0;
-  // K > 1 workgroups per walker: a workgroup computes one work item of every K, and keeps its
-  // table items' partial sums in the slot of the GROUP (its n-th item: slot n) -- a K-th of the
-  // plan's block of them, which k_half_step fills in full; what that frees (54 KB at four
-  // workgroups per walker) is the first place the loop's own arrays go
-  // (from four workgroups per walker on: with two, clearing the whole block every slice and
-  // summing it blindly measured faster than deciding per chunk whose it is -- cfg5 / 256 10.9
-  // against 10.3 M walker-steps/s, cfg3 / 256 7.12 against 6.94; cfg3 / 128, four per walker: 3.95
-  // against 4.07 the other way, and its log-domain synchrotron table fits LDS again)
-  R.tcompact = P->split >= nh_env_int("NH_RUN_TCOMPACT_MIN", 4) ? 1 : 0;
-  int hole_lo = 0, hole_hi = 0;
-  if (R.tcompact) {
-    int nsmax = 0;  // synchrotron items of a slice at most
-    if (H.syn_grid >= 0) nsmax = (H.syn_nE * H.C.syn_cdmax + 63) / 64;
-    const int nslots = R.rowsplit ? H.C.nT / P->split : (H.C.nT + nsmax) / P->split + 2;
-    if (nslots < H.C.nT) {
-      hole_lo = H.o_part_t + nslots * 64;
-      hole_hi = H.o_part_t + H.C.nT * 64;
-    } else {
-      R.tcompact = 0;
-    }
-  }
-  auto take = [&](int n, bool align16) {
-    if (align16) hole_lo += hole_lo & 1;
-    if (hole_lo + n <= hole_hi) {
-      const int at = hole_lo;
-      hole_lo += n;
-      return at;
-    }
-    if (align16) off += off & 1;
-    const int at = off;
-    off += n;
-    return at;
-  };
-  R.o_ut = -1;
-  if (units_tab) {
-    int nunits = 0;
-    for (int g = 0; g < H.ngrids; ++g) nunits += (H.nG[g] + 63) / 64;
-    R.o_ut = take(nunits * (HSU_N / 2), true);  // (a unit's descriptor is read as four ds_read_b128)
-  }
-  {
-    int ncols = 0;
-    for (int t = 0; t < H.ntab; ++t) ncols += H.C.tab[t].nK;
-    R.sum_cols = ncols;
-    R.o_sum = take(ncols, false);
-    R.o_cmp = take(2 * NH_MAX_COMP + 2, false);
-    R.o_pci = take((NH_MAX_PRIOR + 1) / 2, false);
-    R.o_synce = H.syn_grid >= 0 ? take(H.syn_nE, false) : -1;
-    R.o_lnt = -1;  // (allotted with the log-domain block, below)
-    R.o_mt = take(4 * NH_MAX_MOMENT, true);
-    {
-      int nun = 0;
-      for (int g = 0; g < H.ngrids; ++g) nun += (H.nG[g] + 63) / 64;
-      R.o_rs = take((9 + nun + 2 * NH_MAX_GRIDS + 1) / 2, false);
-    }
-    R.nxmax = H.C.nspec + NH_MAX_MOMENT;
-  }
-  for (int t = 0; t < H.ntab; ++t)
-    NH_REQUIRE(H.nG[H.C.tab[t].grid] < 65536, "a table's grid has too many nodes for the items' descriptors");
-  R.o_it = -1;
-  if (!rt && H.C.nT > 0)  // (the register-resident instance keeps its rows per wave: no table)
-    R.o_it = take((HS_MAX_TAB * HST_N + H.C.nT * HSI_N + 1) / 2, true);
-  R.o_pk = take(NH_MAX_PACK * NH_MAX_LAZY * HS_RUN_PKW, false);
-  R.o_small1 = take(HS_O_T64, false);
-  R.o_olds = take(128, false);
-  R.o_lcl = take(H.nE + 1, false);
-  R.o_trail = take((HS_RUN_TRAIL * HS_MAX_TAB + H.C.nspec + 1) / 2, false);
-  for (int t = 0; t < H.ntab; ++t)
-    NH_REQUIRE(H.C.tab[t].tiles <= HS_RUN_TRAIL, "a table of more column tiles than the resident loop stages");
-  // ---- the synchrotron items in the log domain (nh_syn2.h): a log-uniform grid only -------------
-  std::vector<double> s2_host;
-  R.syn2 = 0;
-  R.s2_dev = nullptr;
-  if (H.syn_grid >= 0 && nh_env_int("NH_RUN_SYN2", 1) != 0) {
-    const int nG = H.nG[H.syn_grid];
-    std::vector<double> gam((size_t)nG);
+  // ---- 1. the device's facts: the synchrotron grid's nodes, where the log-domain form is allowed ----
+  const hs_knobs k = hs_knobs_read();
+  std::vector<double> xg;
+  if (H.syn_grid >= 0 && k.run_syn2 != 0) {
     int rc = nh_sync(c);
     if (rc) return rc;
-    NH_CHECK_HIP(hipMemcpy(gam.data(), H.xg[H.syn_grid], (size_t)nG * sizeof(double), hipMemcpyDeviceToHost));
-    bool ok = nG >= 8 && gam[0] > 0.0 && H.scale[H.syn_grid] > 0.0;
-    long double lx = 0.0L, dev = 0.0L;
-    if (ok) {
-      const long double l0 = logl((long double)gam[0]);
-      lx = (logl((long double)gam[nG - 1]) - l0) / (nG - 1);
-      for (int i = 0; i < nG && ok; ++i) {
-        ok = gam[i] > 0.0;
-        if (ok) dev = fmaxl(dev, fabsl(logl((long double)gam[i]) - l0 - i * lx));
-      }
-      // (np.logspace, radiative.py:147-154: the nodes sit on i lx to a few 1e-15; 1e-12 in ln gamma
-      // is 7e-13 in ln Gtilde)
-      ok = ok && lx > 0.0L && dev <= 1e-12L;
-    }
-    int lm = 0;
-    if (ok) {
-      const double delta = (double)(2.0L * lx);
-      lm = (int)lrint(log2(0.16 / delta));
-      ok = lm >= 1 && lm <= 4;  // pieces of m = 2 .. 16 comb steps, h = m delta in [0.113, 0.226]
-    }
-    if (ok) {
-      const int m = 1 << lm;
-      const long double h = m * 2.0L * lx;
-      const int P = (int)ceill(((long double)HS_S2_TTOP - (long double)HS_S2_TBOT) / h);
-      s2_host.assign((size_t)(P + 1) * HS_S2_STRIDE + nG, 0.0);
-      for (int pc = 0; pc < P; ++pc) hs_s2_piece(pc, h, &s2_host[(size_t)pc * HS_S2_STRIDE]);
-      // (piece P, and every node below the table: rho = 0, i.e. Gtilde = 1.808 x^(1/3))
-      s2_host[(size_t)P * HS_S2_STRIDE] = (double)((long double)HS_S2_LAMBDA * logl(1.808L));
-      for (int i = 0; i < nG; ++i)
-        s2_host[(size_t)(P + 1) * HS_S2_STRIDE + i] =
-            (double)((long double)HS_S2_LAMBDA * (logl((long double)gam[i]) / 3.0L + logl((long double)H.scale[H.syn_grid])));
-      R.s2.lm = lm; R.s2.P = P; R.s2.nG = nG; R.s2.pad = 0;
-      R.s2.ilx = (double)(HS_S2_C / lx);  // (ln 2 / 1024) / lx
-      R.s2.th = (double)((long double)NH_SEG_SMALL_POS / lx);
-      R.s2.im = 1.0 / m;
-      R.s2.lml = (double)(m - 1) / m;
-      R.s2_invd = (double)(1.0L / (2.0L * lx));
-      // w = gamma n scale = (E / mec2[eV]) n scale != 0  <=>  ln n + ln E > ln(2^-1075) + ln(mec2 / scale)
-      R.s2_lnw0 = (double)(-1075.0L * logl(2.0L) + logl((long double)NH_MEC2_EV / (long double)H.scale[H.syn_grid]));
-      R.s2_z0 = (double)(((long double)HS_S2_TTOP + 2.0L * logl((long double)gam[0])) / (2.0L * lx));
-      R.s2_r746 = (double)(((long double)HS_S2_TTOP - logl(746.0L)) / (2.0L * lx) -
-                           ((long double)HS_S2_TTOP + 2.0L * logl((long double)gam[0])) / (2.0L * lx));
-      const int off_was = off, hole_was = hole_lo;  // (tentative: undone if it does not fit)
-      R.o_s2tab = take((P + 1) * HS_S2_STRIDE, true);  // (16-byte aligned: the pieces are read as ds_read_b128)
-      // the plan's LDS holds w | dlw of the synchrotron grid and 1/g^2 | its differences | its
-      // cube roots, none of which these items read: when no table and no single-row reduction
-      // shares the grid, the new arrays take their place (cfg3 with four workgroups per walker
-      // has 142 KB of partial sums and arrays before this table)
-      const int sg = H.syn_grid;
-      bool own = nG >= 2 * HS_S2_GUARD && H.o_d[sg] == H.o_w[sg] + nG && H.o_ig23 == H.o_dig2 + nG;
-      for (int t = 0; t < H.ntab; ++t) own = own && H.C.tab[t].grid != sg;
-      for (int q = 0; q < H.nmom; ++q) own = own && H.mgrid[q] != sg;
-      R.s2_own = own ? 1 : 0;
-      if (own) {
-        R.o_s2lw = H.o_w[sg];   // (w, dlw: 2 nG doubles in a row)
-        R.o_s2ig = H.o_dig2;    // (dig2, ig23: 2 nG doubles in a row)
-      } else {
-        R.o_s2lw = take(nG + 2 * HS_S2_GUARD, false);
-        R.o_s2ig = take(nG + 2 * HS_S2_GUARD, false);
-      }
-      if (own && grids_in_lds) {
-        R.o_s2lg = R.o_gx[sg];  // (gamma itself: only the weights w = gamma n read it)
-      } else {
-        R.o_s2lg = take(nG, false);
-      }
-      R.o_s2q = take(4 * H.syn_nE, false);
-      R.o_s2z = take((H.syn_nE + 1) / 2, false);
-      R.o_s2t = take(HS_S2_TN, false);
-      R.o_lnt = take(256, true);
-      if ((size_t)off * sizeof(double) <= 160 * 1024) {
-        R.syn2 = 1;
-      } else {
-        off = off_was;
-        hole_lo = hole_was;
-      }
-    }
+    if (!hs_read_grid(H.xg[H.syn_grid], H.nG[H.syn_grid], xg))
+      return nh_set_error(NH_EHIP, "resident half-step loop: the synchrotron grid could not be read");
   }
-  // (1 / lx of the table grids: optional -- where LDS has room behind everything else)
-  if (nh_env_int("NH_RUN_IL", 1) != 0)
-    for (int g = 0; g < H.ngrids; ++g)
-      if (H.o_dp[g] >= 0 && (hole_lo + H.nG[g] <= hole_hi || (size_t)(off + H.nG[g]) * sizeof(double) <= 158 * 1024))
-        R.o_il[g] = take(H.nG[g], false);
-  R.syn_nodes = H.C.syn_nodes;
-  if (P->split == 1 && R.syn_nodes < 32) R.syn_nodes = R.syn2 ? 48 : 32;
-  if (P->split == 2 && R.syn_nodes < 10) R.syn_nodes = 10;  // (cfg2: 901 -> 885 us; 914 at 16)
-  // (the log-domain items start on a piece boundary with a node and six coefficients of their
-  // own: short items pay for that -- cfg3 / 128, four workgroups per walker, us per half-step:
-  // 18.4 at the plan's 4 nodes, 16.9 at 16, 17.7 at 24, direct form 17.2; cfg3 / 256, two per
-  // walker: 20.8 at 10, 20.8 at 16, 20.0 at 24; cfg2 / 256: 17.7 at 10 and at 16, 18.3 at 24)
-  if (R.syn2 && P->split >= 2 && R.syn_nodes < 16) R.syn_nodes = 16;
-  R.syn_nodes = nh_env_int("NH_RUN_SYN_NODES", R.syn_nodes);
-  R.pipeline = nh_env_int("NH_RUN_PIPELINE", 1);
-  if (nh_env_int("NH_RUN_FAIL_AT", 0) > 0)
-    fprintf(stderr, "libnaima_hip: NH_RUN_FAIL_AT=%d -- that launch of the resident loop is made to time "
-                    "out (fault injection of the tests)\n", nh_env_int("NH_RUN_FAIL_AT", 0));
-  NH_REQUIRE(R.syn_nodes >= 1, "NH_RUN_SYN_NODES must be positive");
-  const size_t lds = (size_t)off * sizeof(double);
-  NH_REQUIRE(lds <= 160 * 1024, "the resident loop's working set does not fit in LDS");
-  const void* fn = hs_run_kernel(H.syn_grid >= 0, shared, R.syn2 != 0, rt);
+  // ---- 2. the plan (nh_hs_plan.h), the launch's grid from the occupancy of its instance ----
+  std::unique_ptr<nh_halfstep_run> Q(new nh_halfstep_run());
+  hs_run& R = Q->R;
+  hs_run_shape S;
+  int rc = hs_run_plan(P, shared, rank, nrank, k, xg.empty() ? nullptr : xg.data(), R, S);
+  if (rc != NH_OK) return rc;
+  const size_t lds = S.lds_bytes;
+  const void* fn = hs_run_kernel(H.syn_grid >= 0, shared, R.syn2 != 0, S.rt);
   if (lds > 64 * 1024)
     NH_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  // every workgroup of the launch has to be resident (they wait for each other's records)
-  int per_cu = 0, ncu = 0, devid = 0;
+  int per_cu = 0;
   NH_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, P->threads, lds));
-  NH_CHECK_HIP(hipGetDevice(&devid));
-  NH_CHECK_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, devid));
-  NH_REQUIRE(per_cu >= 1 && ncu >= 1, "the resident kernel does not fit a compute unit");
-  // (MI355X_MICROARCH.md: the query can be one block per CU high where the SGPR file is what
-  // limits residency -- 6 waves per SIMD at this kernel's ~110 SGPRs; its 128 VGPRs allow 4,
-  // so registers or LDS bind first and the query is exact.  The bounded waits are the net.)
-  {  // (ranks that rehearse a multi-GPU run on one device: a share of its CUs each, nh_halfstep.hip)
-    const int share = nh_env_int("NAIMA_AMD_CU_SHARE", 1);
-    if (share > 1) ncu = ncu / share > 1 ? ncu / share : 1;
-  }
-  long long cap = (long long)per_cu * ncu;
-  if (const char* e = getenv("NH_RUN_GRID")) cap = atoi(e) > 0 ? atoi(e) : cap;
-  // More walkers per half-step than resident workgroups: a workgroup takes several of a slice,
-  // one after the other (dependencies still point backwards in (slice, walker) order).  Pays for
-  // workgroups that own their CU -- cfg3 at 1024 / 2048 walkers: 7.8 / 8.1 M walker-steps/s
-  // launched per half-step, 10.9 / 11.2 M resident -- not for the small workgroups of a
-  // table-only model (cfg5 at 1024 walkers per half-step ran 19.6 M walker-steps/s with two
-  // walkers per workgroup and slice, two 256-thread workgroups per CU, against 24.2 M launched
-  // per half-step, four).  NH_RUN_MAX_PER_WG overrides (1: never).
-  const long long per_wg = nh_env_int("NH_RUN_MAX_PER_WG", P->threads >= 1024 ? 8 : 1);
-  NH_REQUIRE((long long)H.nloc * P->split <= cap * (per_wg > 1 ? per_wg : 1),
-             "more walkers per half-step than resident workgroups");
-  nh_halfstep_run* Q = new nh_halfstep_run();
-  Q->R = R;
-  Q->lds_bytes = lds;
-  Q->threads = P->threads;
-  Q->rt = rt ? 1 : 0;
-  Q->grid = (int)(H.nloc < cap / P->split ? H.nloc : cap / P->split);
-  // two walkers in flight (the DEEP instance): one GPU's loop whose workgroups own their CU, have
-  // the walker to themselves and take more than one of a slice -- a model with a synchrotron
-  // component (the 1024-thread instances; a table-only model's ensembles of that size run in small
-  // workgroups that share a CU, where the hardware overlaps them).  NH_RUN_PIPELINE=0: never.
-  // (With phase A alone made ahead cfg2 -- synchrotron items only, twenty of them for sixteen waves --
-  // measured 1 % slower and models without table items were left out; with the priors made ahead as
-  // well it gains like cfg3: cfg2 / 1024 13.61 -> 14.01 M, / 2048 14.01 -> 14.73 M.)
-  Q->deep = 0;
-  if (!shared && !rt && H.syn_grid >= 0 && P->split == 1 && P->threads >= 1024 && H.nloc > Q->grid &&
-      R.pipeline != 0) {
+  bool deep_candidate = false;
+  rc = hs_run_grid(P, shared, S.rt, R, k, per_cu, nh_cu_count(0), &Q->grid, &deep_candidate);
+  if (rc != NH_OK) return rc;
+  if (deep_candidate) {
     const void* fd = hs_run_kernel(H.syn_grid >= 0, false, R.syn2 != 0, false, true);
     int per_cu_d = 0;
     hipError_t ed = lds > 64 * 1024 ? hipFuncSetAttribute(fd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
@@ -2335,26 +1974,21 @@ static int hs_run_create(nh_ctx* c, nh_halfstep_plan* P, int rank, int nrank, nh
     if (ed == hipSuccess && per_cu_d >= per_cu) Q->deep = 1;  // (as resident as the instance the grid was sized for)
     else (void)hipGetLastError();
   }
+  Q->lds_bytes = lds;
+  Q->threads = P->threads;
+  Q->rt = S.rt ? 1 : 0;
   Q->seq = 1;
-  Q->ring = nullptr; Q->status = nullptr; Q->accw = nullptr; Q->dbg = nullptr;
-  Q->xspec = nullptr; Q->tick = nullptr; Q->split = P->split;
+  Q->split = P->split;
   Q->nrank = shared ? nrank : 1; Q->rank = shared ? rank : 0;
-  Q->base = nullptr; Q->nacc_own = nullptr; Q->curstamp = nullptr; Q->hacc = nullptr;
-  Q->probe_out = nullptr; Q->steps_total = 0; Q->probe_seq = 1; Q->s2_dev = nullptr;
-  Q->report = nullptr; Q->lcnt = nullptr; Q->nlaunch = 0; Q->fail_at = nh_env_int("NH_RUN_FAIL_AT", 0);
-  Q->R.report = nullptr;
-  for (int p = 0; p < HS_RUN_MAX_RANKS; ++p) Q->peer_base[p] = nullptr;
+  Q->probe_seq = 1;
+  Q->fail_at = k.run_fail_at;
   Q->ring_elems = (size_t)(HS_RUN_MAX_STEPS + 1) * R.N * R.gr;
+  // ---- 3. the loop's memory ----
+  nh_owned& m = Q->mem;
   const size_t ring_bytes = Q->ring_elems * sizeof(unsigned long long);
-  hipError_t e = hipSuccess;
   if (!shared) {  // (a shared ensemble's ranks agree on a launch's fate by other means)
-    void* rp = nullptr;
-    e = hipHostMalloc(&rp, 16 * sizeof(int), hipHostMallocDefault);
-    if (e == hipSuccess) {
-      Q->report = static_cast<int*>(rp);
-      memset(Q->report, 0, 16 * sizeof(int));
-      Q->R.report = Q->report;
-    }
+    Q->report = m.host<int>(16 * sizeof(int));
+    if (Q->report) memset(Q->report, 0, 16 * sizeof(int));
   }
   if (shared) {
     // Fine-grained device memory: what another GPU stores into it over xGMI is visible to a
@@ -2362,77 +1996,60 @@ static int hs_run_create(nh_ctx* c, nh_halfstep_plan* P, int rank, int nrank, nh
     // from an L2 that the incoming writes never pass (coarse-grained memory is coherent with
     // other agents at kernel boundaries only).  NH_RUN_SHARED_ALLOC = 1 fine-grained (default) |
     // 2 uncached | 0 plain hipMalloc (two processes on ONE GPU: same memory, same L2s).
+    // (`ring` stays NULL here: a launch points it into `base`, which owns the memory)
     Q->base_bytes = HS_RUN_HEAD * sizeof(unsigned long long) + 2 * ring_bytes;
-    const int how = nh_env_int("NH_RUN_SHARED_ALLOC", 1);
-    void* b = nullptr;
-    if (how == 0) e = hipMalloc(&b, Q->base_bytes);
-    else e = hipExtMallocWithFlags(&b, Q->base_bytes, how == 2 ? hipDeviceMallocUncached : hipDeviceMallocFinegrained);
-    Q->base = static_cast<unsigned long long*>(b);
-    if (e == hipSuccess) e = nh_fill_now(c, Q->base, 0, Q->base_bytes);
+    const int how = k.run_shared_alloc;
+    Q->base = how == 0 ? m.dev<unsigned long long>(Q->base_bytes)
+                       : m.dev_with_flags<unsigned long long>(
+                             Q->base_bytes, how == 2 ? hipDeviceMallocUncached : hipDeviceMallocFinegrained);
+    m.fill(c, Q->base, 0, Q->base_bytes);
     Q->peer_base[Q->rank] = Q->base;
-    if (e == hipSuccess) e = hipMalloc(&Q->nacc_own, (size_t)R.N * sizeof(int));
-    if (e == hipSuccess) e = nh_fill_now(c, Q->nacc_own, 0, (size_t)R.N * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&Q->curstamp, (size_t)R.N * sizeof(int));
-    if (e == hipSuccess) e = nh_fill_now(c, Q->curstamp, 0xFF, (size_t)R.N * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&Q->probe_out, (4 + HS_RUN_MAX_RANKS) * sizeof(int));
+    Q->nacc_own = m.dev<int>((size_t)R.N * sizeof(int));
+    m.fill(c, Q->nacc_own, 0, (size_t)R.N * sizeof(int));
+    Q->curstamp = m.dev<int>((size_t)R.N * sizeof(int));
+    m.fill(c, Q->curstamp, 0xFF, (size_t)R.N * sizeof(int));
+    Q->probe_out = m.dev<int>((4 + HS_RUN_MAX_RANKS) * sizeof(int));
   } else {
-    if (e == hipSuccess) e = hipMalloc(&Q->ring, ring_bytes);
-    if (e == hipSuccess) e = nh_fill_now(c, Q->ring, 0, ring_bytes);
+    Q->ring = m.dev<unsigned long long>(ring_bytes);
+    m.fill(c, Q->ring, 0, ring_bytes);
   }
-  if (e == hipSuccess && R.syn2) {
-    e = hipMalloc(&Q->s2_dev, s2_host.size() * sizeof(double));
-    if (e == hipSuccess)
-      e = nh_put_now(c, Q->s2_dev, s2_host.data(), s2_host.size() * sizeof(double));
+  if (R.syn2) {
+    Q->s2_dev = m.dev<double>(S.s2.data.size() * sizeof(double));
+    m.put(c, Q->s2_dev, S.s2.data.data(), S.s2.data.size() * sizeof(double));
   }
-  if (e == hipSuccess) e = hipMalloc(&Q->lcnt, 4 * sizeof(int));
-  if (e == hipSuccess) e = nh_fill_now(c, Q->lcnt, 0, 4 * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc(&Q->status, sizeof(int));
-  if (e == hipSuccess) e = nh_fill_now(c, Q->status, 0, sizeof(int));
-  if (e == hipSuccess) e = hipMalloc(&Q->accw, (size_t)HS_RUN_MAX_STEPS * R.N * sizeof(int));
-  if (e == hipSuccess) e = nh_fill_now(c, Q->accw, 0, (size_t)HS_RUN_MAX_STEPS * R.N * sizeof(int));
-  if (e == hipSuccess && P->split > 1) {
+  Q->lcnt = m.dev<int>(4 * sizeof(int));
+  m.fill(c, Q->lcnt, 0, 4 * sizeof(int));
+  Q->status = m.dev<int>(sizeof(int));
+  m.fill(c, Q->status, 0, sizeof(int));
+  Q->accw = m.dev<int>((size_t)HS_RUN_MAX_STEPS * R.N * sizeof(int));
+  m.fill(c, Q->accw, 0, (size_t)HS_RUN_MAX_STEPS * R.N * sizeof(int));
+  if (P->split > 1) {
     // per (slice, walker): what workgroups 1 .. K - 1 hand over, two tagged granules per double
     // (no clearing between launches: the tags carry the launch's number)
-    const size_t cellw = (size_t)(P->split - 1) * 2 * Q->R.nxmax;
-    e = hipMalloc(&Q->xspec, (size_t)2 * HS_RUN_MAX_STEPS * H.nloc * cellw * sizeof(unsigned long long));
-    if (e == hipSuccess)
-      e = nh_fill_now(c, Q->xspec, 0, (size_t)2 * HS_RUN_MAX_STEPS * H.nloc * cellw * sizeof(unsigned long long));
+    const size_t cellw = (size_t)(P->split - 1) * 2 * R.nxmax;
+    const size_t xbytes = (size_t)2 * HS_RUN_MAX_STEPS * H.nloc * cellw * sizeof(unsigned long long);
+    Q->xspec = m.dev<double>(xbytes);
+    m.fill(c, Q->xspec, 0, xbytes);
   }
-  if (e == hipSuccess)
-    if (const char* dv = getenv("NH_HS_DEBUG"))
-      if (atoi(dv) != 0) {
-        e = hipMalloc(&Q->dbg, (256 * 64 * 8 + 64 * 4 * 16) * sizeof(long long));
-        if (e == hipSuccess) e = nh_fill_now(c, Q->dbg, 0, (256 * 64 * 8 + 64 * 4 * 16) * sizeof(long long));
-      }
-  if (e != hipSuccess) {
-    if (Q->ring) (void)hipFree(Q->ring);
-    if (Q->base) (void)hipFree(Q->base);
-    if (Q->nacc_own) (void)hipFree(Q->nacc_own);
-    if (Q->curstamp) (void)hipFree(Q->curstamp);
-    if (Q->probe_out) (void)hipFree(Q->probe_out);
-    if (Q->status) (void)hipFree(Q->status);
-    if (Q->lcnt) (void)hipFree(Q->lcnt);
-    if (Q->accw) (void)hipFree(Q->accw);
-    if (Q->dbg) (void)hipFree(Q->dbg);
-    if (Q->xspec) (void)hipFree(Q->xspec);
-    if (Q->tick) (void)hipFree(Q->tick);
-    if (Q->s2_dev) (void)hipFree(Q->s2_dev);
-    if (Q->report) (void)hipHostFree(Q->report);
-    delete Q;
-    return nh_set_error(NH_EHIP, "resident half-step loop: %s", hipGetErrorString(e));
+  if (k.debug) {
+    Q->dbg = m.dev<long long>((256 * 64 * 8 + 64 * 4 * 16) * sizeof(long long));
+    m.fill(c, Q->dbg, 0, (256 * 64 * 8 + 64 * 4 * 16) * sizeof(long long));
   }
-  Q->R.ring = Q->ring; Q->R.status = Q->status; Q->R.accw = Q->accw; Q->R.dbg = Q->dbg;
-  Q->R.xspec = Q->xspec; Q->R.tick = Q->tick; Q->R.s2_dev = Q->s2_dev;
-  Q->R.clk = c->clk;
-  Q->R.spin_limit = 1 << 22;  // ~1 s of polling: a record that has not come by then never will
+  if (!m.ok()) return nh_set_error(NH_EHIP, "resident half-step loop: %s", hipGetErrorString(m.err));
+  // ---- 4. publish ----
+  R.report = Q->report;
+  R.ring = Q->ring; R.status = Q->status; R.accw = Q->accw; R.dbg = Q->dbg;
+  R.xspec = Q->xspec; R.s2_dev = Q->s2_dev;
+  R.clk = c->clk;
+  R.spin_limit = 1 << 22;  // ~1 s of polling: a record that has not come by then never will
   // (a shared ensemble: the ranks' hosts launch on their own clocks; a rank may have to wait for
   // another one's launch to START -- ~16 s)
-  if (shared) Q->R.spin_limit = 1 << 26;
-  if (const char* sl = getenv("NH_RUN_SPIN_LIMIT")) Q->R.spin_limit = atoi(sl) > 0 ? atoi(sl) : Q->R.spin_limit;
-  Q->R.nrank = Q->nrank; Q->R.rank = Q->rank;
-  Q->R.publish_delay = shared ? nh_env_int("NH_RUN_PUBLISH_DELAY", 0) : 0;
-  Q->R.nacc_own = Q->nacc_own; Q->R.curstamp = Q->curstamp;
-  *out = Q;
+  if (shared) R.spin_limit = 1 << 26;
+  if (k.run_spin_limit.set) R.spin_limit = k.run_spin_limit.v > 0 ? k.run_spin_limit.v : R.spin_limit;
+  R.nrank = Q->nrank; R.rank = Q->rank;
+  R.publish_delay = shared ? k.run_publish_delay : 0;
+  R.nacc_own = Q->nacc_own; R.curstamp = Q->curstamp;
+  *out = Q.release();
   return NH_OK;
 }
 
@@ -2797,19 +2414,6 @@ extern "C" int nh_half_step_run_destroy(nh_ctx* c, nh_halfstep_run* Q) {
   int rc = nh_sync(c);
   for (int p = 0; p < HS_RUN_MAX_RANKS; ++p)
     if (Q->base && p != Q->rank && Q->peer_base[p]) (void)hipIpcCloseMemHandle(Q->peer_base[p]);
-  if (Q->base) (void)hipFree(Q->base);
-  else if (Q->ring) (void)hipFree(Q->ring);
-  if (Q->nacc_own) (void)hipFree(Q->nacc_own);
-  if (Q->curstamp) (void)hipFree(Q->curstamp);
-  if (Q->probe_out) (void)hipFree(Q->probe_out);
-  if (Q->status) (void)hipFree(Q->status);
-  if (Q->lcnt) (void)hipFree(Q->lcnt);
-  if (Q->accw) (void)hipFree(Q->accw);
-  if (Q->dbg) (void)hipFree(Q->dbg);
-  if (Q->xspec) (void)hipFree(Q->xspec);
-  if (Q->tick) (void)hipFree(Q->tick);
-  if (Q->s2_dev) (void)hipFree(Q->s2_dev);
-  if (Q->report) (void)hipHostFree(Q->report);
-  delete Q;
+  delete Q;  // (its own memory goes with it: nh_owned)
   return rc;
 }

@@ -244,15 +244,18 @@ static inline void hs_s2_piece(int p, long double h, double* c /*[HS_S2_STRIDE]*
 // What a kernel needs to run hs_syn2_item on a log-uniform grid (radiative.py:147-154 makes it
 // one): the table's pieces followed by Lambda (ln gamma_i / 3 + ln scale) per node, and the comb's
 // constants.  false: the grid is not log-uniform to 1e-12 (or too coarse / too fine for pieces of
-// 2 .. 16 steps): the direct form stays.  (k_half_step's plan; the resident loop's creation holds
-// the same steps.)
+// 2 .. 16 steps): the direct form stays.  min_nodes: the smallest grid the caller can run (k_half_step
+// keeps the guards inside the grid's own arrays: 2 HS_S2_GUARD; the resident loop: 8).
 struct hs_s2_host {
   hs_syn2_par par;
   double invd, z0;           // 1 / (2 lx);  (T_top + 2 ln gamma_0) / (2 lx)
+  // the resident loop's: (T_top - ln 746) invd - z0 (the first live node is ceil(ln(q) invd + this));
+  // ln |n| + ln(E / eV) above lnw0: the weight gamma n scale is not 0 in double
+  double r746, lnw0;
   std::vector<double> data;  // (P + 1) HS_S2_STRIDE table entries | nG node constants
 };
-static inline bool hs_s2_prepare(const double* gam, int nG, double scale, hs_s2_host& o) {
-  bool ok = nG >= 2 * HS_S2_GUARD && gam[0] > 0.0 && scale > 0.0;
+static inline bool hs_s2_prepare(const double* gam, int nG, double scale, int min_nodes, hs_s2_host& o) {
+  bool ok = nG >= min_nodes && gam[0] > 0.0 && scale > 0.0;
   long double lx = 0.0L, dev = 0.0L;
   if (ok) {
     const long double l0 = logl((long double)gam[0]);
@@ -261,12 +264,14 @@ static inline bool hs_s2_prepare(const double* gam, int nG, double scale, hs_s2_
       ok = gam[i] > 0.0;
       if (ok) dev = fmaxl(dev, fabsl(logl((long double)gam[i]) - l0 - i * lx));
     }
+    // (np.logspace, radiative.py:147-154: the nodes sit on i lx to a few 1e-15; 1e-12 in ln gamma
+    // is 7e-13 in ln Gtilde)
     ok = ok && lx > 0.0L && dev <= 1e-12L;
   }
   int lm = 0;
   if (ok) {
     lm = (int)lrint(log2(0.16 / (double)(2.0L * lx)));
-    ok = lm >= 1 && lm <= 4;
+    ok = lm >= 1 && lm <= 4;  // pieces of m = 2 .. 16 comb steps, h = m delta in [0.113, 0.226]
   }
   if (!ok) return false;
   const int m = 1 << lm;
@@ -274,6 +279,7 @@ static inline bool hs_s2_prepare(const double* gam, int nG, double scale, hs_s2_
   const int P = (int)ceill(((long double)HS_S2_TTOP - (long double)HS_S2_TBOT) / h);
   o.data.assign((size_t)(P + 1) * HS_S2_STRIDE + nG, 0.0);
   for (int pc = 0; pc < P; ++pc) hs_s2_piece(pc, h, &o.data[(size_t)pc * HS_S2_STRIDE]);
+  // (piece P, and every node below the table: rho = 0, i.e. Gtilde = 1.808 x^(1/3))
   o.data[(size_t)P * HS_S2_STRIDE] = (double)((long double)HS_S2_LAMBDA * logl(1.808L));
   for (int i = 0; i < nG; ++i)
     o.data[(size_t)(P + 1) * HS_S2_STRIDE + i] =
@@ -285,5 +291,9 @@ static inline bool hs_s2_prepare(const double* gam, int nG, double scale, hs_s2_
   o.par.lml = (double)(m - 1) / m;
   o.invd = (double)(1.0L / (2.0L * lx));
   o.z0 = (double)(((long double)HS_S2_TTOP + 2.0L * logl((long double)gam[0])) / (2.0L * lx));
+  // w = gamma n scale = (E / mec2[eV]) n scale != 0  <=>  ln n + ln E > ln(2^-1075) + ln(mec2 / scale)
+  o.lnw0 = (double)(-1075.0L * logl(2.0L) + logl((long double)NH_MEC2_EV / (long double)scale));
+  o.r746 = (double)(((long double)HS_S2_TTOP - logl(746.0L)) / (2.0L * lx) -
+                    ((long double)HS_S2_TTOP + 2.0L * logl((long double)gam[0])) / (2.0L * lx));
   return true;
 }
