@@ -998,6 +998,50 @@ int nh_psis_columns(nh_ctx* ctx, const double* L, long long M, int ncol, long lo
                     const double* stats, const double* lsel, double* pareto_k, long long* n_tail,
                     double* elpd);
 
+/* ---- rank-normalised convergence statistics: the rank transform of whole pooled columns ------
+ * What scipy.stats.rankdata(method="average"), scipy.special.ndtri on Blom's plotting positions
+ * and two elementwise NumPy expressions compute on the host for the rank-normalised, folded
+ * split-R-hat and the bulk / tail effective sample sizes of Vehtari, Gelman, Simpson, Carpenter &
+ * Buerkner 2021.  x is a row-major DEVICE matrix [rows][ld].  A POOLED column p < ncolp holds
+ * S = nrows * npool values, element e = t * npool + j being x[(row0 + t) * ld + j * cstride + p]:
+ * a plain matrix [M][ncol] is row0 = 0, nrows = M, npool = 1, ncolp = ncol; a chain
+ * [rows][walker][parameter] behind `discard` rows, every walker's values of a parameter pooled
+ * (chain[discard:, :, p].ravel()), is row0 = discard, cstride = ndim, npool = walkers,
+ * ncolp = ndim.  No pooled copy is made.  Stream-ordered on the context's stream, no host
+ * synchronisation, 64-bit indices.  Deterministic and bit-reproducible from call to call: integer
+ * atomics only (digit histograms in LDS, the status count), the scatter of the sort takes its
+ * offsets from wave ballots.
+ * Every entry point: NH_EINVAL for a null argument, row0 < 0, nrows, npool or ncolp < 1,
+ *   cstride < ncolp with npool > 1, (npool - 1) * cstride + ncolp > ld (or ldz, ldo),
+ *   nrows * npool >= 2^31.
+ * nh_rank_columns: r (DEVICE [S][ncolp], the pooled layout) = the 1-based average ranks within
+ *   each pooled column: equal values share the mean of the positions they occupy; -0.0 and +0.0
+ *   are equal.  A pooled column that holds any NaN or +-inf is NaN in every row, and status
+ *   (DEVICE int32 [ncolp]) counts its non-finite values (0 for a ranked column): no partial
+ *   ranking.  A least-significant-digit radix sort of (64-bit key, row index), eight 8-bit
+ *   passes.  Library scratch of 16 * S bytes per pooled column + a little; above 256 MiB the
+ *   pooled columns are ranked in groups (NAIMA_AMD_RANK_SCRATCH_KIB, read at every call, sets
+ *   another budget).
+ * nh_rank_normal_scores: z = Phi^-1((r - 3/8) / (S + 1/4)) for every rank of r (DEVICE
+ *   [S][ncolp], nh_rank_columns' output), S = nrows * npool; NaN in, NaN out.  layout =
+ *   NH_RANK_POOLED: z is [S][ncolp] (ldz, cstride unused); NH_RANK_CHAIN: element e = t * npool + j
+ *   of column p goes to z[t * ldz + j * cstride + p], the chain's layout with its rows starting
+ *   at 0 -- what nh_group_moments and nh_autocorr_prep take.  Phi^-1 is Wichura's AS 241 PPND16
+ *   in FP64 (a rational in the centre, two tail branches in sqrt(-log p)), applied to the
+ *   correctly rounded quotient; accurate for the arguments ranks give, S <= 2^24.
+ * nh_rank_transform: out[t * ldo + j * cstride + p] (the chain's layout, rows from 0) =
+ *   |x - thr[p]| for mode NH_RANK_FOLD, (x <= thr[p] ? 1 : 0) for NH_RANK_LE, thr a DEVICE
+ *   [ncolp]; NaN where x (or, for NH_RANK_LE, thr[p]) is NaN.  NH_EINVAL also: another mode. */
+enum { NH_RANK_POOLED = 0, NH_RANK_CHAIN = 1 };
+enum { NH_RANK_FOLD = 0, NH_RANK_LE = 1 };
+int nh_rank_columns(nh_ctx* ctx, const double* x, long long row0, long long nrows, long long ld,
+                    long long cstride, int npool, int ncolp, double* r, int* status);
+int nh_rank_normal_scores(nh_ctx* ctx, const double* r, long long nrows, int npool, int ncolp,
+                          int layout, long long ldz, long long cstride, double* z);
+int nh_rank_transform(nh_ctx* ctx, const double* x, long long row0, long long nrows, long long ld,
+                      long long cstride, int npool, int ncolp, const double* thr, int mode,
+                      double* out, long long ldo);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,8 @@ NH_PD_NPAR = 8
 NH_EBL_ONE, NH_EBL_HIGH, NH_EBL_OUTSIDE = 1, 2, 4  # nh_ebl_table's per-energy codes
 # nh_hist_columns' caps (include/naima_hip.h)
 NH_HIST_MAX_COLS, NH_HIST_MAX_PAIRS, NH_HIST_MAX_BINS_1D, NH_HIST_MAX_BINS_2D = 32, 496, 4096, 100
+NH_RANK_POOLED, NH_RANK_CHAIN = 0, 1   # nh_rank_normal_scores' layouts
+NH_RANK_FOLD, NH_RANK_LE = 0, 1        # nh_rank_transform's modes
 NH_PSIS_MAX_TAIL = 4096  # nh_psis_columns' cap on the tail length (include/naima_hip.h)
 NH_K_NAMES = ("particle_weights", "integrate_tables", "synchrotron", "tables", "lnprob",
               "ic_seed_walkers", "glue", "integrate_rows", "half_step")
@@ -173,6 +175,9 @@ _SIGS = {
     "nh_pointwise_lnl": [_dp, _dp, _ll, _i, _ll, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ll, _dp, _dp],
     "nh_lnl_column_stats": [_dp, _dp, _ll, _i, _ll, _dp],
     "nh_psis_columns": [_dp, _dp, _ll, _i, _ll, _i, _dp, _dp, _dp, _dp, _dp],
+    "nh_rank_columns": [_dp, _dp, _ll, _ll, _ll, _ll, _i, _i, _dp, _dp],
+    "nh_rank_normal_scores": [_dp, _dp, _ll, _i, _i, _i, _ll, _ll, _dp],
+    "nh_rank_transform": [_dp, _dp, _ll, _ll, _ll, _ll, _i, _i, _dp, _i, _dp, _ll],
 }
 EXPORTS = tuple(_SIGS) + ("nh_last_error", "nh_version", "nh_ssc_table_bytes")
 

@@ -183,6 +183,18 @@ class _Result(InfoCritMixin):
             out.append(a.reshape((-1,) + a.shape[2:]) if flat else a)
         return out
 
+    def get_ess(self, kind="bulk", discard=0, thin=1):
+        """``EnsembleSampler.get_ess`` of the saved chain"""
+        from .posterior import _check_kind, ess
+        _check_kind(kind)
+        return ess(self.get_chain(discard=discard, thin=thin), kind)
+
+    def get_summary(self, discard=0):
+        """``EnsembleSampler.get_summary`` of the saved chain (its ensembles from ``run_info``)"""
+        from .posterior import summary
+        return summary(self.get_chain(discard=discard), int(self.run_info.get("ensembles", 1)),
+                       labels=self.labels or None)
+
     @property
     def chain(self):
         return np.swapaxes(self._chain, 0, 1)
@@ -328,7 +340,7 @@ def save_diagnostic_plots(outname, sampler, modelidxs=None, pdf=False, sed=True,
 
 
 def save_results_table(outname, sampler, convert_log=True, last_step=False, include_blobs=True,
-                       overwrite=False, information_criteria=False):
+                       overwrite=False, information_criteria=False, diagnostics=False):
     """Write ``<outname>_results.ecsv``: median and 16th/84th-percentile distances of every
     parameter (plus the de-logged value for ``log10(x)`` / ``log(x)`` labels and every
     scalar blob), with the run information, the most probable parameters and the BIC as
@@ -336,7 +348,9 @@ def save_results_table(outname, sampler, convert_log=True, last_step=False, incl
     available).  ``information_criteria=True`` adds ``WAIC_elpd``, ``WAIC_p``, ``LOO_elpd``,
     ``LOO_p``, ``LOO_se`` and ``LOO_max_pareto_k`` of the whole chain's stored spectra (blob 0,
     ``naima_amd.infocrit``, computed on the GPU) to the metadata; without it the file is what it
-    always was.  Returns the table as a dict of columns + ``meta``."""
+    always was.  ``diagnostics=True`` adds ``ESS_bulk`` and ``ESS_tail`` per parameter and, for a
+    run of several ensembles, ``Rhat_rank`` (``posterior.summary`` of the whole chain, ranked on
+    the GPU).  Returns the table as a dict of columns + ``meta``."""
     import os
 
     import yaml
@@ -372,6 +386,14 @@ def save_results_table(outname, sampler, convert_log=True, last_step=False, incl
         meta["WAIC_elpd"], meta["WAIC_p"] = w["elpd_waic"], w["p_waic"]
         meta["LOO_elpd"], meta["LOO_p"], meta["LOO_se"] = lo["elpd_loo"], lo["p_loo"], lo["se"]
         meta["LOO_max_pareto_k"] = float(np.max(lo["pareto_k"]))
+    if diagnostics:
+        from .posterior import summary
+        k = int(getattr(sampler, "run_info", {}).get("ensembles", getattr(sampler, "ensembles", 1)))
+        sm = summary(chain, k)
+        meta["ESS_bulk"] = [float(v) for v in sm["ess_bulk"]]
+        meta["ESS_tail"] = [float(v) for v in sm["ess_tail"]]
+        if k > 1:
+            meta["Rhat_rank"] = [float(v) for v in sm["rhat_rank"]]
     for k, v in dict(getattr(sampler, "run_info", {})).items():
         meta[k] = v.tolist() if isinstance(v, np.ndarray) else (v.item() if isinstance(
             v, np.generic) else v)

@@ -16,6 +16,12 @@ device matrix: a ``plot._Samples``, or ``(DeviceArray, M, ncol, ld)``.
 pools the ensemble's walkers into one sequence and returns its count, mean and variance
 (``nh_group_moments``); the Gelman-Rubin formula over those ``m * ndim`` moments is host arithmetic.
 
+``rank_columns``, ``rank_normalize``, ``rhat(method="rank")``, ``ess`` and ``summary`` are the
+rank-normalised statistics of Vehtari et al. 2021: every pooled column of a chain is ranked on the
+device (``nh_rank_columns``: average ranks from a radix sort), the ranks become normal scores
+(``nh_rank_normal_scores``), and the moments and autocorrelation kernels read those exactly as they
+read a chain.
+
 Importing this module creates no GPU context; argument errors come before any device work.
 matplotlib is imported by ``corner`` only.
 """
@@ -27,7 +33,8 @@ from ._lib import (NH_HIST_MAX_BINS_1D, NH_HIST_MAX_BINS_2D, NH_HIST_MAX_COLS,
                    NH_HIST_MAX_PAIRS)
 
 __all__ = ["column_stats", "histogram", "histogram_pairs", "gaussian_kde", "contour_thresholds",
-           "corner", "DEFAULT_LEVELS", "group_moments", "rhat", "rhat_from_moments"]
+           "corner", "DEFAULT_LEVELS", "group_moments", "rhat", "rhat_from_moments",
+           "rank_columns", "rank_normalize", "ess", "summary"]
 
 # the mass of a 2-D Gaussian inside 0.5, 1, 1.5 and 2 sigma (corner's default contours)
 DEFAULT_LEVELS = tuple(1.0 - np.exp(-0.5 * np.array([0.5, 1.0, 1.5, 2.0]) ** 2))
@@ -324,15 +331,42 @@ def rhat_from_moments(count, mean, var, draws):
     return r
 
 
-def rhat(x, ensembles, discard=0, split=True):
+def rhat(x, ensembles, discard=0, split=True, method="moments", folded=True):
     """Gelman-Rubin R-hat per parameter of a chain of ``ensembles`` >= 2 independent ensembles
     (``x`` as ``group_moments`` takes it).  The walkers of ONE ensemble are not independent chains
     -- every proposal is built from another walker of it -- so each ensemble is pooled into one
     sequence; ``split=True`` cuts each into its first and second half (split-R-hat, which also
     sees a drift within the run), giving m = 2 k sequences, else m = k.  Every sequence has
     L = (rows per part) x (walkers of an ensemble) draws; the formula is ``rhat_from_moments``'s.
-    Only the m x ndim moments come to the host."""
-    gm = group_moments(x, ensembles, discard, 2 if split else 1)
+    Only the m x ndim moments come to the host.
+
+    ``method="rank"`` is the statistic the threshold 1.01 of Vehtari et al. 2021 is defined for:
+    the same pooling, ``split`` and formula applied to the rank-normalised scores ``z`` of the
+    chain (``rank_normalize``) and, with ``folded=True``, to those of ``|x - median|`` (the median
+    over a parameter's pooled values), the larger of the two per parameter.  The first is blind
+    to neither heavy tails nor infinite variances, the second sees ensembles that agree in
+    location and differ in scale.  NaN for a parameter with a non-finite value.  ``folded`` has no
+    meaning for ``method="moments"``."""
+    _check_method(method)
+    nsplit = 2 if split else 1
+    if method == "moments":
+        return _rhat_moments(x, ensembles, discard, nsplit)
+    rows, nw, ndim, k, _ = _chain_shape(x, ensembles, discard, nsplit)
+    pool = _pool_chain(x, discard)
+    out = _rhat_moments((_z_chain(pool), pool.nrows, nw, ndim), k, 0, nsplit)
+    if folded:
+        out = np.maximum(out, _rhat_moments((_z_chain(_folded(pool)), pool.nrows, nw, ndim), k, 0,
+                                            nsplit))
+    return out
+
+
+def _check_method(method):
+    if method not in ("moments", "rank"):
+        raise ValueError("method must be 'moments' or 'rank', not %r" % (method,))
+
+
+def _rhat_moments(x, ensembles, discard, nsplit):
+    gm = group_moments(x, ensembles, discard, nsplit)
     m = gm["n"].shape[0] * gm["n"].shape[1]
     return rhat_from_moments(gm["n"].reshape(m, -1), gm["mean"].reshape(m, -1),
                              gm["var"].reshape(m, -1), gm["draws"])
@@ -348,6 +382,264 @@ def _quantiles(s, q):
     v = column_select(s, list(lo) + list(hi))
     a, b = v[:len(lo)], v[len(lo):]
     return a + (b - a) * (pos - lo)[:, np.newaxis]
+
+
+# ---------------------------------------------------------------------------------------
+# rank-normalised statistics (Vehtari, Gelman, Simpson, Carpenter & Buerkner 2021)
+# ---------------------------------------------------------------------------------------
+class _Pool:
+    """pooled columns of a device matrix as nh_rank_columns takes them: element t * npool + j of
+    column p is x[(row0 + t) * ld + j * cstride + p]; ``owner`` keeps the buffer alive"""
+    __slots__ = ("ctx", "ptr", "owner", "row0", "nrows", "ld", "cstride", "npool", "ncolp")
+
+    def __init__(self, ctx, ptr, owner, row0, nrows, ld, cstride, npool, ncolp):
+        self.ctx, self.ptr, self.owner = ctx, ptr, owner
+        self.row0, self.nrows, self.ld = int(row0), int(nrows), int(ld)
+        self.cstride, self.npool, self.ncolp = int(cstride), int(npool), int(ncolp)
+
+    @property
+    def S(self):
+        return self.nrows * self.npool
+
+    def args(self):
+        return (self.ptr, self.row0, self.nrows, self.ld, self.cstride, self.npool, self.ncolp)
+
+    def flat(self):
+        """the pooled columns as the columns of a plot._Samples: rows behind row0; a chain whose
+        rows are exactly [walker][parameter] is the matrix [rows * walkers][parameters]"""
+        from .plot import _Samples
+        assert self.npool == 1 or (self.cstride == self.ncolp and self.ld == self.npool * self.ncolp)
+        ld = self.ld if self.npool == 1 else self.ncolp
+        return _Samples(self.ctx, self.ptr + 8 * self.row0 * self.ld, self.S, self.ncolp, ld,
+                        self.owner)
+
+
+def _is_chain_tuple(x):
+    return isinstance(x, tuple) and len(x) == 4 and hasattr(x[0], "ptr")
+
+
+def _chain_dims(x, discard, least=1):
+    """(rows, nwalkers, ndim) of a host chain or of a device block ``(DeviceArray, rows, nwalkers,
+    ndim)``, with at least ``least`` rows behind ``discard``; checked without a device"""
+    if isinstance(x, tuple):
+        if not _is_chain_tuple(x):
+            raise ValueError("a device chain is (DeviceArray, rows, nwalkers, ndim)")
+        rows, nw, ndim = (int(v) for v in x[1:])
+        if rows < 0 or nw < 1 or ndim < 1 or rows * nw * ndim * 8 > x[0].nbytes:
+            raise ValueError("a device chain of %d x %d x %d does not fit its buffer"
+                             % (rows, nw, ndim))
+    else:
+        shape = np.shape(x)
+        if len(shape) != 3:
+            raise ValueError("a chain must be (rows, nwalkers, ndim)")
+        rows, nw, ndim = shape
+        if nw < 1 or ndim < 1:
+            raise ValueError("the chain has no walkers or no parameters")
+    discard = int(discard)
+    if discard < 0:
+        raise ValueError("discard must not be negative")
+    if rows - discard < least:
+        raise ValueError("%d rows behind discard = %d: %d needed at least"
+                         % (max(0, rows - discard), discard, least))
+    return rows, nw, ndim
+
+
+def _pool_chain(x, discard=0):
+    """the parameters of a chain, every walker pooled, behind ``discard`` rows"""
+    from . import _lib
+    rows, nw, ndim = _chain_dims(x, discard)
+    if isinstance(x, tuple):
+        buf = x[0]
+        ctx = buf.ctx
+    else:
+        ctx = _lib.get_context()
+        buf = ctx.array(np.ascontiguousarray(x, dtype=np.float64).reshape(rows, nw * ndim))
+    return _Pool(ctx, buf.ptr, buf, int(discard), rows - int(discard), nw * ndim, ndim, nw, ndim)
+
+
+def _pool_any(x, discard=0):
+    """(pool, shape of the result): a chain (3-D host array), else a matrix as ``_matrix`` takes it"""
+    if not isinstance(x, tuple) and not hasattr(x, "ncol") and len(np.shape(x)) == 3:
+        pool = _pool_chain(x, discard)
+        return pool, (pool.nrows, pool.npool, pool.ncolp)
+    M, ncol = _shape(x)
+    discard = int(discard)
+    if discard < 0:
+        raise ValueError("discard must not be negative")
+    if M - discard < 1:
+        raise ValueError("no samples behind discard = %d" % discard)
+    s = _matrix(x)
+    return (_Pool(s.ctx, s.ptr, s, discard, s.M - discard, s.ld, 0, 1, s.ncol),
+            (s.M - discard, s.ncol))
+
+
+def _ranks(pool):
+    """(r [S][ncolp], status int32 [ncolp]) on the device"""
+    ctx = pool.ctx
+    r, status = ctx.empty((pool.S, pool.ncolp)), ctx.empty((pool.ncolp,), np.int32)
+    ctx.call("nh_rank_columns", *pool.args(), r, status)
+    return r, status
+
+
+def _z_chain(pool):
+    """the normal scores of the pooled ranks in the chain's layout, [nrows][npool * ncolp]"""
+    from ._lib import NH_RANK_CHAIN
+    ctx = pool.ctx
+    r, _ = _ranks(pool)
+    z = ctx.empty((pool.nrows, pool.npool * pool.ncolp))
+    ctx.call("nh_rank_normal_scores", r, pool.nrows, pool.npool, pool.ncolp, NH_RANK_CHAIN,
+             pool.npool * pool.ncolp, pool.ncolp, z)
+    return z
+
+
+def _transformed(pool, thr, mode):
+    """the chain-layout block [nrows][npool * ncolp] of |x - thr| or x <= thr, as a pool"""
+    ctx = pool.ctx
+    ld = pool.npool * pool.ncolp
+    out = ctx.empty((pool.nrows, ld))
+    ctx.call("nh_rank_transform", *pool.args(), ctx.array(np.ascontiguousarray(thr, dtype=float)),
+             mode, out, ld)
+    return _Pool(ctx, out.ptr, out, 0, pool.nrows, ld, pool.ncolp, pool.npool, pool.ncolp)
+
+
+def _median(pool):
+    """np.median of every pooled column: the mean of the two middle order statistics"""
+    from .plot import column_select
+    S = pool.S
+    v = column_select(pool.flat(), [(S - 1) // 2, S // 2])
+    return 0.5 * (v[0] + v[1])
+
+
+def _folded(pool):
+    from ._lib import NH_RANK_FOLD
+    return _transformed(pool, _median(pool), NH_RANK_FOLD)
+
+
+def rank_columns(x, discard=0, device=False):
+    """``scipy.stats.rankdata(col, method="average")`` of every column of ``x``, ranked on the GPU
+    (``nh_rank_columns``): 1-based ranks, equal values -- a rejected move repeats a walker's value
+    -- share the mean of the positions they occupy, -0.0 equals +0.0.  ``x`` is a matrix ``(M,)``
+    or ``(M, ncol)`` (host, a ``plot._Samples`` or ``(DeviceArray, M, ncol, ld)``), or a host chain
+    ``(rows, nwalkers, ndim)``, of which every parameter is ranked over all walkers and rows
+    (``chain[discard:, :, d].ravel()``); the result has the shape of ``x[discard:]``.  A column
+    with a NaN or an infinite value is NaN throughout.  ``device=True`` returns the device block
+    ``(DeviceArray [M][ncol], M, ncol, ncol)``, a chain's M being rows x walkers."""
+    pool, shape = _pool_any(x, discard)
+    r, _ = _ranks(pool)
+    return (r, pool.S, pool.ncolp, pool.ncolp) if device else r.get().reshape(shape)
+
+
+def rank_normalize(x, ensembles=1, discard=0, device=False):
+    """The rank-normalised scores ``z = ndtri((r - 3/8) / (S + 1/4))`` of ``x``, ``r`` being
+    ``rank_columns``' ranks and ``S`` the number of values ranked together (Blom's offsets, as in
+    Vehtari et al. 2021).  ``x`` is what ``rank_columns`` takes, or a device chain
+    ``(DeviceArray, rows, nwalkers, ndim)`` as ``group_moments`` takes it; a chain is ranked over
+    all walkers of all ``ensembles`` (which must divide the walkers) and comes back in the chain's
+    layout, ``(rows - discard, nwalkers, ndim)`` -- with ``device=True`` as the block
+    ``(DeviceArray, rows - discard, nwalkers, ndim)`` that ``group_moments`` takes; a matrix as
+    ``(DeviceArray, M, ncol, ncol)``."""
+    if isinstance(ensembles, bool) or not isinstance(ensembles, (int, np.integer)) or ensembles < 1:
+        raise ValueError("ensembles must be a positive integer")
+    # (a 4-tuple is read as a chain here, as group_moments reads it)
+    if isinstance(x, tuple) or (not hasattr(x, "ncol") and len(np.shape(x)) == 3):
+        _, nw, _ = _chain_dims(x, discard)
+        if nw % int(ensembles):
+            raise ValueError("%d walkers do not split into %d ensembles" % (nw, int(ensembles)))
+        pool = _pool_chain(x, discard)
+        shape = (pool.nrows, pool.npool, pool.ncolp)
+    else:
+        pool, shape = _pool_any(x, discard)
+    z = _z_chain(pool)
+    if device:
+        return (z,) + tuple(shape) if len(shape) == 3 else (z, shape[0], shape[1], shape[1])
+    return z.get().reshape(shape)
+
+
+def _taus(ctx, dx, shape, c):
+    """emcee's integrated autocorrelation time of every parameter of the device chain dx
+    [rows][nwalkers * ndim], the autocorrelation function averaged over the walkers
+    (``autocorr.integrated_time(..., tol=0, quiet=True)``)"""
+    from .autocorr import _dimension
+    return np.array([_dimension(ctx, dx, shape, d, c)[0] for d in range(shape[2])], dtype=float)
+
+
+def _check_kind(kind):
+    if kind not in ("bulk", "tail"):
+        raise ValueError("kind must be 'bulk' or 'tail', not %r" % (kind,))
+
+
+def _ess_bulk(pool, c, z=None):
+    shape = (pool.nrows, pool.npool, pool.ncolp)
+    return pool.S / _taus(pool.ctx, _z_chain(pool) if z is None else z, shape, c)
+
+
+def _ess_tail(pool, c):
+    from ._lib import NH_RANK_LE
+    shape = (pool.nrows, pool.npool, pool.ncolp)
+    q = _quantiles(pool.flat(), [0.05, 0.95])
+    tau = [_taus(pool.ctx, _transformed(pool, qq, NH_RANK_LE).owner, shape, c) for qq in q]
+    return np.minimum(pool.S / tau[0], pool.S / tau[1])
+
+
+def ess(x, kind="bulk", discard=0, c=5):
+    """The effective sample size of each parameter of a chain ``(rows, nwalkers, ndim)`` (host, or
+    the device block ``(DeviceArray, rows, nwalkers, ndim)``): ``S / tau`` with
+    ``S = (rows - discard) * nwalkers`` and ``tau`` the integrated autocorrelation time of a
+    TRANSFORMED chain -- ``kind="bulk"``: the rank-normalised scores ``rank_normalize`` gives, which
+    says how well the centre of the posterior is known whatever its tails; ``kind="tail"``: the
+    smaller of the two for the indicator chains ``x <= q05`` and ``x <= q95`` (the quantiles over
+    the pooled values), which says how well the 5 % and 95 % quantiles -- and with them credible
+    bands -- are known.
+
+    ``tau`` is emcee's estimator as this package computes it everywhere
+    (``autocorr.integrated_time(..., c=c, tol=0, quiet=True)``: the autocorrelation function
+    averaged over the walkers, Sokal's window), NOT Stan's Geyer-truncated estimator over
+    independent chains: the walkers of one ensemble are not independent chains.  A NaN ``tau`` --
+    a walker whose transformed series is constant, such as one that never went below ``q05``, a
+    non-finite value, a chain of one row -- gives a NaN ESS."""
+    _check_kind(kind)
+    _chain_dims(x, discard)
+    pool = _pool_chain(x, discard)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return _ess_bulk(pool, c) if kind == "bulk" else _ess_tail(pool, c)
+
+
+def summary(x, ensembles=1, discard=0, labels=None, c=5):
+    """The table of a fit's parameters from GPU reductions over the chain ``x`` (as ``ess`` takes
+    it), a dict of arrays [ndim]: ``mean`` and ``sd`` (ddof = 1) of the pooled values, ``median``,
+    ``q16`` and ``q84`` (``np.quantile``'s linear rule on exact order statistics), ``ess_bulk``,
+    ``ess_tail``, ``tau`` (emcee's, of the values themselves, in rows) and, for ``ensembles`` >= 2,
+    ``rhat`` (moments) and ``rhat_rank`` (``rhat(method="rank")``), both split.  ``labels`` (one
+    per parameter) are returned under ``"labels"``.  Only arrays of ndim values reach the host."""
+    if isinstance(ensembles, bool) or not isinstance(ensembles, (int, np.integer)) or ensembles < 1:
+        raise ValueError("ensembles must be a positive integer")
+    k = int(ensembles)
+    rows, nw, ndim = _chain_dims(x, discard)
+    if k > 1:
+        _chain_shape(x, k, discard, 2)
+    elif nw % k:
+        raise ValueError("%d walkers do not split into %d ensembles" % (nw, k))
+    if labels is not None and len(labels) != ndim:
+        raise ValueError("%d labels for %d parameters" % (len(labels), ndim))
+    pool = _pool_chain(x, discard)
+    flat = pool.flat()
+    st = column_stats(flat)
+    q = _quantiles(flat, [0.16, 0.5, 0.84])
+    z = _z_chain(pool)
+    shape = (pool.nrows, nw, ndim)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out = dict(mean=st["mean"], sd=np.sqrt(st["var"]), median=q[1], q16=q[0], q84=q[2],
+                   ess_bulk=_ess_bulk(pool, c, z), ess_tail=_ess_tail(pool, c),
+                   tau=_taus(pool.ctx, pool.ptr + 8 * pool.row0 * pool.ld, shape, c))
+    if k > 1:
+        block = (pool.owner, rows, nw, ndim)
+        out["rhat"] = _rhat_moments(block, k, discard, 2)
+        out["rhat_rank"] = np.maximum(
+            _rhat_moments((z, pool.nrows, nw, ndim), k, 0, 2),
+            _rhat_moments((_z_chain(_folded(pool)), pool.nrows, nw, ndim), k, 0, 2))
+    if labels is not None:
+        out["labels"] = list(labels)
+    return out
 
 
 # ---------------------------------------------------------------------------------------

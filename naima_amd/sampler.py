@@ -223,15 +223,60 @@ class EnsembleSampler(InfoCritMixin):
         x = self.get_chain(discard=discard, thin=thin)
         return thin * integrated_time(x, **kwargs)
 
-    def get_rhat(self, discard=0, split=True):
+    def get_rhat(self, discard=0, split=True, method="moments"):
         """Gelman-Rubin R-hat of each parameter across the independent ensembles
         (``posterior.rhat`` of ``get_chain(discard=discard)``, the moments computed on the GPU);
-        needs ``ensembles`` >= 2"""
-        from .posterior import rhat
+        needs ``ensembles`` >= 2.  ``method="rank"``: the rank-normalised, folded statistic of
+        Vehtari et al. 2021, the chain ranked on the GPU."""
+        from .posterior import _check_method, rhat
+        _check_method(method)
         if self.ensembles < 2:
             raise ValueError("R-hat compares independent ensembles: make the sampler with "
                              "ensembles >= 2")
-        return rhat(self.get_chain(discard=discard), self.ensembles, split=split)
+        if method == "moments":
+            return rhat(self.get_chain(discard=discard), self.ensembles, split=split)
+        block = self._chain_block(1)
+        if block is not None:
+            return rhat(block, self.ensembles, discard=discard, split=split, method=method)
+        return rhat(self.get_chain(discard=discard), self.ensembles, split=split, method=method)
+
+    def _chain_block(self, thin=1):
+        """the stored chain as the device block ``(DeviceArray, rows, nwalkers, ndim)`` where the
+        device loop still holds ALL of it in one pending history block in HBM (one rank, every
+        stored row asked for), else None: the caller uploads ``get_chain()``.  Nothing is flushed;
+        the launches that fill the block are settled first, as a flush settles them."""
+        dev = self._dev
+        if dev is None or thin != 1 or self.comm.size > 1 or len(self._chain) or len(dev.hist) != 1:
+            return None
+        b = dev.hist[0]
+        if b["n"] < 1 or b.get("own") is not None or b.get("thin_by", 1) != 1:
+            return None
+        dev._meet()
+        return (b["coords"], b["n"], self.nwalkers, self.ndim)
+
+    def get_ess(self, kind="bulk", discard=0, thin=1):
+        """The bulk or tail effective sample size of each parameter
+        (``posterior.ess(self.get_chain(discard=discard, thin=thin), kind)``, ranked and reduced
+        on the GPU): the stored values over emcee's autocorrelation time of the rank-normalised
+        chain, or of the indicators of its 5 % and 95 % quantiles.  Read from the history block in
+        HBM where the device loop still holds the whole chain there (``thin=1``)."""
+        from .posterior import _check_kind, ess
+        _check_kind(kind)
+        block = self._chain_block(thin)
+        if block is not None:
+            return ess(block, kind, discard=discard)
+        return ess(self.get_chain(discard=discard, thin=thin), kind)
+
+    def get_summary(self, discard=0):
+        """``posterior.summary`` of ``get_chain(discard=discard)``: mean, sd, median, q16, q84,
+        ess_bulk, ess_tail, tau and, with several ensembles, rhat and rhat_rank per parameter;
+        read from the history block in HBM where the device loop still holds the whole chain"""
+        from .posterior import summary
+        block = self._chain_block(1)
+        labels = getattr(self, "labels", None)
+        if block is not None:
+            return summary(block, self.ensembles, discard=discard, labels=labels)
+        return summary(self.get_chain(discard=discard), self.ensembles, labels=labels)
 
     # legacy emcee-2 names that naima's analysis code touches
     @property
@@ -436,7 +481,8 @@ class EnsembleSampler(InfoCritMixin):
 
 
     def run_until_converged(self, initial_state, max_steps, check_every=100, tol=50, rtol=0.01,
-                            c=5, discard=0, thin_by=1, max_lag=1024, rhat=None):
+                            c=5, discard=0, thin_by=1, max_lag=1024, rhat=None,
+                            rhat_method="moments"):
         """Run until the integrated autocorrelation time has converged (the loop of emcee's
         tutorial "Autocorrelation analysis & convergence"), ``max_steps`` stored rows at the most.
 
@@ -454,6 +500,9 @@ class EnsembleSampler(InfoCritMixin):
         rows (``posterior.rhat``) -- what tau alone cannot see, an ensemble that has settled
         somewhere else.  ``convergence["rhat"]`` is then the last check's R-hat and the history
         entries are ``(rows, tau, rhat)``.  tau is estimated over all walkers as before.
+        ``rhat_method="rank"`` checks the rank-normalised, folded statistic instead
+        (``posterior.rhat(method="rank")``, the one a threshold of 1.01 is defined for): the rows
+        stored so far are ranked where they lie; ``convergence["rhat_method"]`` records which.
 
         On the device loop (``where == "device"``) the chain stays in HBM: the call allocates ONE
         history block of ``max_steps`` rows -- the memory of ``run_mcmc(max_steps)`` -- that its
@@ -482,10 +531,13 @@ class EnsembleSampler(InfoCritMixin):
             rhat = float(rhat)
             if not rhat > 1.0:
                 raise ValueError("rhat must be larger than 1")
+        from .posterior import _check_method
+        _check_method(rhat_method)
         info = dict(converged=False, rows=0, tau=np.full(self.ndim, np.nan), history=[],
                     where="host", max_lag=max_lag, rebuilds=0)
         if rhat is not None:
             info["rhat"] = np.full(self.ndim, np.nan)
+            info["rhat_method"] = rhat_method
         self.convergence = info
         old, warned = [np.inf], []
         from .posterior import rhat as _rhat
@@ -494,7 +546,9 @@ class EnsembleSampler(InfoCritMixin):
             """R-hat of the rows behind discard; NaN while each half has fewer than two"""
             if rows - discard < 4:
                 return np.full(self.ndim, np.nan)
-            return _rhat(x, self.ensembles, discard=discard)
+            if rhat_method == "moments":
+                return _rhat(x, self.ensembles, discard=discard)
+            return _rhat(x, self.ensembles, discard=discard, method=rhat_method)
 
         def check(rows, tau, rh=None):
             """the books of one check -> stop?"""
@@ -734,11 +788,12 @@ def run_sampler(nrun=100, sampler=None, pos=None, verbose=True, thin_by=1, conve
     it.  The burn-in of ``get_sampler`` is not thinned.
 
     ``converge`` = True, or a dict of ``EnsembleSampler.run_until_converged``'s keywords
-    (``check_every``, ``tol``, ``rtol``, ``c``, ``discard``, ``max_lag``, ``rhat``): ``nrun`` is then
+    (``check_every``, ``tol``, ``rtol``, ``c``, ``discard``, ``max_lag``, ``rhat``, ``rhat_method``): ``nrun`` is then
     the MAXIMUM, the run stops once the autocorrelation time has converged, and ``run_info`` gains
     ``converged`` and ``autocorr_time`` (in stored rows).  With ``rhat`` (a sampler of several
     ensembles) the Gelman-Rubin statistic across them must also lie below it; ``run_info`` gains
-    ``rhat``, the last check's value per parameter."""
+    ``rhat``, the last check's value per parameter (and ``rhat_method`` when it is not the
+    moments statistic)."""
     thin_by = int(thin_by)
     if thin_by <= 0:
         raise ValueError("Invalid thinning argument")
@@ -764,6 +819,8 @@ def run_sampler(nrun=100, sampler=None, pos=None, verbose=True, thin_by=1, conve
         sampler.run_info["autocorr_time"] = [float(t) for t in conv["tau"]]
         if "rhat" in conv:
             sampler.run_info["rhat"] = [float(t) for t in conv["rhat"]]
+            if conv["rhat_method"] != "moments":
+                sampler.run_info["rhat_method"] = conv["rhat_method"]
         if verbose and sampler.comm.rank == 0:
             print("{0} after {1} of at most {2} steps; autocorrelation time: {3}".format(
                 "Converged" if conv["converged"] else "Not converged", conv["rows"], int(nrun),
