@@ -1042,6 +1042,52 @@ int nh_rank_transform(nh_ctx* ctx, const double* x, long long row0, long long nr
                       long long cstride, int npool, int ncolp, const double* thr, int mode,
                       double* out, long long ldo);
 
+/* ---- posterior predictive checks: replicated data, discrepancy statistics, PIT ----------------
+ * Goodness of fit from a chain's stored spectra.  x [M][ld] holds M spectra at the table's nE
+ * energies in the model's unit; conv, flux, elo, ehi [nE] and ul (int32 [nE]) are the data columns
+ * of the likelihood (nh_pointwise_lnl), mc[s][k] = x[s][k]*conv[k] the model in the data's unit.
+ * Upper limits take no part in a discrepancy statistic; P is the set of the other points.  Every
+ * matrix is a row-major DEVICE matrix with ncol <= ld columns in use; every array is a DEVICE
+ * array; results stay on the device.  Stream-ordered on the context's stream, no host
+ * synchronisation, 64-bit row indices.  Deterministic: integer atomics only; every floating-point
+ * sum has an order fixed by the shapes alone.
+ * Every entry point: NH_EINVAL for M == 0, M >= 2^31, nE < 1, nE > ld or a null argument.
+ * nh_ppc_rows: the sampling distribution is the one the likelihood implies (core.py:76-85): a
+ *   datum y given the model m is split normal, scale ehi on the side y < m (weight
+ *   ehi/(elo+ehi)) and elo on the side y > m.  For k in P and the global row index row = row0 + s,
+ *   Philox4x32-10 (Salmon et al. 2011: multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants
+ *   0x9E3779B9, 0xBB67AE85) of counter (lo32(row), hi32(row), k, 0) under key (lo32(seed),
+ *   hi32(seed)) gives r0..r3;
+ *     U = (((uint64)r0 << 20 | r1 >> 12) + 0.5) 2^-52,  V = (r2 + 0.5) 2^-32,  W = r3 2^-32,
+ *     a = sqrt(-2 log U) |cos(2 pi V)|  (half-normal),  below = W (elo + ehi) < ehi,
+ *     y_rep = below ? mc - ehi a : mc + elo a,  r_rep = below ? -a : +a,
+ *   and the observed residual is r_obs = -d/sg with d = mc - flux, sg = d > 0 ? ehi : elo.  A
+ *   value depends on (seed, row, k) alone: neither on the launch shape nor on how the rows are
+ *   cut into calls.  Y [M][ldY] (or NULL) receives y_rep, mc itself at an upper limit; T [M][6]
+ *   (or NULL) = chi2_obs, chi2_rep, maxabs_obs, maxabs_rep, runs_obs, runs_rep over P in column
+ *   order: chi2 = sum r^2 (lane order, then a butterfly), maxabs = max |r| (NaN if an r is),
+ *   runs = 1 + the sign changes between consecutive points of P, r >= 0 counting as positive
+ *   (0 for an empty P), stored as doubles -- a matrix nh_column_moments, nh_hist_columns and
+ *   nh_column_select take as it is.  One wave per row.
+ *   NH_EINVAL also: Y and T both NULL, nE > ldY, row0 < 0.
+ * nh_ppc_counts: counts (int64 [4]) over the rows of T [M][6] whose six values are all finite:
+ *   [0] chi2_rep >= chi2_obs, [1] maxabs_rep >= maxabs_obs, [2] runs_rep <= runs_obs; [3] the
+ *   number of the other rows.
+ * nh_pit_columns: out [2][nE].  out[0][k], k in P: the mean over the rows of the split-normal CDF
+ *   F(flux[k] | mc[s][k]), F = 2 ehi/(elo+ehi) Phi(z/ehi) for z = y - m <= 0 (Phi through erfc:
+ *   a far point stays positive), ehi/(elo+ehi) + 2 elo/(elo+ehi) (Phi(z/elo) - 1/2) above.
+ *   out[1][k], k an upper limit: the fraction of rows with mc > flux.  NaN where the other
+ *   applies.  Column sums in the tiling of nh_column_moments, per-chunk partials added in chunk
+ *   order: repeated calls are bit-identical. */
+int nh_ppc_rows(nh_ctx* ctx, const double* x, long long M, int nE, long long ld,
+                const double* conv, const double* flux, const double* elo, const double* ehi,
+                const int* ul, unsigned long long seed, long long row0, double* Y, long long ldY,
+                double* T);
+int nh_ppc_counts(nh_ctx* ctx, const double* T, long long M, long long* counts);
+int nh_pit_columns(nh_ctx* ctx, const double* x, long long M, int nE, long long ld,
+                   const double* conv, const double* flux, const double* elo, const double* ehi,
+                   const int* ul, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -178,6 +178,10 @@ _SIGS = {
     "nh_rank_columns": [_dp, _dp, _ll, _ll, _ll, _ll, _i, _i, _dp, _dp],
     "nh_rank_normal_scores": [_dp, _dp, _ll, _i, _i, _i, _ll, _ll, _dp],
     "nh_rank_transform": [_dp, _dp, _ll, _ll, _ll, _ll, _i, _i, _dp, _i, _dp, _ll],
+    "nh_ppc_rows": [_dp, _dp, _ll, _i, _ll, _dp, _dp, _dp, _dp, _dp, C.c_ulonglong, _ll, _dp, _ll,
+                    _dp],
+    "nh_ppc_counts": [_dp, _dp, _ll, _dp],
+    "nh_pit_columns": [_dp, _dp, _ll, _i, _ll, _dp, _dp, _dp, _dp, _dp, _dp],
 }
 EXPORTS = tuple(_SIGS) + ("nh_last_error", "nh_version", "nh_ssc_table_bytes")
 

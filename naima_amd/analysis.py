@@ -11,6 +11,7 @@ import numpy as np
 from . import units as u
 from .datatable import DataTable
 from .infocrit import InfoCritMixin
+from .predictive import PredictiveMixin
 
 __all__ = ["save_run", "read_run", "save_results_table", "find_ML", "save_diagnostic_plots"]
 
@@ -159,9 +160,9 @@ def save_run(filename, sampler, compression=True, clobber=False):
     return filename
 
 
-class _Result(InfoCritMixin):
+class _Result(InfoCritMixin, PredictiveMixin):
     """what read_run returns: chain / log-prob / blobs with emcee's accessor names, and the
-    sampler's get_pointwise_log_likelihood / waic / loo"""
+    sampler's get_pointwise_log_likelihood / waic / loo / get_posterior_predictive / ppc"""
 
     def __init__(self, chain, log_prob, blobs, blob_units, data, labels, run_info, accf):
         self._chain, self._lp, self._blobs = chain, log_prob, blobs
@@ -340,7 +341,8 @@ def save_diagnostic_plots(outname, sampler, modelidxs=None, pdf=False, sed=True,
 
 
 def save_results_table(outname, sampler, convert_log=True, last_step=False, include_blobs=True,
-                       overwrite=False, information_criteria=False, diagnostics=False):
+                       overwrite=False, information_criteria=False, diagnostics=False,
+                       goodness_of_fit=False):
     """Write ``<outname>_results.ecsv``: median and 16th/84th-percentile distances of every
     parameter (plus the de-logged value for ``log10(x)`` / ``log(x)`` labels and every
     scalar blob), with the run information, the most probable parameters and the BIC as
@@ -350,7 +352,10 @@ def save_results_table(outname, sampler, convert_log=True, last_step=False, incl
     ``naima_amd.infocrit``, computed on the GPU) to the metadata; without it the file is what it
     always was.  ``diagnostics=True`` adds ``ESS_bulk`` and ``ESS_tail`` per parameter and, for a
     run of several ensembles, ``Rhat_rank`` (``posterior.summary`` of the whole chain, ranked on
-    the GPU).  Returns the table as a dict of columns + ``meta``."""
+    the GPU).  ``goodness_of_fit=True`` adds ``PPC_p_chi2``, ``PPC_p_max``, ``PPC_p_runs`` and
+    ``PPC_chi2_obs_mean`` of the posterior predictive check of the whole chain's stored spectra
+    (blob 0, ``naima_amd.predictive.ppc`` with seed 0).  Returns the table as a dict of columns +
+    ``meta``."""
     import os
 
     import yaml
@@ -394,6 +399,12 @@ def save_results_table(outname, sampler, convert_log=True, last_step=False, incl
         meta["ESS_tail"] = [float(v) for v in sm["ess_tail"]]
         if k > 1:
             meta["Rhat_rank"] = [float(v) for v in sm["rhat_rank"]]
+    if goodness_of_fit:
+        from .infocrit import sampler_spectra
+        from .predictive import ppc
+        g = ppc(*sampler_spectra(sampler))
+        meta["PPC_p_chi2"], meta["PPC_p_max"] = g["p_chi2"], g["p_max"]
+        meta["PPC_p_runs"], meta["PPC_chi2_obs_mean"] = g["p_runs"], g["chi2_obs"]["mean"]
     for k, v in dict(getattr(sampler, "run_info", {})).items():
         meta[k] = v.tolist() if isinstance(v, np.ndarray) else (v.item() if isinstance(
             v, np.generic) else v)

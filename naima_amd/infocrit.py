@@ -135,19 +135,11 @@ def compare(results, names=None, ic="loo"):
 # ---------------------------------------------------------------------------------------
 # device
 # ---------------------------------------------------------------------------------------
-def pointwise_log_likelihood(model, data, unit=None, totals=False):
-    """L[s][k], the term of data point k in ``lnprobmodel`` of spectrum s (module docstring), as
-    a device matrix handle (``.get()`` downloads it; ``waic`` and ``loo`` take it as it is).
-
-    ``model`` is a ``Quantity`` (M, n_data) in host memory, or a device matrix as
-    ``posterior._matrix`` accepts it together with its ``unit``; the conversion to the data's
-    unit is ``core._conversion_to_data``, the one the fit itself used (SED <-> differential
-    included).  ``totals=True`` returns (L, row sums as a device array [M]) instead.  A
-    non-finite term raises ``ValueError`` with their number."""
+def _model_values(model, data, unit):
+    """(values, unit, M, nE) of a model argument -- a ``Quantity`` (M, n_data), or a matrix as
+    ``posterior._matrix`` accepts it together with its ``unit`` -- checked against the data
+    table, without a device"""
     from . import units as u
-    from .core import _data_on_device
-    from .plot import _Samples
-    from .posterior import _matrix
     if isinstance(model, u.Quantity):
         if unit is not None and u.Unit(unit) != model.unit:
             raise ValueError("unit= contradicts the Quantity's own unit")
@@ -163,6 +155,22 @@ def pointwise_log_likelihood(model, data, unit=None, totals=False):
         raise ValueError("model has %d energies, data table has %d" % (nE, n_data))
     if M >= 2 ** 31:
         raise ValueError("more than 2^31 - 1 samples")
+    return values, unit, M, nE
+
+
+def pointwise_log_likelihood(model, data, unit=None, totals=False):
+    """L[s][k], the term of data point k in ``lnprobmodel`` of spectrum s (module docstring), as
+    a device matrix handle (``.get()`` downloads it; ``waic`` and ``loo`` take it as it is).
+
+    ``model`` is a ``Quantity`` (M, n_data) in host memory, or a device matrix as
+    ``posterior._matrix`` accepts it together with its ``unit``; the conversion to the data's
+    unit is ``core._conversion_to_data``, the one the fit itself used (SED <-> differential
+    included).  ``totals=True`` returns (L, row sums as a device array [M]) instead.  A
+    non-finite term raises ``ValueError`` with their number."""
+    from .core import _data_on_device
+    from .plot import _Samples
+    from .posterior import _matrix
+    values, unit, M, nE = _model_values(model, data, unit)
     s = _matrix(values)
     ctx = s.ctx
     dd = _data_on_device(ctx, data)
@@ -240,11 +248,12 @@ def loo(L, reff=1.0):
 # ---------------------------------------------------------------------------------------
 # a sampler's (or a read run's) stored spectra
 # ---------------------------------------------------------------------------------------
-def sampler_pointwise(sampler, discard=0, thin=1, modelidx=0):
-    """The pointwise matrix of stored blob ``modelidx`` of every (step, walker) that
-    ``get_blobs(discard=discard, thin=thin)`` selects, rows in its flattened order: uploaded once,
-    returned as the device handle.  A blob that is not a spectrum at the data's energies raises
-    the ``TypeError`` of ``plot._process_blob``.  Collective on several ranks, as ``get_blobs``."""
+def sampler_spectra(sampler, discard=0, thin=1, modelidx=0):
+    """(spectra, data): stored blob ``modelidx`` of every (step, walker) that
+    ``get_blobs(discard=discard, thin=thin)`` selects as a ``Quantity`` (M, n_data), rows in its
+    flattened order, and the sampler's data table.  A blob that is not a spectrum at the data's
+    energies raises the ``TypeError`` of ``plot._process_blob``.  Collective on several ranks, as
+    ``get_blobs``."""
     from . import units as u
     wrong = TypeError("Model {0} has wrong blob format".format(modelidx))
     data = getattr(sampler, "data", None)
@@ -259,7 +268,15 @@ def sampler_pointwise(sampler, discard=0, thin=1, modelidx=0):
         raise wrong
     if b.shape[0] * b.shape[1] == 0:
         raise ValueError("discard = %d leaves no stored step" % discard)
-    return pointwise_log_likelihood(u.Quantity(b.reshape(-1, b.shape[2]), unit), data)
+    return u.Quantity(b.reshape(-1, b.shape[2]), unit), data
+
+
+def sampler_pointwise(sampler, discard=0, thin=1, modelidx=0):
+    """The pointwise matrix of stored blob ``modelidx`` of every (step, walker) that
+    ``get_blobs(discard=discard, thin=thin)`` selects, rows in its flattened order: uploaded once,
+    returned as the device handle.  A blob that is not a spectrum at the data's energies raises
+    the ``TypeError`` of ``plot._process_blob``.  Collective on several ranks, as ``get_blobs``."""
+    return pointwise_log_likelihood(*sampler_spectra(sampler, discard, thin, modelidx))
 
 
 class InfoCritMixin:

@@ -708,6 +708,55 @@ def plot_data(input_data, xlabel=None, ylabel=None, sed=True, figure=None, e_uni
     return f
 
 
+def plot_ppc(sampler, modelidx=0, confs=(0.68, 0.95), seed=0, sed=True, figure=None):
+    """The posterior predictive check of a fit (``naima_amd.predictive``): the data over the
+    PREDICTIVE bands of central probability ``confs`` -- quantiles per energy of one replicated
+    data set per stored spectrum, so they hold the noise of the data, unlike ``plot_fit``'s model
+    bands -- and below them the probability integral transform of every flux point; the three
+    Bayesian p-values in the title.  Replicates, quantiles and statistics are taken on the GPU."""
+    from .infocrit import sampler_spectra
+    from .posterior import _matrix
+    from .predictive import posterior_predictive, ppc, predictive_quantiles
+    confs = sorted((float(c) for c in confs), reverse=True)
+    if not confs or not all(0.0 < c < 1.0 for c in confs):
+        raise ValueError("confs must be probabilities in (0, 1)")
+    import matplotlib.pyplot as plt
+    model, data = sampler_spectra(sampler, modelidx=modelidx)
+    spectra = _matrix(model.value)  # (uploaded once for both calls)
+    res = ppc(spectra, data, unit=model.unit, seed=seed)
+    y = posterior_predictive(spectra, data, unit=model.unit, seed=seed)
+    q = [0.5] + [v for c in confs for v in ((1.0 - c) / 2.0, (1.0 + c) / 2.0)]
+    df_unit, dsedf = sed_conversion(data["energy"], data["flux"].unit, sed)
+    fac = (u.Quantity(np.ones(y.ncol), data["flux"].unit) * dsedf).to(df_unit).value
+    bands = predictive_quantiles(y, q) * fac
+    e_unit = data["energy"].unit
+    ene = data["energy"].to(e_unit).value
+    f = plt.figure() if figure is None else figure
+    ax1 = plt.subplot2grid((4, 1), (0, 0), rowspan=3, fig=f)
+    ax2 = plt.subplot2grid((4, 1), (3, 0), sharex=ax1, fig=f)
+    color = color_cycle[3]
+    for i, c in enumerate(confs):
+        ax1.fill_between(ene, bands[1 + 2 * i], bands[2 + 2 * i], lw=0.0, color=color,
+                         alpha=0.25 + 0.25 * i / max(len(confs) - 1, 1),
+                         label="{0:g}% predictive".format(100 * c))
+    ax1.plot(ene, bands[0], color=color, lw=1)
+    _plot_data_to_ax(data, ax1, e_unit=e_unit, sed=sed)
+    ax1.legend(loc="lower left", frameon=False)
+    ax1.set_title(r"$p_{{\chi^2}}$ = {0:.3f}   $p_\mathrm{{max}}$ = {1:.3f}   "
+                  r"$p_\mathrm{{runs}}$ = {2:.3f}".format(res["p_chi2"], res["p_max"],
+                                                          res["p_runs"]))
+    ax2.axhline(0.5, color="k", lw=1, ls="--")
+    ax2.plot(ene, res["pit"], ls="", marker="o", ms=5, color=color_cycle[0])
+    ax2.plot(ene, res["ul_violation"], ls="", marker="v", ms=5, color=color_cycle[2])
+    ax2.set_ylim(0.0, 1.0)
+    ax2.set_ylabel("PIT")
+    ax2.set_xlabel(r"$\mathrm{Energy}$" + " [{0}]".format(_unit_label(e_unit)))
+    for t in ax1.get_xticklabels():
+        t.set_visible(False)
+    f.subplots_adjust(hspace=0)
+    return f
+
+
 def plot_corner(sampler, show_ML=True, **kwargs):
     """Corner plot of the chain (plot.py:1393-1439): through ``corner.corner`` when the corner
     package is installed; else, after a warning, the built-in figure ``posterior.corner`` draws

@@ -20,6 +20,7 @@ import numpy as np
 from . import units as u
 from .dist import LocalComm, shard_bounds, shard_counts
 from .infocrit import InfoCritMixin
+from .predictive import PredictiveMixin
 
 __all__ = ["EnsembleSampler", "State", "get_sampler", "run_sampler"]
 
@@ -48,7 +49,7 @@ def _split_blob(b):
     return np.asarray(b, dtype=float), None
 
 
-class EnsembleSampler(InfoCritMixin):
+class EnsembleSampler(InfoCritMixin, PredictiveMixin):
     """Stretch-move ensemble sampler over a *batched* log-probability.
 
     log_prob_fn(coords[n, ndim], *args) -> lnp[n]  or  (lnp[n], blob0[n,...], ...)
