@@ -1088,6 +1088,60 @@ int nh_pit_columns(nh_ctx* ctx, const double* x, long long M, int nE, long long 
                    const double* conv, const double* flux, const double* elo, const double* ehi,
                    const int* ul, double* out);
 
+/* ---- marginal likelihood by bridge sampling: covariance, normal proposal, iteration sums ------
+ * What the bridge-sampling estimate of Z = int exp(lnprob) (Meng & Wong 1996; the "normal" method
+ * of Gronau et al. 2017) reads from a chain in HBM.  Pooled rows are addressed as the pooled
+ * columns of nh_rank_columns are: pooled row e = t * npool + j holds the d values
+ * x[(row0 + t) * ld + j * cstride + 0 .. d - 1]; S = nrows * npool of them.  A chain
+ * [rows][walker][parameter] behind `discard` rows is row0 = discard, cstride = d, npool = walkers;
+ * a plain matrix [M][ld] is npool = 1.  mean is [d], L the LOWER Cholesky factor of the
+ * covariance, row-major [d][d] (the upper triangle is not read); every array is a DEVICE array and
+ * results stay on the device.  FP64; stream-ordered on the context's stream, no host
+ * synchronisation; no atomics: every floating-point sum has an order fixed by the shapes alone
+ * (per-chunk partials added in chunk order, the tiling of nh_column_moments), so repeated calls
+ * are bit-identical.
+ * nh_chain_cov, nh_mvn_logpdf: NH_EINVAL for a null argument, row0 < 0, nrows, npool or d < 1,
+ *   d > NH_EVID_MAX_DIM, cstride < d with npool > 1, (npool - 1) * cstride + d > ld,
+ *   nrows * npool >= 2^31.
+ * nh_chain_cov: mean [d] and cov [d][d], the unbiased (ddof = 1) covariance of the S pooled rows,
+ *   exactly symmetric.  Two passes: the mean, then the centred products.  A column that holds a
+ *   NaN or +-inf has a NaN mean, and its row and column of cov are NaN.  S = 1: cov is NaN (0/0).
+ * nh_mvn_draw: out[r][0..d-1] = mean + L z_r for r < n, out a matrix [n][ld]; columns d..ld-1 are
+ *   not written.  z_r[c] is standard normal: Philox4x32-10 (nh_ppc_rows' generator) of counter
+ *   (lo32(row), hi32(row), c >> 1, 0x4D564E31) under key (lo32(seed), hi32(seed)), row = row0 + r,
+ *   gives r0..r3; U = (((uint64)r0 << 20 | r1 >> 12) + 0.5) 2^-52, V the same of (r2, r3),
+ *   z = sqrt(-2 log U) cos(2 pi V) for an even c and ... sin(2 pi V) for an odd one (Box-Muller).
+ *   Counter word 3 keeps the stream apart from nh_ppc_rows' (word 3 = 0) under the same seed.  A
+ *   value depends on (seed, row, c) alone: neither on the launch shape nor on how the rows are
+ *   cut into calls.  z2[r] = sum_c z_r[c]^2 in column order.
+ *   NH_EINVAL: a null argument, d outside [1, NH_EVID_MAX_DIM], n outside [1, 2^31), row0 < 0,
+ *   d > ld.
+ * nh_mvn_logpdf: out[e] = log N(theta_e; mean, L L^T) = -d/2 log 2 pi - sum_i log L_ii - |y|^2/2,
+ *   y = L^-1 (theta_e - mean) by forward substitution, for every pooled row; with lp [S] given
+ *   (else NULL), out[e] = lp[e] - log N(...): the chain's stored log-probability over the
+ *   proposal's density.  A row with a NaN or +-inf entry gives NaN.
+ * nh_bridge_l2: out[i] = lp[i] + z2[i]/2 + d/2 log 2 pi + sum_i log L_ii for i < n: the same
+ *   ratio at draw i of nh_mvn_draw, whose density follows from its own |z|^2.  lp = -inf (a draw
+ *   the prior forbids) stays -inf.
+ * nh_bridge_sums: one iteration of the estimator.  out [2] = { sum_j f(l2[j] - lstar),
+ *   sum_i g(l1[i] - lstar) } with f(x) = e^x / (s1 e^x + s2 r), g(x) = 1 / (s1 e^x + s2 r); for
+ *   x > 0 both are evaluated through e^-x, so nothing overflows, and x = -inf gives f = 0
+ *   exactly.  f1 [N2] and f2 [N1] (or NULL) receive the terms themselves.  Two launches.
+ *   NH_EINVAL: a null l1, l2 or out, N1 or N2 outside [1, 2^31). */
+#define NH_EVID_MAX_DIM 32
+int nh_chain_cov(nh_ctx* ctx, const double* x, long long row0, long long nrows, long long ld,
+                 long long cstride, int npool, int d, double* mean, double* cov);
+int nh_mvn_draw(nh_ctx* ctx, const double* mean, const double* L, int d, unsigned long long seed,
+                long long row0, long long n, double* out, long long ld, double* z2);
+int nh_mvn_logpdf(nh_ctx* ctx, const double* x, long long row0, long long nrows, long long ld,
+                  long long cstride, int npool, int d, const double* mean, const double* L,
+                  const double* lp, double* out);
+int nh_bridge_l2(nh_ctx* ctx, const double* lp, const double* z2, long long n, const double* L,
+                 int d, double* out);
+int nh_bridge_sums(nh_ctx* ctx, const double* l1, long long N1, const double* l2, long long N2,
+                   double lstar, double s1, double s2, double r, double* out, double* f1,
+                   double* f2);
+
 #ifdef __cplusplus
 }
 #endif

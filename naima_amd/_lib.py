@@ -22,6 +22,7 @@ NH_HIST_MAX_COLS, NH_HIST_MAX_PAIRS, NH_HIST_MAX_BINS_1D, NH_HIST_MAX_BINS_2D = 
 NH_RANK_POOLED, NH_RANK_CHAIN = 0, 1   # nh_rank_normal_scores' layouts
 NH_RANK_FOLD, NH_RANK_LE = 0, 1        # nh_rank_transform's modes
 NH_PSIS_MAX_TAIL = 4096  # nh_psis_columns' cap on the tail length (include/naima_hip.h)
+NH_EVID_MAX_DIM = 32     # nh_chain_cov's, nh_mvn_*'s cap on the dimension (include/naima_hip.h)
 NH_K_NAMES = ("particle_weights", "integrate_tables", "synchrotron", "tables", "lnprob",
               "ic_seed_walkers", "glue", "integrate_rows", "half_step")
 PD_KIND = {"PowerLaw": 0, "ExponentialCutoffPowerLaw": 1, "BrokenPowerLaw": 2,
@@ -182,6 +183,11 @@ _SIGS = {
                     _dp],
     "nh_ppc_counts": [_dp, _dp, _ll, _dp],
     "nh_pit_columns": [_dp, _dp, _ll, _i, _ll, _dp, _dp, _dp, _dp, _dp, _dp],
+    "nh_chain_cov": [_dp, _dp, _ll, _ll, _ll, _ll, _i, _i, _dp, _dp],
+    "nh_mvn_draw": [_dp, _dp, _dp, _i, C.c_ulonglong, _ll, _ll, _dp, _ll, _dp],
+    "nh_mvn_logpdf": [_dp, _dp, _ll, _ll, _ll, _ll, _i, _i, _dp, _dp, _dp, _dp],
+    "nh_bridge_l2": [_dp, _dp, _dp, _ll, _dp, _i, _dp],
+    "nh_bridge_sums": [_dp, _dp, _ll, _dp, _ll, _d, _d, _d, _d, _dp, _dp, _dp],
 }
 EXPORTS = tuple(_SIGS) + ("nh_last_error", "nh_version", "nh_ssc_table_bytes")
 

@@ -342,7 +342,7 @@ def save_diagnostic_plots(outname, sampler, modelidxs=None, pdf=False, sed=True,
 
 def save_results_table(outname, sampler, convert_log=True, last_step=False, include_blobs=True,
                        overwrite=False, information_criteria=False, diagnostics=False,
-                       goodness_of_fit=False):
+                       goodness_of_fit=False, evidence=None):
     """Write ``<outname>_results.ecsv``: median and 16th/84th-percentile distances of every
     parameter (plus the de-logged value for ``log10(x)`` / ``log(x)`` labels and every
     scalar blob), with the run information, the most probable parameters and the BIC as
@@ -354,8 +354,11 @@ def save_results_table(outname, sampler, convert_log=True, last_step=False, incl
     run of several ensembles, ``Rhat_rank`` (``posterior.summary`` of the whole chain, ranked on
     the GPU).  ``goodness_of_fit=True`` adds ``PPC_p_chi2``, ``PPC_p_max``, ``PPC_p_runs`` and
     ``PPC_chi2_obs_mean`` of the posterior predictive check of the whole chain's stored spectra
-    (blob 0, ``naima_amd.predictive.ppc`` with seed 0).  Returns the table as a dict of columns +
-    ``meta``."""
+    (blob 0, ``naima_amd.predictive.ppc`` with seed 0).  ``evidence`` adds ``logZ``, ``logZ_err``
+    and ``logZ_forbidden_fraction``: a result of ``naima_amd.evidence.bridge_sampling``, or True
+    for ``sampler.log_evidence()`` with its defaults (a sampler only: a read run has no
+    log-probability function; and mind that module's docstring on proper priors and
+    ``log_prior_norm``).  Returns the table as a dict of columns + ``meta``."""
     import os
 
     import yaml
@@ -405,6 +408,17 @@ def save_results_table(outname, sampler, convert_log=True, last_step=False, incl
         g = ppc(*sampler_spectra(sampler))
         meta["PPC_p_chi2"], meta["PPC_p_max"] = g["p_chi2"], g["p_max"]
         meta["PPC_p_runs"], meta["PPC_chi2_obs_mean"] = g["p_runs"], g["chi2_obs"]["mean"]
+    if evidence is not None and evidence is not False:
+        if evidence is True:
+            if not hasattr(sampler, "log_evidence"):
+                raise ValueError("evidence=True needs a sampler with a log-probability function; "
+                                 "pass a result of naima_amd.evidence.bridge_sampling")
+            evidence = sampler.log_evidence()
+        try:
+            meta["logZ"], meta["logZ_err"] = float(evidence["logz"]), float(evidence["logz_err"])
+            meta["logZ_forbidden_fraction"] = float(evidence["forbidden_fraction"])
+        except (TypeError, KeyError, IndexError):
+            raise ValueError("evidence must be True or a result of evidence.bridge_sampling")
     for k, v in dict(getattr(sampler, "run_info", {})).items():
         meta[k] = v.tolist() if isinstance(v, np.ndarray) else (v.item() if isinstance(
             v, np.generic) else v)

@@ -31,40 +31,20 @@
 // repeated calls give bit-identical results.  Row indices are 64-bit, M < 2^31.  Every launch is
 // on the context's stream; nothing synchronises with the host.
 #include "nh_colred.h"
+#include "nh_philox.h"
 
 namespace {
 
 __device__ __forceinline__ double ppc_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 // ---------------------------------------------------------------- the random stream
-// Philox4x32-10 (Salmon, Moraes, Dror & Shaw 2011): ten rounds of two 32 x 32 -> 64 bit products,
-// the key bumped by the Weyl constants between rounds
-struct ppc_u4 {
-  unsigned x, y, z, w;
-};
-
-__host__ __device__ __forceinline__ ppc_u4 ppc_philox(unsigned c0, unsigned c1, unsigned c2,
-                                                      unsigned c3, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (unsigned)p1;
-    c3 = (unsigned)p0;
-    c0 = n0;
-    c2 = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return ppc_u4{c0, c1, c2, c3};
-}
-
+// (Philox4x32-10: nh_philox.h; counter word 3 = 0 is this stream's)
 // the half-normal a and the side of the replicate of (row, k)
 __host__ __device__ __forceinline__ double ppc_draw(unsigned long long seed, long long row, int k,
                                                     double elo, double ehi, bool* below) {
-  const ppc_u4 r = ppc_philox((unsigned)((unsigned long long)row & 0xffffffffull),
-                              (unsigned)((unsigned long long)row >> 32), (unsigned)k, 0u,
-                              (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32));
+  const nh_u4 r = nh_philox((unsigned)((unsigned long long)row & 0xffffffffull),
+                            (unsigned)((unsigned long long)row >> 32), (unsigned)k, 0u,
+                            (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32));
   const double U =
       ((double)(((unsigned long long)r.x << 20) | (unsigned long long)(r.y >> 12)) + 0.5) *
       0x1p-52;

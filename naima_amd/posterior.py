@@ -22,6 +22,9 @@ device (``nh_rank_columns``: average ranks from a radix sort), the ranks become 
 (``nh_rank_normal_scores``), and the moments and autocorrelation kernels read those exactly as they
 read a chain.
 
+``covariance`` is the mean and the unbiased covariance matrix of a chain's pooled rows or of a
+matrix (``nh_chain_cov``, two passes), what ``evidence.bridge_sampling`` fits its proposal to.
+
 Importing this module creates no GPU context; argument errors come before any device work.
 matplotlib is imported by ``corner`` only.
 """
@@ -29,12 +32,12 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (NH_HIST_MAX_BINS_1D, NH_HIST_MAX_BINS_2D, NH_HIST_MAX_COLS,
+from ._lib import (NH_EVID_MAX_DIM, NH_HIST_MAX_BINS_1D, NH_HIST_MAX_BINS_2D, NH_HIST_MAX_COLS,
                    NH_HIST_MAX_PAIRS)
 
 __all__ = ["column_stats", "histogram", "histogram_pairs", "gaussian_kde", "contour_thresholds",
            "corner", "DEFAULT_LEVELS", "group_moments", "rhat", "rhat_from_moments",
-           "rank_columns", "rank_normalize", "ess", "summary"]
+           "rank_columns", "rank_normalize", "ess", "summary", "covariance"]
 
 # the mass of a 2-D Gaussian inside 0.5, 1, 1.5 and 2 sigma (corner's default contours)
 DEFAULT_LEVELS = tuple(1.0 - np.exp(-0.5 * np.array([0.5, 1.0, 1.5, 2.0]) ** 2))
@@ -640,6 +643,28 @@ def summary(x, ensembles=1, discard=0, labels=None, c=5):
     if labels is not None:
         out["labels"] = list(labels)
     return out
+
+
+def covariance(x, discard=0):
+    """(mean [d], cov [d][d]) of the rows of ``x`` behind ``discard``: ``np.mean(rows, axis=0)``
+    and ``np.cov(rows, rowvar=False)`` (unbiased), in two passes on the GPU (``nh_chain_cov``).
+    ``x`` is a host chain ``(rows, nwalkers, ndim)`` or a device chain ``(DeviceArray, rows,
+    nwalkers, ndim)``, of which every walker is pooled (a 4-tuple is read as a chain, as
+    ``rank_normalize`` reads it), or a matrix ``(M,)`` / ``(M, d)`` (host, or a
+    ``plot._Samples``).  d <= 32.  A column with a NaN or an infinite value is NaN in the mean and
+    in its row and column of the covariance; a single row gives a NaN covariance."""
+    if isinstance(x, tuple) or (not hasattr(x, "ncol") and len(np.shape(x)) == 3):
+        d = _chain_dims(x, discard)[2]
+    else:
+        M, d = _shape(x)
+    if d > NH_EVID_MAX_DIM:
+        raise ValueError("%d columns are more than the %d a covariance takes"
+                         % (d, NH_EVID_MAX_DIM))
+    pool = _pool_chain(x, discard) if isinstance(x, tuple) else _pool_any(x, discard)[0]
+    ctx = pool.ctx
+    mean, cov = ctx.empty((d,)), ctx.empty((d, d))
+    ctx.call("nh_chain_cov", *pool.args(), mean, cov)
+    return mean.get(), cov.get()
 
 
 # ---------------------------------------------------------------------------------------

@@ -19,6 +19,7 @@ import numpy as np
 
 from . import units as u
 from .dist import LocalComm, shard_bounds, shard_counts
+from .evidence import EvidenceMixin
 from .infocrit import InfoCritMixin
 from .predictive import PredictiveMixin
 
@@ -49,7 +50,7 @@ def _split_blob(b):
     return np.asarray(b, dtype=float), None
 
 
-class EnsembleSampler(InfoCritMixin, PredictiveMixin):
+class EnsembleSampler(InfoCritMixin, PredictiveMixin, EvidenceMixin):
     """Stretch-move ensemble sampler over a *batched* log-probability.
 
     log_prob_fn(coords[n, ndim], *args) -> lnp[n]  or  (lnp[n], blob0[n,...], ...)
