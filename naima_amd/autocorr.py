@@ -19,6 +19,8 @@ import logging
 
 import numpy as np
 
+from .dview import as_chain
+
 __all__ = ["function_1d", "integrated_time", "AutocorrError", "auto_window", "RunningAutocorr",
            "converged"]
 
@@ -44,20 +46,12 @@ def auto_window(taus, c):
     return len(taus) - 1
 
 
-def _device_chain(x):
-    """(ctx, device [n_t][n_w*n_d] copy of the host chain x [n_t][n_w][n_d])"""
-    from . import _lib
-    ctx = _lib.get_context()
-    n_t, n_w, n_d = x.shape
-    return ctx, ctx.array(np.ascontiguousarray(x, dtype=np.float64).reshape(n_t, n_w * n_d))
-
-
-def _prep(ctx, dx, shape, d):
-    """centre dimension d's series on the device: (z, s2, ok); ok is False when a walker's series
-    is constant or holds a non-finite value (the dimension is NaN then)"""
-    n_t, n_w, n_d = shape
+def _prep(chain, d):
+    """centre dimension d's series of a DeviceChain on the device: (z, s2, ok); ok is False when a
+    walker's series is constant or holds a non-finite value (the dimension is NaN then)"""
+    ctx, (n_t, n_w, n_d) = chain.ctx, chain.shape
     z, s2 = ctx.empty((n_w, n_t)), ctx.empty((n_w,))
-    ctx.call("nh_autocorr_prep", dx, n_t, n_w, n_d, d, z, s2)
+    ctx.call("nh_autocorr_prep", chain.ptr, n_t, n_w, n_d, d, z, s2)
     v = s2.get()
     return z, s2, bool(np.all(np.isfinite(v) & (v > 0)))
 
@@ -75,10 +69,11 @@ def _window_done(taus, c):
     return bool(m[0]) and not bool(np.all(m))
 
 
-def _dimension(ctx, dx, shape, d, c):
-    """(tau, window, f) of dimension d; f holds the lags computed, NaN-filled for a NaN dimension"""
-    n_t, n_w, _ = shape
-    z, s2, ok = _prep(ctx, dx, shape, d)
+def _dimension(chain, d, c):
+    """(tau, window, f) of a DeviceChain's dimension d; f holds the lags computed, NaN-filled for
+    a NaN dimension"""
+    ctx, (n_t, n_w, _) = chain.ctx, chain.shape
+    z, s2, ok = _prep(chain, d)
     if not ok:
         return np.nan, n_t - 1, np.full(1, np.nan)
     f = np.empty(0)
@@ -114,8 +109,8 @@ def _as3d(x, has_walkers):
 def _integrated(x, c=5, has_walkers=True):
     """(tau [n_d], windows [n_d], [f of each dimension], n_t) without the tolerance check"""
     x = _as3d(x, has_walkers)
-    ctx, dx = _device_chain(x)
-    out = [_dimension(ctx, dx, x.shape, d, c) for d in range(x.shape[2])]
+    chain = as_chain(x)
+    out = [_dimension(chain, d, c) for d in range(x.shape[2])]
     tau = np.array([o[0] for o in out], dtype=float)
     windows = np.array([o[1] for o in out], dtype=int)
     return tau, windows, [o[2] for o in out], x.shape[0]
@@ -130,12 +125,11 @@ def function_1d(x):
     n_t = x.shape[0]
     if n_t == 0:
         raise ValueError("the series is empty")
-    x3 = x[:, np.newaxis, np.newaxis]
-    ctx, dx = _device_chain(x3)
-    z, s2, ok = _prep(ctx, dx, x3.shape, 0)
+    chain = as_chain(x[:, np.newaxis, np.newaxis])
+    z, s2, ok = _prep(chain, 0)
     if not ok:
         return np.full(n_t, np.nan)
-    return _lags(ctx, z, s2, n_t, 1, 0, n_t)
+    return _lags(chain.ctx, z, s2, n_t, 1, 0, n_t)
 
 
 def integrated_time(x, c=5, tol=50, quiet=False, has_walkers=True):

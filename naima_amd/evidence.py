@@ -44,6 +44,7 @@ import warnings
 import numpy as np
 
 from ._lib import NH_EVID_MAX_DIM
+from .dview import DeviceChain, as_chain, chain_dims, matrix_on
 
 __all__ = ["bridge_sampling", "bayes_factor", "EvidenceMixin"]
 
@@ -72,36 +73,34 @@ def _pos_float(name, v):
     return f
 
 
-def _logp_dims(log_prob, rows, nw):
-    """the stored log-probabilities match a chain of (rows, nw): a host array of that shape, or a
-    device array (or a tuple that starts with one) of at least rows * nw values"""
+def _logp(chain, log_prob, rows, nw):
+    """the log-probabilities of a chain of (rows, nw) as ``as_chain`` takes them: a host array of
+    that shape beside a host chain, the DeviceMatrix of a device array of rows * nw values (or of
+    a tuple that starts with one) beside a device chain, None for those a DeviceChain carries"""
+    if log_prob is None and getattr(chain, "logp", None) is not None:
+        return None
     dev = log_prob[0] if isinstance(log_prob, tuple) and len(log_prob) else log_prob
-    if hasattr(dev, "ptr") and hasattr(dev, "nbytes"):
-        if isinstance(log_prob, tuple) and tuple(int(v) for v in log_prob[1:3]) != (rows, nw):
-            raise ValueError("the device log-probabilities are not (%d, %d)" % (rows, nw))
-        if rows * nw * 8 > dev.nbytes:
-            raise ValueError("device log-probabilities of %d x %d do not fit their buffer"
-                             % (rows, nw))
-        return True
+    if hasattr(dev, "ptr") != isinstance(chain, (tuple, DeviceChain)):
+        raise ValueError("chain and log_prob must both be host arrays or both device blocks")
+    if hasattr(dev, "ptr"):  # (a tuple's own shape: the chain refuses one that is not its own)
+        return matrix_on(dev, *(log_prob[1:3] if isinstance(log_prob, tuple) else (rows, nw)))
     if np.shape(log_prob) != (rows, nw):
         raise ValueError("log_prob must be (rows, nwalkers) = (%d, %d), not %r"
                          % (rows, nw, np.shape(log_prob)))
-    return False
+    return log_prob
 
 
 def _check(chain, log_prob, log_prob_fn, seed, n_draws, neff, log_prior_norm, tol, maxiter,
            discard, batch):
-    from .posterior import _chain_dims
     from .predictive import _int_in
-    rows, nw, ndim = _chain_dims(chain, discard, 2)
+    rows, nw, ndim = chain_dims(chain, discard, 2)
     if ndim > NH_EVID_MAX_DIM:
         raise ValueError("%d parameters are more than the %d the covariance kernels take"
                          % (ndim, NH_EVID_MAX_DIM))
     discard = int(discard)
     n = rows - discard
     h = n // 2
-    if isinstance(chain, tuple) != _logp_dims(log_prob, rows, nw):
-        raise ValueError("chain and log_prob must both be host arrays or both device blocks")
+    logp = _logp(chain, log_prob, rows, nw)
     if not callable(log_prob_fn):
         raise ValueError("log_prob_fn must be callable")
     seed = _int_in("seed", seed, 2 ** 64)
@@ -116,7 +115,7 @@ def _check(chain, log_prob, log_prob_fn, seed, n_draws, neff, log_prior_norm, to
     tol = _pos_float("tol", tol)
     maxiter = _pos_int("maxiter", maxiter)
     batch = nw if batch is None else _pos_int("batch", batch)
-    return dict(rows=rows, nw=nw, ndim=ndim, discard=discard, h=h, n2=n - h, N1=N1, N2=N2,
+    return dict(logp=logp, nw=nw, ndim=ndim, discard=discard, h=h, n2=n - h, N1=N1, N2=N2,
                 seed=seed, neff=neff, lpn=lpn, tol=tol, maxiter=maxiter, batch=batch)
 
 
@@ -148,12 +147,6 @@ def _evaluate(log_prob_fn, theta, batch):
     return out
 
 
-def _vector(ctx, buf, n):
-    """a device vector [n] as a one-column matrix"""
-    from .plot import _Samples
-    return _Samples(ctx, buf.ptr, n, 1, 1, buf)
-
-
 def bridge_sampling(chain, log_prob, log_prob_fn, seed=0, n_draws=None, neff=None,
                     log_prior_norm=0.0, tol=1e-10, maxiter=1000, discard=0, batch=None):
     """The log marginal likelihood of a chain by bridge sampling (module docstring: the priors
@@ -162,7 +155,8 @@ def bridge_sampling(chain, log_prob, log_prob_fn, seed=0, n_draws=None, neff=Non
     ``chain`` (rows, nwalkers, ndim) and ``log_prob`` (rows, nwalkers) are host arrays, as
     ``get_chain()`` and ``get_log_prob()`` return them, which are uploaded once; or device blocks:
     ``(DeviceArray, rows, nwalkers, ndim)`` laid out [rows][nwalkers * ndim], and a DeviceArray
-    [rows][nwalkers] (or a tuple ``(DeviceArray, rows, nwalkers)``).  ``log_prob_fn(theta[n, ndim])
+    [rows][nwalkers] (or a tuple ``(DeviceArray, rows, nwalkers)``); or a ``dview.DeviceChain``,
+    with ``log_prob=None`` where it carries its ``logp``.  ``log_prob_fn(theta[n, ndim])
     -> lnprob[n]`` is the function the chain was sampled from, called with host arrays of
     ``batch`` rows (default ``nwalkers``); ``-inf`` marks a point the prior forbids; NaN and +inf
     raise ``ValueError``.  ``n_draws`` = N2 proposals (default N1, the size of the second half);
@@ -186,22 +180,16 @@ def bridge_sampling(chain, log_prob, log_prob_fn, seed=0, n_draws=None, neff=Non
     ``maxiter`` warns and sets ``converged`` to False."""
     a = _check(chain, log_prob, log_prob_fn, seed, n_draws, neff, log_prior_norm, tol, maxiter,
                discard, batch)
-    from .posterior import _Pool, _pool_chain, _taus, column_stats, ess
+    from .posterior import _taus, column_stats, ess
     from .plot import column_select
-    rows, nw, ndim, N1, N2 = a["rows"], a["nw"], a["ndim"], a["N1"], a["N2"]
-    pool = _pool_chain(chain, a["discard"])
-    ctx = pool.ctx
-    ld = nw * ndim
-    fit = _Pool(ctx, pool.ptr, pool.owner, a["discard"], a["h"], ld, ndim, nw, ndim)
-    post = _Pool(ctx, pool.ptr, pool.owner, a["discard"] + a["h"], a["n2"], ld, ndim, nw, ndim)
-    if isinstance(chain, tuple):
-        lp = log_prob[0] if isinstance(log_prob, tuple) else log_prob
-    else:
-        lp = ctx.array(np.ascontiguousarray(log_prob, dtype=np.float64))
+    nw, ndim, N1, N2 = a["nw"], a["ndim"], a["N1"], a["N2"]
+    chain = as_chain(chain, a["discard"], 2, logp=a["logp"])
+    ctx = chain.ctx
+    fit, post = chain.rows(0, a["h"]), chain.behind(a["h"])
 
     # the proposal: mean and covariance of the first half, its Cholesky factor
     mean_d, cov_d = ctx.empty((ndim,)), ctx.empty((ndim, ndim))
-    ctx.call("nh_chain_cov", *fit.args(), mean_d, cov_d)
+    ctx.call("nh_chain_cov", *fit.pooled(), mean_d, cov_d)
     mean, cov = mean_d.get(), cov_d.get()
     try:
         if not (np.all(np.isfinite(mean)) and np.all(np.isfinite(cov))):
@@ -214,14 +202,14 @@ def bridge_sampling(chain, log_prob, log_prob_fn, seed=0, n_draws=None, neff=Non
 
     # l1 = lnprob - log g at the second half
     l1 = ctx.empty((N1,))
-    ctx.call("nh_mvn_logpdf", *post.args(), mean_d, L_d, lp.ptr + 8 * post.row0 * nw, l1)
-    v1 = _vector(ctx, l1, N1)
+    ctx.call("nh_mvn_logpdf", *post.pooled(), mean_d, L_d, post.logp.ptr, l1)
+    v1 = matrix_on(l1, N1, 1)
     if int(column_stats(v1)["n"][0]) != N1:
         raise ValueError("the second half of the chain holds a non-finite log-probability or "
                          "sample (a walker that started outside the prior and has not moved in "
                          "yet? discard more rows, or start every walker inside)")
     if a["neff"] is None:
-        e = ess((pool.owner, rows, nw, ndim), "bulk", discard=post.row0)
+        e = ess(post, "bulk")
         if np.any(np.isfinite(e)):
             neff = min(float(np.nanmedian(e)), float(N1))
         else:
@@ -266,8 +254,9 @@ def bridge_sampling(chain, log_prob, log_prob_fn, seed=0, n_draws=None, neff=Non
     # the error, from the terms at the r reached
     f1, f2 = ctx.empty((N2,)), ctx.empty((N1,))
     ctx.call("nh_bridge_sums", l1, N1, l2, N2, lstar, s1, s2, r, sums, f1, f2)
-    m1, m2 = column_stats(_vector(ctx, f1, N2)), column_stats(_vector(ctx, f2, N1))
-    tau = float(_taus(ctx, f2, (a["n2"], nw, 1), 5)[0]) if a["n2"] > 1 else 1.0
+    m1, m2 = column_stats(matrix_on(f1, N2, 1)), column_stats(matrix_on(f2, N1, 1))
+    f2_chain = DeviceChain(matrix_on(f2, a["n2"], nw), nw, 1)  # (one parameter: f2 per walker)
+    tau = float(_taus(f2_chain, 5)[0]) if a["n2"] > 1 else 1.0
     with np.errstate(invalid="ignore", divide="ignore"):
         t1 = (m1["var"][0] / (m1["mean"][0] ** 2 * N2)) if N2 > 1 else 0.0
         t2 = (tau * m2["var"][0] / (m2["mean"][0] ** 2 * N1)) if N1 > 1 else 0.0
@@ -275,7 +264,7 @@ def bridge_sampling(chain, log_prob, log_prob_fn, seed=0, n_draws=None, neff=Non
 
     # importance sampling from the same draws: sum_j exp(l2_j - max l2) is the numerator's sum
     # with s1 = 0, s2 r = 1
-    top = float(column_stats(_vector(ctx, l2, N2))["max"][0])
+    top = float(column_stats(matrix_on(l2, N2, 1))["max"][0])
     ctx.call("nh_bridge_sums", l1, N1, l2, N2, top, 0.0, 1.0, 1.0, sums, None, None)
     logz_is = top + math.log(float(sums.get()[0])) - math.log(N2) - a["lpn"]
 
@@ -312,6 +301,5 @@ class EvidenceMixin:
 
         block = self._chain_block(1)
         if block is not None:
-            logp = self._dev.hist[0]["logp"]
-            return bridge_sampling(block, logp, fn, discard=discard, **kw)
+            return bridge_sampling(block, None, fn, discard=discard, **kw)
         return bridge_sampling(self.get_chain(), self.get_log_prob(), fn, discard=discard, **kw)

@@ -30,7 +30,7 @@ weight, which is 0 after the shift).  The tail lives in one workgroup's LDS: Mt 
 chain.
 
 Every function takes ``L`` as a host array ``(M, n_data)``, which is uploaded once per call, or
-as a device matrix: what ``pointwise_log_likelihood`` returns, a ``plot._Samples``, or
+as a device matrix: a ``dview.DeviceMatrix`` (what ``pointwise_log_likelihood`` returns), or
 ``(DeviceArray, M, ncol, ld)``.  Importing this module creates no GPU context; argument errors
 come before any device work.
 """
@@ -40,6 +40,7 @@ import warnings
 import numpy as np
 
 from ._lib import NH_PSIS_MAX_TAIL
+from .dview import as_matrix, matrix_on, matrix_shape
 
 __all__ = ["pointwise_log_likelihood", "waic", "loo", "compare", "tail_length", "PARETO_K_WARN"]
 
@@ -49,22 +50,6 @@ PARETO_K_WARN = 0.7  # above it the PSIS estimate of a point is not reliable (Ve
 # ---------------------------------------------------------------------------------------
 # host arithmetic
 # ---------------------------------------------------------------------------------------
-def _shape(x):
-    """(M, ncol) of a matrix argument, without a device: a device matrix as posterior._matrix
-    takes it, or a host array that must be 2-D"""
-    if hasattr(x, "M") and hasattr(x, "ncol"):
-        return int(x.M), int(x.ncol)
-    if isinstance(x, tuple) and len(x) == 4 and not np.isscalar(x[0]) and hasattr(x[0], "ptr"):
-        return int(x[1]), int(x[2])
-    s = np.shape(x)
-    if len(s) != 2:
-        raise ValueError("a pointwise matrix must be 2-D (samples, data points); got shape %s"
-                         % (tuple(s),))
-    if s[0] == 0 or s[1] == 0:
-        raise ValueError("no samples")
-    return int(s[0]), int(s[1])
-
-
 def tail_length(M, reff=1.0):
     """Mt = min(M // 5, ceil(3 sqrt(M / reff))), the number of largest importance ratios the
     generalised Pareto distribution is fitted to; ``reff`` is the relative efficiency of the
@@ -137,7 +122,7 @@ def compare(results, names=None, ic="loo"):
 # ---------------------------------------------------------------------------------------
 def _model_values(model, data, unit):
     """(values, unit, M, nE) of a model argument -- a ``Quantity`` (M, n_data), or a matrix as
-    ``posterior._matrix`` accepts it together with its ``unit`` -- checked against the data
+    ``dview.as_matrix`` accepts it together with its ``unit`` -- checked against the data
     table, without a device"""
     from . import units as u
     if isinstance(model, u.Quantity):
@@ -149,7 +134,7 @@ def _model_values(model, data, unit):
     if unit is None:
         raise ValueError("a model that is not a Quantity needs unit=")
     unit = u.Unit(unit)
-    M, nE = _shape(values)
+    M, nE = matrix_shape(values, pointwise=True)
     n_data = int(np.size(data["flux"].value))
     if nE != n_data:
         raise ValueError("model has %d energies, data table has %d" % (nE, n_data))
@@ -163,15 +148,13 @@ def pointwise_log_likelihood(model, data, unit=None, totals=False):
     a device matrix handle (``.get()`` downloads it; ``waic`` and ``loo`` take it as it is).
 
     ``model`` is a ``Quantity`` (M, n_data) in host memory, or a device matrix as
-    ``posterior._matrix`` accepts it together with its ``unit``; the conversion to the data's
+    ``dview.as_matrix`` accepts it together with its ``unit``; the conversion to the data's
     unit is ``core._conversion_to_data``, the one the fit itself used (SED <-> differential
     included).  ``totals=True`` returns (L, row sums as a device array [M]) instead.  A
     non-finite term raises ``ValueError`` with their number."""
     from .core import _data_on_device
-    from .plot import _Samples
-    from .posterior import _matrix
     values, unit, M, nE = _model_values(model, data, unit)
-    s = _matrix(values)
+    s = as_matrix(values)
     ctx = s.ctx
     dd = _data_on_device(ctx, data)
     L = ctx.empty((M, nE))
@@ -183,7 +166,7 @@ def pointwise_log_likelihood(model, data, unit=None, totals=False):
     if bad:
         raise ValueError("%d of the %d pointwise log-likelihood terms are not finite (a NaN in a "
                          "spectrum, a zero error, cl = 1?)" % (bad, M * nE))
-    out = _Samples(ctx, L.ptr, M, nE, nE, L)
+    out = matrix_on(L, M, nE)
     return (out, total) if totals else out
 
 
@@ -202,9 +185,8 @@ def waic(L):
     their sums ``elpd_waic`` and ``p_waic`` (and ``lppd``), ``se = sqrt(n_data var(elpd_waic_i,
     ddof=1))``, ``n_samples`` and ``n_data``.  elpd is on the log-score scale (multiply by -2 for
     the deviance scale) and defined up to the data table's constant (module docstring)."""
-    from .posterior import _matrix
-    M, nE = _shape(L)
-    s = _matrix(L)
+    M, nE = matrix_shape(L, pointwise=True)
+    s = as_matrix(L)
     st = _column_stats(s).get()
     lppd_i = st[3] - math.log(M)
     p_i = st[2]
@@ -223,11 +205,9 @@ def loo(L, reff=1.0):
     ``get_autocorr_time`` for a thinned-by-one chain); it only sets the tail length.  Warns when
     a ``pareto_k`` exceeds 0.7, naming how many points."""
     import ctypes as C
-
-    from .posterior import _matrix
-    M, nE = _shape(L)
+    M, nE = matrix_shape(L, pointwise=True)
     Mt = tail_length(M, reff)
-    s = _matrix(L)
+    s = as_matrix(L)
     ctx = s.ctx
     stats = _column_stats(s)
     lsel = ctx.empty((1, nE))

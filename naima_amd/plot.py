@@ -20,6 +20,7 @@ import numpy as np
 
 from . import units as u
 from .core import sed_conversion
+from .dview import DeviceMatrix, as_matrix, matrix_on
 from .validator import validate_array
 
 __all__ = ["plot_chain", "plot_fit", "plot_data", "plot_blob", "plot_corner"]
@@ -109,28 +110,8 @@ def _split_model(blob, energy, modelidx):
     raise TypeError("Model {0} has wrong blob format".format(modelidx))
 
 
-class _Samples:
-    """samples x energies on the device: row-major buffer of M rows, ncol columns, stride ld"""
-
-    def __init__(self, ctx, ptr, M, ncol, ld, keep):
-        self.ctx, self.ptr, self.M, self.ncol, self.ld, self.keep = ctx, ptr, M, ncol, ld, keep
-
-    def get(self):
-        from . import _lib
-        host = np.empty((self.M, self.ld))
-        if host.nbytes:
-            _lib._chk(_lib._lib.nh_download(self.ctx.h, host.ctypes.data, self.ptr, host.nbytes))
-        return host[:, :self.ncol]
-
-
-def _host_samples(ctx, model):
-    a = np.ascontiguousarray(np.asarray(model, dtype=float).reshape(len(model), -1))
-    buf = ctx.array(a)
-    return _Samples(ctx, buf.ptr, a.shape[0], a.shape[1], a.shape[1], buf)
-
-
 def _evaluate_device(ctx, sampler, pars, data, modelidx):
-    """one model call on device parameters -> (modelx, unit, _Samples), or None when the model
+    """one model call on device parameters -> (modelx, unit, DeviceMatrix), or None when the model
     cannot take them (what EnsembleSampler._probe_device catches)"""
     from .darray import DEbl, DMat, DPars
     n = len(pars)
@@ -148,7 +129,7 @@ def _evaluate_device(ctx, sampler, pars, data, modelidx):
         return None
     _check_shape(d.shape, n, modelx, modelidx)
     buf, ptr = d.buffer()
-    return modelx, q.unit, _Samples(ctx, ptr, n, d.shape[1], d.shape[1], buf)
+    return modelx, q.unit, DeviceMatrix(ctx, ptr, n, d.shape[1], d.shape[1], buf)
 
 
 def _check_shape(shape, n, modelx, modelidx):
@@ -165,17 +146,17 @@ def _evaluate_host(ctx, sampler, pars, data, modelidx):
     modelx, q = _split_model(_pick(out, modelidx), data["energy"], modelidx)
     v = np.asarray(q.value, dtype=float)
     _check_shape(v.shape, len(pars), modelx, modelidx)
-    return modelx, q.unit, _host_samples(ctx, v)
+    return modelx, q.unit, as_matrix(v)
 
 
 def _samples_on_device(sampler, modelidx=0, n_samples=100, last_step=False, e_range=None,
                        e_npoints=100, seed=None, batch=None):
-    """(modelx, unit, _Samples): the stored blob history uploaded once, or ``n_samples``
+    """(modelx, unit, DeviceMatrix): the stored blob history uploaded once, or ``n_samples``
     fresh model evaluations at parameters drawn from the chain, on the device"""
     from . import _lib
     if e_range is None:
         modelx, model = _process_blob(sampler, modelidx, last_step=last_step)
-        return modelx, model.unit, _host_samples(_lib.get_context(), model.value)
+        return modelx, model.unit, as_matrix(model.value)
     _, data = _energy_grid(sampler, e_range, e_npoints)
     pars = _draw(sampler, n_samples, last_step, seed)
     ctx = _lib.get_context()
@@ -189,14 +170,13 @@ def _samples_on_device(sampler, modelidx=0, n_samples=100, last_step=False, e_ra
         mx, un, s = _evaluate(ctx, sampler, pars[a:a + batch], data, modelidx)
         if whole is None:
             modelx, unit = mx, un
-            whole = ctx.empty((len(pars), s.ncol))
-        elif un != unit or s.ncol != whole.shape[1]:
+            whole = matrix_on(ctx.empty((len(pars), s.ncol)), len(pars), s.ncol)
+        elif un != unit or s.ncol != whole.ncol:
             raise TypeError("Model {0} has wrong blob format: chunks of draws differ in unit or "
                             "length".format(modelidx))
-        ctx.call("nh_copy", whole.ptr + 8 * a * s.ncol, s.ptr, 8 * s.M * s.ncol)
+        ctx.call("nh_copy", whole.rows(a, a + s.M).ptr, s.ptr, 8 * s.M * s.ncol)
         del s
-    m = whole.shape[1]
-    return modelx, unit, _Samples(ctx, whole.ptr, len(pars), m, m, whole)
+    return modelx, unit, whole
 
 
 def _evaluate(ctx, sampler, pars, data, modelidx):
@@ -220,11 +200,9 @@ def _read_or_calc_samples(sampler, modelidx=0, n_samples=100, last_step=False, e
 
 def column_select(samples, ranks):
     """out[r][c] = np.sort(samples[:, c])[ranks[r]] by nh_column_select (16 ranks per launch);
-    ``samples`` is a _Samples or a host array [M][m]"""
-    from . import _lib
+    ``samples`` is a DeviceMatrix or a host array [M][m]"""
     import ctypes as C
-    if not isinstance(samples, _Samples):
-        samples = _host_samples(_lib.get_context(), samples)
+    samples = as_matrix(samples)
     ctx = samples.ctx
     ranks = [int(r) for r in ranks]
     out = np.empty((len(ranks), samples.ncol))
@@ -353,7 +331,7 @@ def _posterior_hist(ax, dist, label, title):
     posterior.gaussian_kde) over one upload of ``dist``."""
     from . import posterior
     nbins = int(np.clip(np.sqrt(dist.size), 25, 100))
-    s = posterior._matrix(dist)
+    s = as_matrix(dist)
     counts, edges = posterior.histogram(s, bins=nbins)
     counts, edges = counts[0], edges[0]
     heights = counts / (counts.sum() * np.diff(edges))  # (np.histogram's density=True)
@@ -715,14 +693,13 @@ def plot_ppc(sampler, modelidx=0, confs=(0.68, 0.95), seed=0, sed=True, figure=N
     bands -- and below them the probability integral transform of every flux point; the three
     Bayesian p-values in the title.  Replicates, quantiles and statistics are taken on the GPU."""
     from .infocrit import sampler_spectra
-    from .posterior import _matrix
     from .predictive import posterior_predictive, ppc, predictive_quantiles
     confs = sorted((float(c) for c in confs), reverse=True)
     if not confs or not all(0.0 < c < 1.0 for c in confs):
         raise ValueError("confs must be probabilities in (0, 1)")
     import matplotlib.pyplot as plt
     model, data = sampler_spectra(sampler, modelidx=modelidx)
-    spectra = _matrix(model.value)  # (uploaded once for both calls)
+    spectra = as_matrix(model.value)  # (uploaded once for both calls)
     res = ppc(spectra, data, unit=model.unit, seed=seed)
     y = posterior_predictive(spectra, data, unit=model.unit, seed=seed)
     q = [0.5] + [v for c in confs for v in ((1.0 - c) / 2.0, (1.0 + c) / 2.0)]

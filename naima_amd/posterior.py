@@ -9,7 +9,8 @@ fallback for the reductions; only the edges, the bandwidths and the contour leve
 counts are host arithmetic.
 
 Every function takes a host array ``(M,)`` or ``(M, ncol)``, which is uploaded once per call, or a
-device matrix: a ``plot._Samples``, or ``(DeviceArray, M, ncol, ld)``.
+device matrix: a ``dview.DeviceMatrix``, or ``(DeviceArray, M, ncol, ld)``; a chain is a host array
+``(rows, nwalkers, ndim)``, a ``dview.DeviceChain`` or ``(DeviceArray, rows, nwalkers, ndim)``.
 
 ``group_moments`` and ``rhat`` read a chain of several independent ensembles
 (``EnsembleSampler(..., ensembles=k)``): per (part of the rows, ensemble, parameter) the device
@@ -34,6 +35,8 @@ import numpy as np
 
 from ._lib import (NH_EVID_MAX_DIM, NH_HIST_MAX_BINS_1D, NH_HIST_MAX_BINS_2D, NH_HIST_MAX_COLS,
                    NH_HIST_MAX_PAIRS)
+from .dview import (DeviceChain, DeviceMatrix, as_chain, as_matrix, chain_dims, matrix_on,
+                    matrix_shape)
 
 __all__ = ["column_stats", "histogram", "histogram_pairs", "gaussian_kde", "contour_thresholds",
            "corner", "DEFAULT_LEVELS", "group_moments", "rhat", "rhat_from_moments",
@@ -142,44 +145,10 @@ def contour_thresholds(H, levels=None):
 # ---------------------------------------------------------------------------------------
 # device
 # ---------------------------------------------------------------------------------------
-def _matrix(x):
-    """x as a plot._Samples (ctx, ptr, M, ncol, ld)"""
-    from . import _lib
-    from .plot import _Samples
-    if isinstance(x, _Samples):
-        return x
-    if isinstance(x, tuple) and len(x) == 4 and isinstance(x[0], _lib.DeviceArray):
-        dev, M, ncol, ld = x[0], int(x[1]), int(x[2]), int(x[3])
-        if M < 1 or ncol < 1 or ld < ncol or M * ld * 8 > dev.nbytes:
-            raise ValueError("a device matrix of %d x %d (ld %d) does not fit its buffer"
-                             % (M, ncol, ld))
-        return _Samples(dev.ctx, dev.ptr, M, ncol, ld, dev)
-    a = np.asarray(x, dtype=np.float64)
-    if a.ndim == 1:
-        a = a[:, np.newaxis]
-    if a.ndim != 2:
-        raise ValueError("samples must be (M,) or (M, ncol)")
-    if a.shape[0] == 0 or a.shape[1] == 0:
-        raise ValueError("no samples")
-    ctx = _lib.get_context()
-    buf = ctx.array(np.ascontiguousarray(a))
-    return _Samples(ctx, buf.ptr, a.shape[0], a.shape[1], a.shape[1], buf)
-
-
-def _shape(x):
-    """(M, ncol) of what _matrix would make of x, without a device"""
-    if hasattr(x, "M") and hasattr(x, "ncol"):
-        return x.M, x.ncol
-    if isinstance(x, tuple) and len(x) == 4 and not np.isscalar(x[0]) and hasattr(x[0], "ptr"):
-        return int(x[1]), int(x[2])
-    s = np.shape(x)
-    return (s[0], 1) if len(s) == 1 else tuple(s)
-
-
 def column_stats(x):
     """Per column: ``n`` finite values, ``n_nan`` NaNs (int64), and ``min``, ``max``, ``mean``,
     ``var`` (unbiased, ddof=1) of the finite values, as a dict of arrays [ncol]."""
-    s = _matrix(x)
+    s = as_matrix(x)
     ctx = s.ctx
     counts, stats = ctx.empty((2, s.ncol), np.int64), ctx.empty((4, s.ncol))
     ctx.call("nh_column_moments", s.ptr, s.M, s.ncol, s.ld, counts, stats)
@@ -213,8 +182,8 @@ def histogram(x, bins=20, range=None):
     column's finite minimum and maximum.  NaN, +-inf and values outside the range are dropped."""
     bins = _check_bins(bins, False)
     if range is not None:
-        _range(range, _shape(x)[1])
-    h1, _, edges = _histograms(_matrix(x), bins, range, [])
+        _range(range, matrix_shape(x)[1])
+    h1, _, edges = _histograms(as_matrix(x), bins, range, [])
     return h1, edges
 
 
@@ -223,11 +192,11 @@ def histogram_pairs(x, bins=20, range=None, pairs=None):
     (default: every i < j): (H int64 [npairs][bins][bins], pairs, edges [ncol][bins+1]), with
     ``H[p][a][b]`` counting the rows in bin a of column i and bin b of column j."""
     bins = _check_bins(bins, True)
-    ncol = _shape(x)[1]
+    ncol = matrix_shape(x)[1]
     pairs = _check_pairs(pairs, ncol)
     if range is not None:
         _range(range, ncol)
-    _, H, edges = _histograms(_matrix(x), bins, range, pairs)
+    _, H, edges = _histograms(as_matrix(x), bins, range, pairs)
     return H, pairs, edges
 
 
@@ -236,7 +205,7 @@ def gaussian_kde(x, points, bw_method=None):
     ``points`` is (G,) for every column or (ncol, G); ``bw_method`` None / "scott", "silverman"
     or a scalar factor; the bandwidth is factor * sqrt(var) over the column's finite values."""
     _bandwidth_factor(bw_method, 2.0)
-    s = _matrix(x)
+    s = as_matrix(x)
     p = np.asarray(points, dtype=np.float64)
     if p.ndim == 1:
         p = np.tile(p, (s.ncol, 1))
@@ -255,26 +224,14 @@ def gaussian_kde(x, points, bw_method=None):
 # Gelman-Rubin R-hat over independent ensembles
 # ---------------------------------------------------------------------------------------
 def _chain_shape(x, ensembles, discard, nsplit):
-    """(rows, nwalkers, ndim, k, n) of a host chain (rows, nwalkers, ndim) or of a device block
-    ``(DeviceArray [rows at least][nwalkers * ndim], rows, nwalkers, ndim)``, checked without a
-    device"""
+    """(rows, nwalkers, ndim, k, n) of a chain as ``dview.chain_dims`` takes it that holds
+    ``ensembles`` = k ensembles of n walkers, checked without a device"""
     if isinstance(ensembles, bool) or not isinstance(ensembles, (int, np.integer)):
         raise ValueError("ensembles must be an integer")
     k = int(ensembles)
     if k < 2:
         raise ValueError("R-hat compares independent ensembles: ensembles must be at least 2")
-    if isinstance(x, tuple):
-        if len(x) != 4 or not hasattr(x[0], "ptr"):
-            raise ValueError("a device chain is (DeviceArray, rows, nwalkers, ndim)")
-        rows, nw, ndim = (int(v) for v in x[1:])
-        if rows < 0 or nw < 1 or ndim < 1 or rows * nw * ndim * 8 > x[0].nbytes:
-            raise ValueError("a device chain of %d x %d x %d does not fit its buffer"
-                             % (rows, nw, ndim))
-    else:
-        shape = np.shape(x)
-        if len(shape) != 3:
-            raise ValueError("a chain must be (rows, nwalkers, ndim)")
-        rows, nw, ndim = shape
+    rows, nw, ndim = chain_dims(x)
     if nw % k:
         raise ValueError("%d walkers do not split into %d ensembles" % (nw, k))
     if ndim > 256:
@@ -290,31 +247,26 @@ def _chain_shape(x, ensembles, discard, nsplit):
 
 def group_moments(x, ensembles, discard=0, nsplit=1):
     """The chain ``x`` -- a host array (rows, nwalkers, ndim) as ``get_chain()`` returns it, which
-    is uploaded, or a device block ``(DeviceArray, rows, nwalkers, ndim)`` laid out
-    [rows][nwalkers * ndim] -- holds ``ensembles`` = k ensembles, walkers [r n, (r+1) n) being
+    is uploaded, a ``dview.DeviceChain`` or the block ``(DeviceArray, rows, nwalkers, ndim)`` laid
+    out [rows][nwalkers * ndim] -- holds ``ensembles`` = k ensembles, walkers [r n, (r+1) n) being
     ensemble r.  The rows behind ``discard`` are cut into ``nsplit`` equal parts (a remainder is
     dropped from the front); per (part, ensemble, parameter), all walkers of the ensemble pooled:
     ``n`` finite values (int64), their ``mean`` and ``var`` (unbiased), arrays [nsplit][k][ndim],
     and ``draws``, the number of values of each such sequence."""
-    from . import _lib
     nsplit = int(nsplit)
     if nsplit < 1:
         raise ValueError("nsplit must be at least 1")
-    rows, nw, ndim, k, n = _chain_shape(x, ensembles, discard, nsplit)
-    if isinstance(x, tuple):
-        buf = x[0]
-        ctx = buf.ctx
-    else:
-        ctx = _lib.get_context()
-        buf = ctx.array(np.ascontiguousarray(x, dtype=np.float64).reshape(rows, nw * ndim))
+    _, nw, ndim, k, n = _chain_shape(x, ensembles, discard, nsplit)
+    m = as_chain(x, discard).m
+    ctx = m.ctx
     nq = nsplit * k * ndim
     counts, stats = ctx.empty((nq,), np.int64), ctx.empty((2, nq))
-    ctx.call("nh_group_moments", buf, int(discard), rows - int(discard), nw * ndim, k, n, ndim,
-             nsplit, counts, stats)
+    ctx.call("nh_group_moments", m.base, m.row0, m.M, nw * ndim, k, n, ndim, nsplit, counts,
+             stats)
     c, v = counts.get(), stats.get()
     shape = (nsplit, k, ndim)
     return dict(n=c.reshape(shape), mean=v[0].reshape(shape), var=v[1].reshape(shape),
-                draws=(rows - int(discard)) // nsplit * n)
+                draws=m.M // nsplit * n)
 
 
 def rhat_from_moments(count, mean, var, draws):
@@ -354,12 +306,11 @@ def rhat(x, ensembles, discard=0, split=True, method="moments", folded=True):
     nsplit = 2 if split else 1
     if method == "moments":
         return _rhat_moments(x, ensembles, discard, nsplit)
-    rows, nw, ndim, k, _ = _chain_shape(x, ensembles, discard, nsplit)
-    pool = _pool_chain(x, discard)
-    out = _rhat_moments((_z_chain(pool), pool.nrows, nw, ndim), k, 0, nsplit)
+    k = _chain_shape(x, ensembles, discard, nsplit)[3]
+    chain = as_chain(x, discard)
+    out = _rhat_moments(_z_chain(chain), k, 0, nsplit)
     if folded:
-        out = np.maximum(out, _rhat_moments((_z_chain(_folded(pool)), pool.nrows, nw, ndim), k, 0,
-                                            nsplit))
+        out = np.maximum(out, _rhat_moments(_z_chain(_folded(chain)), k, 0, nsplit))
     return out
 
 
@@ -390,152 +341,91 @@ def _quantiles(s, q):
 # ---------------------------------------------------------------------------------------
 # rank-normalised statistics (Vehtari, Gelman, Simpson, Carpenter & Buerkner 2021)
 # ---------------------------------------------------------------------------------------
-class _Pool:
-    """pooled columns of a device matrix as nh_rank_columns takes them: element t * npool + j of
-    column p is x[(row0 + t) * ld + j * cstride + p]; ``owner`` keeps the buffer alive"""
-    __slots__ = ("ctx", "ptr", "owner", "row0", "nrows", "ld", "cstride", "npool", "ncolp")
-
-    def __init__(self, ctx, ptr, owner, row0, nrows, ld, cstride, npool, ncolp):
-        self.ctx, self.ptr, self.owner = ctx, ptr, owner
-        self.row0, self.nrows, self.ld = int(row0), int(nrows), int(ld)
-        self.cstride, self.npool, self.ncolp = int(cstride), int(npool), int(ncolp)
-
-    @property
-    def S(self):
-        return self.nrows * self.npool
-
-    def args(self):
-        return (self.ptr, self.row0, self.nrows, self.ld, self.cstride, self.npool, self.ncolp)
-
-    def flat(self):
-        """the pooled columns as the columns of a plot._Samples: rows behind row0; a chain whose
-        rows are exactly [walker][parameter] is the matrix [rows * walkers][parameters]"""
-        from .plot import _Samples
-        assert self.npool == 1 or (self.cstride == self.ncolp and self.ld == self.npool * self.ncolp)
-        ld = self.ld if self.npool == 1 else self.ncolp
-        return _Samples(self.ctx, self.ptr + 8 * self.row0 * self.ld, self.S, self.ncolp, ld,
-                        self.owner)
-
-
-def _is_chain_tuple(x):
-    return isinstance(x, tuple) and len(x) == 4 and hasattr(x[0], "ptr")
-
-
-def _chain_dims(x, discard, least=1):
-    """(rows, nwalkers, ndim) of a host chain or of a device block ``(DeviceArray, rows, nwalkers,
-    ndim)``, with at least ``least`` rows behind ``discard``; checked without a device"""
-    if isinstance(x, tuple):
-        if not _is_chain_tuple(x):
-            raise ValueError("a device chain is (DeviceArray, rows, nwalkers, ndim)")
-        rows, nw, ndim = (int(v) for v in x[1:])
-        if rows < 0 or nw < 1 or ndim < 1 or rows * nw * ndim * 8 > x[0].nbytes:
-            raise ValueError("a device chain of %d x %d x %d does not fit its buffer"
-                             % (rows, nw, ndim))
-    else:
-        shape = np.shape(x)
-        if len(shape) != 3:
-            raise ValueError("a chain must be (rows, nwalkers, ndim)")
-        rows, nw, ndim = shape
-        if nw < 1 or ndim < 1:
-            raise ValueError("the chain has no walkers or no parameters")
-    discard = int(discard)
-    if discard < 0:
-        raise ValueError("discard must not be negative")
-    if rows - discard < least:
-        raise ValueError("%d rows behind discard = %d: %d needed at least"
-                         % (max(0, rows - discard), discard, least))
-    return rows, nw, ndim
-
-
-def _pool_chain(x, discard=0):
-    """the parameters of a chain, every walker pooled, behind ``discard`` rows"""
-    from . import _lib
-    rows, nw, ndim = _chain_dims(x, discard)
-    if isinstance(x, tuple):
-        buf = x[0]
-        ctx = buf.ctx
-    else:
-        ctx = _lib.get_context()
-        buf = ctx.array(np.ascontiguousarray(x, dtype=np.float64).reshape(rows, nw * ndim))
-    return _Pool(ctx, buf.ptr, buf, int(discard), rows - int(discard), nw * ndim, ndim, nw, ndim)
-
-
-def _pool_any(x, discard=0):
-    """(pool, shape of the result): a chain (3-D host array), else a matrix as ``_matrix`` takes it"""
-    if not isinstance(x, tuple) and not hasattr(x, "ncol") and len(np.shape(x)) == 3:
-        pool = _pool_chain(x, discard)
-        return pool, (pool.nrows, pool.npool, pool.ncolp)
-    M, ncol = _shape(x)
+def _dims(x, discard, tuple_is_chain=False):
+    """the shape of ``x[discard:]``, checked without a device: (rows, nwalkers, ndim) of a chain
+    -- a DeviceChain, a 3-D host array, a legacy tuple where the caller reads one as a chain
+    (``dview``'s docstring) -- else (M, ncol) of a matrix"""
+    if (tuple_is_chain and isinstance(x, tuple)) or isinstance(x, DeviceChain) or \
+            not isinstance(x, (tuple, DeviceMatrix)) and len(np.shape(x)) == 3:
+        rows, nw, ndim = chain_dims(x, discard, 1)
+        return rows - int(discard), nw, ndim
+    M, ncol = matrix_shape(x)
     discard = int(discard)
     if discard < 0:
         raise ValueError("discard must not be negative")
     if M - discard < 1:
         raise ValueError("no samples behind discard = %d" % discard)
-    s = _matrix(x)
-    return (_Pool(s.ctx, s.ptr, s, discard, s.M - discard, s.ld, 0, 1, s.ncol),
-            (s.M - discard, s.ncol))
+    return M - discard, ncol
 
 
-def _ranks(pool):
-    """(r [S][ncolp], status int32 [ncolp]) on the device"""
-    ctx = pool.ctx
-    r, status = ctx.empty((pool.S, pool.ncolp)), ctx.empty((pool.ncolp,), np.int32)
-    ctx.call("nh_rank_columns", *pool.args(), r, status)
+def _view(x, discard, shape):
+    """the view of ``x`` behind ``discard`` rows, ``shape`` being what ``_dims`` made of it"""
+    if len(shape) == 3:
+        return as_chain(x, discard)
+    return as_matrix(x).rows(discard, discard + shape[0])
+
+
+def _like(v, buf):
+    """the device array ``buf`` [nrows][nwalkers * ndim] as a view of ``v``'s kind and shape"""
+    m = matrix_on(buf, v.nrows, v.nwalkers * v.ndim)
+    return DeviceChain(m, v.nwalkers, v.ndim) if isinstance(v, DeviceChain) else m
+
+
+def _ranks(v):
+    """(r [S][ndim], status int32 [ndim]) on the device"""
+    ctx = v.ctx
+    r, status = ctx.empty((v.S, v.ndim)), ctx.empty((v.ndim,), np.int32)
+    ctx.call("nh_rank_columns", *v.pooled(), r, status)
     return r, status
 
 
-def _z_chain(pool):
-    """the normal scores of the pooled ranks in the chain's layout, [nrows][npool * ncolp]"""
+def _z_chain(v):
+    """the normal scores of the pooled ranks in the chain's layout, as a view like ``v``"""
     from ._lib import NH_RANK_CHAIN
-    ctx = pool.ctx
-    r, _ = _ranks(pool)
-    z = ctx.empty((pool.nrows, pool.npool * pool.ncolp))
-    ctx.call("nh_rank_normal_scores", r, pool.nrows, pool.npool, pool.ncolp, NH_RANK_CHAIN,
-             pool.npool * pool.ncolp, pool.ncolp, z)
-    return z
+    ctx, ld = v.ctx, v.nwalkers * v.ndim
+    r, _ = _ranks(v)
+    z = ctx.empty((v.nrows, ld))
+    ctx.call("nh_rank_normal_scores", r, v.nrows, v.nwalkers, v.ndim, NH_RANK_CHAIN, ld, v.ndim, z)
+    return _like(v, z)
 
 
-def _transformed(pool, thr, mode):
-    """the chain-layout block [nrows][npool * ncolp] of |x - thr| or x <= thr, as a pool"""
-    ctx = pool.ctx
-    ld = pool.npool * pool.ncolp
-    out = ctx.empty((pool.nrows, ld))
-    ctx.call("nh_rank_transform", *pool.args(), ctx.array(np.ascontiguousarray(thr, dtype=float)),
-             mode, out, ld)
-    return _Pool(ctx, out.ptr, out, 0, pool.nrows, ld, pool.ncolp, pool.npool, pool.ncolp)
+def _transformed(chain, thr, mode):
+    """the chain |x - thr| or x <= thr"""
+    ctx, ld = chain.ctx, chain.nwalkers * chain.ndim
+    out = ctx.empty((chain.nrows, ld))
+    ctx.call("nh_rank_transform", *chain.pooled(),
+             ctx.array(np.ascontiguousarray(thr, dtype=float)), mode, out, ld)
+    return _like(chain, out)
 
 
-def _median(pool):
-    """np.median of every pooled column: the mean of the two middle order statistics"""
-    from .plot import column_select
-    S = pool.S
-    v = column_select(pool.flat(), [(S - 1) // 2, S // 2])
-    return 0.5 * (v[0] + v[1])
-
-
-def _folded(pool):
+def _folded(chain):
+    """the chain |x - median|, np.median of every parameter's pooled values"""
     from ._lib import NH_RANK_FOLD
-    return _transformed(pool, _median(pool), NH_RANK_FOLD)
+    from .plot import column_select
+    v = column_select(chain.flat(), [(chain.S - 1) // 2, chain.S // 2])  # (the two middle ones)
+    return _transformed(chain, 0.5 * (v[0] + v[1]), NH_RANK_FOLD)
 
 
 def rank_columns(x, discard=0, device=False):
     """``scipy.stats.rankdata(col, method="average")`` of every column of ``x``, ranked on the GPU
     (``nh_rank_columns``): 1-based ranks, equal values -- a rejected move repeats a walker's value
     -- share the mean of the positions they occupy, -0.0 equals +0.0.  ``x`` is a matrix ``(M,)``
-    or ``(M, ncol)`` (host, a ``plot._Samples`` or ``(DeviceArray, M, ncol, ld)``), or a host chain
-    ``(rows, nwalkers, ndim)``, of which every parameter is ranked over all walkers and rows
-    (``chain[discard:, :, d].ravel()``); the result has the shape of ``x[discard:]``.  A column
-    with a NaN or an infinite value is NaN throughout.  ``device=True`` returns the device block
-    ``(DeviceArray [M][ncol], M, ncol, ncol)``, a chain's M being rows x walkers."""
-    pool, shape = _pool_any(x, discard)
-    r, _ = _ranks(pool)
-    return (r, pool.S, pool.ncolp, pool.ncolp) if device else r.get().reshape(shape)
+    or ``(M, ncol)`` (host, a ``dview.DeviceMatrix`` or ``(DeviceArray, M, ncol, ld)``), or a chain
+    ``(rows, nwalkers, ndim)`` (host, or a ``dview.DeviceChain``), of which every parameter is
+    ranked over all walkers and rows (``chain[discard:, :, d].ravel()``); the result has the shape
+    of ``x[discard:]``.  A column with a NaN or an infinite value is NaN throughout.
+    ``device=True`` returns the device block ``(DeviceArray [M][ncol], M, ncol, ncol)``, a chain's
+    M being rows x walkers."""
+    shape = _dims(x, discard)
+    v = _view(x, discard, shape)
+    r, _ = _ranks(v)
+    return (r, v.S, v.ndim, v.ndim) if device else r.get().reshape(shape)
 
 
 def rank_normalize(x, ensembles=1, discard=0, device=False):
     """The rank-normalised scores ``z = ndtri((r - 3/8) / (S + 1/4))`` of ``x``, ``r`` being
     ``rank_columns``' ranks and ``S`` the number of values ranked together (Blom's offsets, as in
-    Vehtari et al. 2021).  ``x`` is what ``rank_columns`` takes, or a device chain
+    Vehtari et al. 2021).  ``x`` is what ``rank_columns`` takes, except that a tuple is the chain
     ``(DeviceArray, rows, nwalkers, ndim)`` as ``group_moments`` takes it; a chain is ranked over
     all walkers of all ``ensembles`` (which must divide the walkers) and comes back in the chain's
     layout, ``(rows - discard, nwalkers, ndim)`` -- with ``device=True`` as the block
@@ -543,27 +433,21 @@ def rank_normalize(x, ensembles=1, discard=0, device=False):
     ``(DeviceArray, M, ncol, ncol)``."""
     if isinstance(ensembles, bool) or not isinstance(ensembles, (int, np.integer)) or ensembles < 1:
         raise ValueError("ensembles must be a positive integer")
-    # (a 4-tuple is read as a chain here, as group_moments reads it)
-    if isinstance(x, tuple) or (not hasattr(x, "ncol") and len(np.shape(x)) == 3):
-        _, nw, _ = _chain_dims(x, discard)
-        if nw % int(ensembles):
-            raise ValueError("%d walkers do not split into %d ensembles" % (nw, int(ensembles)))
-        pool = _pool_chain(x, discard)
-        shape = (pool.nrows, pool.npool, pool.ncolp)
-    else:
-        pool, shape = _pool_any(x, discard)
-    z = _z_chain(pool)
+    shape = _dims(x, discard, True)
+    if len(shape) == 3 and shape[1] % int(ensembles):
+        raise ValueError("%d walkers do not split into %d ensembles" % (shape[1], int(ensembles)))
+    z = _z_chain(_view(x, discard, shape)).owner
     if device:
         return (z,) + tuple(shape) if len(shape) == 3 else (z, shape[0], shape[1], shape[1])
     return z.get().reshape(shape)
 
 
-def _taus(ctx, dx, shape, c):
-    """emcee's integrated autocorrelation time of every parameter of the device chain dx
-    [rows][nwalkers * ndim], the autocorrelation function averaged over the walkers
+def _taus(chain, c):
+    """emcee's integrated autocorrelation time of every parameter of a DeviceChain, the
+    autocorrelation function averaged over the walkers
     (``autocorr.integrated_time(..., tol=0, quiet=True)``)"""
     from .autocorr import _dimension
-    return np.array([_dimension(ctx, dx, shape, d, c)[0] for d in range(shape[2])], dtype=float)
+    return np.array([_dimension(chain, d, c)[0] for d in range(chain.ndim)], dtype=float)
 
 
 def _check_kind(kind):
@@ -571,22 +455,20 @@ def _check_kind(kind):
         raise ValueError("kind must be 'bulk' or 'tail', not %r" % (kind,))
 
 
-def _ess_bulk(pool, c, z=None):
-    shape = (pool.nrows, pool.npool, pool.ncolp)
-    return pool.S / _taus(pool.ctx, _z_chain(pool) if z is None else z, shape, c)
+def _ess_bulk(chain, c, z=None):
+    return chain.S / _taus(_z_chain(chain) if z is None else z, c)
 
 
-def _ess_tail(pool, c):
+def _ess_tail(chain, c):
     from ._lib import NH_RANK_LE
-    shape = (pool.nrows, pool.npool, pool.ncolp)
-    q = _quantiles(pool.flat(), [0.05, 0.95])
-    tau = [_taus(pool.ctx, _transformed(pool, qq, NH_RANK_LE).owner, shape, c) for qq in q]
-    return np.minimum(pool.S / tau[0], pool.S / tau[1])
+    q = _quantiles(chain.flat(), [0.05, 0.95])
+    tau = [_taus(_transformed(chain, qq, NH_RANK_LE), c) for qq in q]
+    return np.minimum(chain.S / tau[0], chain.S / tau[1])
 
 
 def ess(x, kind="bulk", discard=0, c=5):
-    """The effective sample size of each parameter of a chain ``(rows, nwalkers, ndim)`` (host, or
-    the device block ``(DeviceArray, rows, nwalkers, ndim)``): ``S / tau`` with
+    """The effective sample size of each parameter of a chain ``(rows, nwalkers, ndim)`` (host, a
+    ``dview.DeviceChain`` or the block ``(DeviceArray, rows, nwalkers, ndim)``): ``S / tau`` with
     ``S = (rows - discard) * nwalkers`` and ``tau`` the integrated autocorrelation time of a
     TRANSFORMED chain -- ``kind="bulk"``: the rank-normalised scores ``rank_normalize`` gives, which
     says how well the centre of the posterior is known whatever its tails; ``kind="tail"``: the
@@ -601,10 +483,9 @@ def ess(x, kind="bulk", discard=0, c=5):
     a walker whose transformed series is constant, such as one that never went below ``q05``, a
     non-finite value, a chain of one row -- gives a NaN ESS."""
     _check_kind(kind)
-    _chain_dims(x, discard)
-    pool = _pool_chain(x, discard)
+    chain = as_chain(x, discard)
     with np.errstate(invalid="ignore", divide="ignore"):
-        return _ess_bulk(pool, c) if kind == "bulk" else _ess_tail(pool, c)
+        return _ess_bulk(chain, c) if kind == "bulk" else _ess_tail(chain, c)
 
 
 def summary(x, ensembles=1, discard=0, labels=None, c=5):
@@ -617,29 +498,24 @@ def summary(x, ensembles=1, discard=0, labels=None, c=5):
     if isinstance(ensembles, bool) or not isinstance(ensembles, (int, np.integer)) or ensembles < 1:
         raise ValueError("ensembles must be a positive integer")
     k = int(ensembles)
-    rows, nw, ndim = _chain_dims(x, discard)
+    ndim = chain_dims(x, discard, 1)[2]
     if k > 1:
         _chain_shape(x, k, discard, 2)
-    elif nw % k:
-        raise ValueError("%d walkers do not split into %d ensembles" % (nw, k))
     if labels is not None and len(labels) != ndim:
         raise ValueError("%d labels for %d parameters" % (len(labels), ndim))
-    pool = _pool_chain(x, discard)
-    flat = pool.flat()
+    chain = as_chain(x, discard)
+    flat = chain.flat()
     st = column_stats(flat)
     q = _quantiles(flat, [0.16, 0.5, 0.84])
-    z = _z_chain(pool)
-    shape = (pool.nrows, nw, ndim)
+    z = _z_chain(chain)
     with np.errstate(invalid="ignore", divide="ignore"):
         out = dict(mean=st["mean"], sd=np.sqrt(st["var"]), median=q[1], q16=q[0], q84=q[2],
-                   ess_bulk=_ess_bulk(pool, c, z), ess_tail=_ess_tail(pool, c),
-                   tau=_taus(pool.ctx, pool.ptr + 8 * pool.row0 * pool.ld, shape, c))
+                   ess_bulk=_ess_bulk(chain, c, z), ess_tail=_ess_tail(chain, c),
+                   tau=_taus(chain, c))
     if k > 1:
-        block = (pool.owner, rows, nw, ndim)
-        out["rhat"] = _rhat_moments(block, k, discard, 2)
-        out["rhat_rank"] = np.maximum(
-            _rhat_moments((z, pool.nrows, nw, ndim), k, 0, 2),
-            _rhat_moments((_z_chain(_folded(pool)), pool.nrows, nw, ndim), k, 0, 2))
+        out["rhat"] = _rhat_moments(chain, k, 0, 2)
+        out["rhat_rank"] = np.maximum(_rhat_moments(z, k, 0, 2),
+                                      _rhat_moments(_z_chain(_folded(chain)), k, 0, 2))
     if labels is not None:
         out["labels"] = list(labels)
     return out
@@ -648,22 +524,18 @@ def summary(x, ensembles=1, discard=0, labels=None, c=5):
 def covariance(x, discard=0):
     """(mean [d], cov [d][d]) of the rows of ``x`` behind ``discard``: ``np.mean(rows, axis=0)``
     and ``np.cov(rows, rowvar=False)`` (unbiased), in two passes on the GPU (``nh_chain_cov``).
-    ``x`` is a host chain ``(rows, nwalkers, ndim)`` or a device chain ``(DeviceArray, rows,
-    nwalkers, ndim)``, of which every walker is pooled (a 4-tuple is read as a chain, as
-    ``rank_normalize`` reads it), or a matrix ``(M,)`` / ``(M, d)`` (host, or a
-    ``plot._Samples``).  d <= 32.  A column with a NaN or an infinite value is NaN in the mean and
-    in its row and column of the covariance; a single row gives a NaN covariance."""
-    if isinstance(x, tuple) or (not hasattr(x, "ncol") and len(np.shape(x)) == 3):
-        d = _chain_dims(x, discard)[2]
-    else:
-        M, d = _shape(x)
-    if d > NH_EVID_MAX_DIM:
+    ``x`` is a chain -- host ``(rows, nwalkers, ndim)``, a ``dview.DeviceChain`` or ``(DeviceArray,
+    rows, nwalkers, ndim)`` (a 4-tuple is read as a chain, as ``rank_normalize`` reads it) -- of
+    which every walker is pooled, or a matrix ``(M,)`` / ``(M, d)`` (host, or a
+    ``dview.DeviceMatrix``).  d <= 32.  A column with a NaN or an infinite value is NaN in the
+    mean and in its row and column of the covariance; a single row gives a NaN covariance."""
+    shape = _dims(x, discard, True)
+    if shape[-1] > NH_EVID_MAX_DIM:
         raise ValueError("%d columns are more than the %d a covariance takes"
-                         % (d, NH_EVID_MAX_DIM))
-    pool = _pool_chain(x, discard) if isinstance(x, tuple) else _pool_any(x, discard)[0]
-    ctx = pool.ctx
-    mean, cov = ctx.empty((d,)), ctx.empty((d, d))
-    ctx.call("nh_chain_cov", *pool.args(), mean, cov)
+                         % (shape[-1], NH_EVID_MAX_DIM))
+    v = _view(x, discard, shape)
+    mean, cov = v.ctx.empty((v.ndim,)), v.ctx.empty((v.ndim, v.ndim))
+    v.ctx.call("nh_chain_cov", *v.pooled(), mean, cov)
     return mean.get(), cov.get()
 
 
@@ -679,7 +551,7 @@ def corner(samples, labels=None, truths=None, quantiles=(0.16, 0.5, 0.84), bins=
     ``truth_color``.  One pass over the samples on the GPU gives every histogram and one
     selection the quantiles; no panel downloads samples.  Returns the matplotlib figure."""
     bins = _check_bins(bins, True)
-    M, n = _shape(samples)
+    M, n = matrix_shape(samples)
     pairs = _check_pairs(None, n)
     quantiles = [float(v) for v in (quantiles if quantiles is not None else ())]
     if any(not 0.0 <= v <= 1.0 for v in quantiles):
@@ -691,7 +563,7 @@ def corner(samples, labels=None, truths=None, quantiles=(0.16, 0.5, 0.84), bins=
     if range is not None:
         _range(range, n)
     import matplotlib.pyplot as plt
-    s = _matrix(samples)
+    s = as_matrix(samples)
     h1, H, edges = _histograms(s, bins, range, pairs)
     qv = _quantiles(s, quantiles) if quantiles else np.empty((0, n))
     truth_color = "#4682b4" if truth_color is None else truth_color

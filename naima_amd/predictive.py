@@ -35,6 +35,8 @@ creates no GPU context; argument errors come before any device work; there is no
 """
 import numpy as np
 
+from .dview import as_matrix, matrix_on, matrix_shape
+
 __all__ = ["posterior_predictive", "ppc", "pit", "predictive_quantiles", "PredictiveMixin",
            "T_COLUMNS"]
 
@@ -80,17 +82,15 @@ def _check_q(q):
 def _rows(values, unit, data, M, nE, seed, row0, want_y, want_t):
     """nh_ppc_rows: (the spectra's handle, Y handle or None, T handle or None)"""
     from .core import _data_on_device
-    from .plot import _Samples
-    from .posterior import _matrix
-    s = _matrix(values)
+    s = as_matrix(values)
     ctx = s.ctx
     dd = _data_on_device(ctx, data)
     Y = ctx.empty((M, nE)) if want_y else None
     T = ctx.empty((M, 6)) if want_t else None
     ctx.call("nh_ppc_rows", s.ptr, M, nE, s.ld, dd.conv(unit), dd.flux, dd.elo, dd.ehi, dd.ul,
              seed, row0, Y, nE, T)
-    return (s, None if Y is None else _Samples(ctx, Y.ptr, M, nE, nE, Y),
-            None if T is None else _Samples(ctx, T.ptr, M, 6, 6, T))
+    return (s, None if Y is None else matrix_on(Y, M, nE),
+            None if T is None else matrix_on(T, M, 6))
 
 
 def _pit(s, unit, data, nE):
@@ -109,7 +109,7 @@ def posterior_predictive(model, data, unit=None, seed=0, row0=0):
     the column of an upper limit holds the model itself.
 
     ``model`` is a ``Quantity`` (M, n_data) in host memory, or a device matrix as
-    ``posterior._matrix`` accepts it together with its ``unit``.  Row s uses the stream of global
+    ``dview.as_matrix`` accepts it together with its ``unit``.  Row s uses the stream of global
     row ``row0 + s``: a chain replicated in pieces gives the rows it gives in one call."""
     values, unit, M, nE, seed, row0 = _check(model, data, unit, seed, row0)
     return _rows(values, unit, data, M, nE, seed, row0, True, False)[1]
@@ -119,9 +119,8 @@ def pit(model, data, unit=None):
     """(pit, ul_violation), arrays [n_data]: the probability integral transform of every datum
     that is not an upper limit under its posterior predictive distribution (NaN at upper
     limits), and for every upper limit the fraction of samples above it (NaN elsewhere)."""
-    from .posterior import _matrix
     values, unit, M, nE, _, _ = _check(model, data, unit)
-    out = _pit(_matrix(values), unit, data, nE)
+    out = _pit(as_matrix(values), unit, data, nE)
     return out[0], out[1]
 
 
@@ -166,11 +165,10 @@ def predictive_quantiles(y_rep, q):
     of a replicate matrix (what ``posterior_predictive`` returns, or a host array), [len(q)]
     [n_data], from exact order statistics taken on the device (``nh_column_select``).  These are
     PREDICTIVE bands: they hold the noise of the data, unlike ``plot_fit``'s model bands."""
-    from .infocrit import _shape
-    from .posterior import _matrix, _quantiles
+    from .posterior import _quantiles
     q = _check_q(q)
-    _shape(y_rep)
-    return _quantiles(_matrix(y_rep), q)
+    matrix_shape(y_rep, pointwise=True)
+    return _quantiles(as_matrix(y_rep), q)
 
 
 # ---------------------------------------------------------------------------------------

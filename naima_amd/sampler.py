@@ -243,10 +243,11 @@ class EnsembleSampler(InfoCritMixin, PredictiveMixin, EvidenceMixin):
         return rhat(self.get_chain(discard=discard), self.ensembles, split=split, method=method)
 
     def _chain_block(self, thin=1):
-        """the stored chain as the device block ``(DeviceArray, rows, nwalkers, ndim)`` where the
+        """the stored chain as a ``dview.DeviceChain`` with its log-probabilities where the
         device loop still holds ALL of it in one pending history block in HBM (one rank, every
         stored row asked for), else None: the caller uploads ``get_chain()``.  Nothing is flushed;
         the launches that fill the block are settled first, as a flush settles them."""
+        from .dview import DeviceChain, matrix_on
         dev = self._dev
         if dev is None or thin != 1 or self.comm.size > 1 or len(self._chain) or len(dev.hist) != 1:
             return None
@@ -254,7 +255,8 @@ class EnsembleSampler(InfoCritMixin, PredictiveMixin, EvidenceMixin):
         if b["n"] < 1 or b.get("own") is not None or b.get("thin_by", 1) != 1:
             return None
         dev._meet()
-        return (b["coords"], b["n"], self.nwalkers, self.ndim)
+        return DeviceChain(matrix_on(b["coords"], b["n"], self.nwalkers * self.ndim),
+                           self.nwalkers, self.ndim, matrix_on(b["logp"], b["n"], self.nwalkers))
 
     def get_ess(self, kind="bulk", discard=0, thin=1):
         """The bulk or tail effective sample size of each parameter

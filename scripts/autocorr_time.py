@@ -21,6 +21,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from naima_amd import autocorr as A  # noqa: E402
+from naima_amd.dview import as_chain  # noqa: E402
 
 SHAPES = [(10000, 512, 6), (20000, 2048, 6)]
 
@@ -74,11 +75,11 @@ def main():
         x = ar1(rng, n_t, n_w, np.linspace(0.5, 0.9, n_d))
         dev_s = median_time(lambda: A.integrated_time(x, quiet=True))
         tau_dev = A.integrated_time(x, quiet=True)
-        ctx, dx = A._device_chain(x)
+        dx = as_chain(x)
 
         def resident():
             for d in range(n_d):
-                A._dimension(ctx, dx, x.shape, d, 5)
+                A._dimension(dx, d, 5)
         res_s = median_time(resident)
         del dx
         hw = min(n_w, args.host_walkers)

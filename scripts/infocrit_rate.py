@@ -29,8 +29,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from naima_amd import infocrit as IC  # noqa: E402
-from naima_amd import posterior as P  # noqa: E402
 from naima_amd.datatable import make_data  # noqa: E402
+from naima_amd.dview import as_matrix  # noqa: E402
 from naima_amd.plot import column_select  # noqa: E402
 
 SHAPES = [(512, 500, 40), (1024, 1500, 40), (1024, 1500, 130)]
@@ -71,7 +71,7 @@ def main():
         M = n_w * n_t
         data, x = problem(rng, M, nE)
         unit = data["flux"].unit
-        s = P._matrix(x)
+        s = as_matrix(x)
         L = IC.pointwise_log_likelihood(s, data, unit=unit)
         Mt = IC.tail_length(M)
         out = {"shape": [n_w, n_t, nE], "rows": M, "tail_length": Mt,

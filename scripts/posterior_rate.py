@@ -31,6 +31,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from naima_amd import posterior as P  # noqa: E402
+from naima_amd.dview import as_matrix  # noqa: E402
 
 SHAPES = [(512, 10000, 6), (2048, 20000, 6)]
 BINS, G, Q = 20, 101, (0.16, 0.5, 0.84)
@@ -73,7 +74,7 @@ def main():
         M = n_w * n_t
         x = chain(rng, M, n_d)
         pairs = [(i, j) for i in range(n_d) for j in range(i + 1, n_d)]
-        s = P._matrix(x)
+        s = as_matrix(x)
         st = P.column_stats(s)
         pts = st["mean"][:, None] + np.sqrt(st["var"])[:, None] * np.linspace(-4, 4, G)
 
@@ -86,7 +87,7 @@ def main():
                "hist2d_s": median_time(lambda: P.histogram_pairs(s, BINS)),
                "kde_s": median_time(lambda: P.gaussian_kde(s, pts)),
                "corner_s": median_time(lambda: corner_data(s)),
-               "corner_upload_s": median_time(lambda: corner_data(P._matrix(x)))}
+               "corner_upload_s": median_time(lambda: corner_data(as_matrix(x)))}
         (h1, H, edges), q = corner_data(s)
         kde = P.gaussian_kde(s, pts)
         del s
@@ -105,12 +106,12 @@ def main():
             "host_hist1d_s": t1 * M / hr, "host_hist2d_s": t2 * M / hr,
             "host_kde_s": tk * M / kr, "host_corner_s": (t1 + t2 + tq) * M / hr})
         # the device's results on the rows the host saw
-        sh = P._matrix(xh)
+        sh = as_matrix(xh)
         g1, gH, _ = P._histograms(sh, BINS, list(zip(edges[:, 0], edges[:, -1])), pairs)
         out["hist1d_equal"] = bool(all(np.array_equal(a, b) for a, b in zip(g1, ref1)))
         out["hist2d_equal"] = bool(all(np.array_equal(a, b) for a, b in zip(gH, ref2)))
         out["quantile_max_rel_diff"] = float(np.max(np.abs(P._quantiles(sh, Q) / refq - 1)))
-        gk = P.gaussian_kde(P._matrix(xk), pts)
+        gk = P.gaussian_kde(as_matrix(xk), pts)
         out["kde_max_rel_diff"] = float(np.max(np.abs(gk / np.array(refk) - 1)))
         out["speedup_hist1d"] = out["host_hist1d_s"] / out["hist1d_s"]
         out["speedup_hist2d"] = out["host_hist2d_s"] / out["hist2d_s"]

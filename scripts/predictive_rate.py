@@ -27,9 +27,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from naima_amd import posterior as P  # noqa: E402
 from naima_amd import predictive as PP  # noqa: E402
 from naima_amd.datatable import make_data  # noqa: E402
+from naima_amd.dview import as_matrix  # noqa: E402
 
 SHAPES = [(512, 500, 40), (1024, 1500, 40), (1024, 1500, 130)]
 
@@ -69,7 +69,7 @@ def main():
         M = n_w * n_t
         data, cols, x = problem(rng, M, nE)
         unit = data["flux"].unit
-        s = P._matrix(x)
+        s = as_matrix(x)
 
         def replicate():
             y = PP.posterior_predictive(s, data, unit=unit, seed=1)
