@@ -176,6 +176,16 @@ int nh_integrate_tables(nh_ctx* ctx, const double* w, const double* dlw, int N, 
  * components).  It evens out the work per CU when (tiles x walkers) does not fill the
  * 256 CUs evenly; nh_integrate_tables_nsplit gives the recommended value. */
 int nh_integrate_tables_nsplit(int N, int nG, int nK);
+/* Which kernel nh_integrate_tables launches for a shape (host arithmetic only; the launcher
+ * asks the same function): *rows_kernel = 1 the one-wave-per-(walker, k) kernel of small
+ * batches (N*nK < 1024; the other outputs are 0), else the table kernel with *C = 1/2/4/8/16
+ * waves splitting the abscissa of a plane, *W = 1/2/4 walkers per thread and *staged = 1 when
+ * the workgroup copies its walkers' w and dlw rows to LDS first.  *fused = 1 when, asked through
+ * nh_integrate_tables_lnprob (want_epilogue != 0), that launch also carries the likelihood;
+ * 0 when the entry point launches it separately.  N = 0 launches nothing: all outputs 0.
+ * Sizes that nh_integrate_tables refuses are refused here. */
+int nh_integrate_tables_plan(int N, int nG, int nK, int nsplit, int want_epilogue,
+                             int* rows_kernel, int* C, int* W, int* staged, int* fused);
 
 /* ---- row 5: radiative.py:282-342 Synchrotron._spectrum ------------------- */
 /* out[w*ldo+k] = spectrum 1/(s eV) at photon energy E_eV[k] for field B_G[w*ldB]

@@ -1062,29 +1062,19 @@ extern "C" int nh_integrate_tables_nsplit(int N, int nG, int nK) {
   return (blocks > 256 && blocks < 512) ? 2 : 1;
 }
 
-// L != NULL asks for the likelihood epilogue; *fused says whether this launch could carry it
-// (one tile, one plane, staged rows, at most two walkers per thread) -- if not, the caller
-// launches the likelihood itself
-static int integrate_impl(nh_ctx* c, const double* w, const double* dlw, int N, int nG,
-                          const double* lx, const double* Kt, const double* dlnKt, int nK,
-                          const double* scale, double* out, int ldo, int nonnegative, int nsplit,
-                          const nh_lnprob_args* L, int loc_comp, bool* fused) {
-  if (fused) *fused = false;
-  NH_REQUIRE(c && w && dlw && lx && Kt && dlnKt && out, "NULL pointer");
-  NH_REQUIRE(N >= 0 && nG >= 2 && nK >= 1 && ldo >= nK, "bad sizes");
+// The launcher's choice, from the shape alone (nh_integrate_tables_plan, naima_hip.h): the rows
+// kernel, or the instance k_integrate_tables<C, W, SIGNED, staged, fused>.  NH_INT_W / NH_INT_C
+// (experiments; read once) override W and C: only 1/2/4 and 1/2/4/8/16 have instances.
+struct nh_int_plan { bool rows; int C, W; bool stage, epi; };
+static int integrate_plan(int N, int nG, int nK, int nsplit, bool want_epi, nh_int_plan* P) {
+  *P = {false, 0, 0, false, false};
+  NH_REQUIRE(N >= 0 && nG >= 2 && nK >= 1, "bad sizes");
   NH_REQUIRE(nsplit >= 1 && nsplit <= 8, "nsplit must be 1..8");
   NH_REQUIRE((long long)N * nG < (1LL << 31) && (long long)nG * nK < (1LL << 28),
              "arrays too large for 32-bit offsets");
   if (N == 0) return NH_OK;
-  long long pairs = (long long)N * nK;
-  nh_prof_scope ps(c, pairs * 4 < 4096 ? NH_K_ROWS : NH_K_INTEGRATE);
-  if (pairs * 4 < 4096) {  // too few (walker, k) pairs to fill the chip with pair-lanes
-    hipLaunchKernelGGL(k_integrate_rows, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0,
-                       c->stream, w, dlw, N, nG, lx, Kt, dlnKt, nK, scale, out, ldo);
-    NH_CHECK_HIP(hipGetLastError());
-    if (nsplit > 1)  // everything is in plane 0
-      NH_CHECK_HIP(hipMemsetAsync(out + (long long)N * ldo, 0,
-                                  (size_t)(nsplit - 1) * N * ldo * sizeof(double), c->stream));
+  if ((long long)N * nK * 4 < 4096) {  // too few (walker, k) pairs to fill the chip with pair-lanes
+    P->rows = true;
     return NH_OK;
   }
   const int nseg = nG - 1;
@@ -1104,11 +1094,56 @@ static int integrate_impl(nh_ctx* c, const double* w, const double* dlw, int N, 
   while (C < Cmax && (long long)blocks * C < 12288 && nseg / nsplit / (2 * C) >= 8) C *= 2;
   static const int ov_C = nh_env_int("NH_INT_C", 0);
   if (ov_C > 0) C = ov_C;
+  if (C != 16 && C != 8 && C != 4 && C != 2) C = 1;  // (what the launcher's switch falls to)
+  P->C = C;
+  P->W = W;
+  P->stage = 2 * (size_t)W * nG * sizeof(double) <= 48 * 1024;
+  P->epi = want_epi && P->stage && nsplit == 1 && ktiles == 1 && W <= 2 && (C == 16 || C == 8);
+  return NH_OK;
+}
+
+extern "C" int nh_integrate_tables_plan(int N, int nG, int nK, int nsplit, int want_epilogue,
+                                        int* rows_kernel, int* C, int* W, int* staged,
+                                        int* fused) {
+  NH_REQUIRE(rows_kernel && C && W && staged && fused, "NULL pointer");
+  nh_int_plan P;
+  const int rc = integrate_plan(N, nG, nK, nsplit, want_epilogue != 0, &P);
+  *rows_kernel = P.rows, *C = P.C, *W = P.W, *staged = P.stage, *fused = P.epi;
+  return rc;
+}
+
+// L != NULL asks for the likelihood epilogue; *fused says whether this launch could carry it
+// (one tile, one plane, staged rows, at most two walkers per thread) -- if not, the caller
+// launches the likelihood itself
+static int integrate_impl(nh_ctx* c, const double* w, const double* dlw, int N, int nG,
+                          const double* lx, const double* Kt, const double* dlnKt, int nK,
+                          const double* scale, double* out, int ldo, int nonnegative, int nsplit,
+                          const nh_lnprob_args* L, int loc_comp, bool* fused) {
+  if (fused) *fused = false;
+  NH_REQUIRE(c && w && dlw && lx && Kt && dlnKt && out, "NULL pointer");
+  NH_REQUIRE(N >= 0 && nG >= 2 && nK >= 1 && ldo >= nK, "bad sizes");
+  nh_int_plan P;
+  if (const int rc = integrate_plan(N, nG, nK, nsplit, L != nullptr, &P)) return rc;
+  if (N == 0) return NH_OK;
+  nh_prof_scope ps(c, P.rows ? NH_K_ROWS : NH_K_INTEGRATE);
+  if (P.rows) {
+    const long long pairs = (long long)N * nK;
+    hipLaunchKernelGGL(k_integrate_rows, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0,
+                       c->stream, w, dlw, N, nG, lx, Kt, dlnKt, nK, scale, out, ldo);
+    NH_CHECK_HIP(hipGetLastError());
+    if (nsplit > 1)  // everything is in plane 0 (the columns k >= nK of a row are not `out`'s)
+      NH_CHECK_HIP(hipMemset2DAsync(out + (long long)N * ldo, (size_t)ldo * sizeof(double), 0,
+                                    (size_t)nK * sizeof(double), (size_t)(nsplit - 1) * N,
+                                    c->stream));
+    return NH_OK;
+  }
+  const int C = P.C, W = P.W;
+  const bool stage = P.stage, epi = P.epi;
+  const int ktiles = (nK + 63) / 64;
+  const unsigned blocks = (unsigned)(ktiles * ((N + W - 1) / W) * nsplit);
   const size_t stg_bytes = 2 * (size_t)W * nG * sizeof(double);
-  const bool stage = stg_bytes <= 48 * 1024;
   nh_lnprob_args none = {};
   const nh_lnprob_args& LA = L ? *L : none;
-  const bool epi = L && stage && nsplit == 1 && ktiles == 1 && W <= 2 && (C == 16 || C == 8);
   if (fused) *fused = epi;
 #define NH_LAUNCH_INT_T(CC, WW, SS, TT)                                                      \
   hipLaunchKernelGGL((k_integrate_tables<CC, WW, SS, TT>), dim3(blocks), dim3(64 * CC),      \

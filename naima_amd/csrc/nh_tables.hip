@@ -23,7 +23,9 @@
 #define NH_TAB_AT ((long long)i * ld + k)
 
 // second pass of every builder: dlnKt[i][k] = ln|K[i+1][k] / K[i][k]| -- the
-// log-ratio of ADJACENT nodes, accurate to ~2 ulp however large ln K itself is
+// log-ratio of ADJACENT nodes, accurate to ~3 ulp OF ITSELF however large ln K is and however
+// close to 1 the ratio: within a factor 2, K2 - K1 is exact and log1p keeps the relative accuracy
+// that the rounding of the quotient K2/K1 (2^-53 absolute in the logarithm) would cost
 __global__ __launch_bounds__(256) void k_table_dlog(const double* __restrict__ Kt, int nG, int nE,
                                                      int ld, double* __restrict__ dlnKt) {
   NH_TAB_PROLOGUE
@@ -31,7 +33,10 @@ __global__ __launch_bounds__(256) void k_table_dlog(const double* __restrict__ K
   if (i + 1 < nG) {
     const double k1 = Kt[NH_TAB_AT], k2 = Kt[(long long)(i + 1) * ld + k];
     // a zero node ends the power-law segment (utils.py:347-348): marked for nh_seg_pos
-    v = (k1 == 0.0 || k2 == 0.0) ? NH_DL_ZERO : log(fabs(k2 / k1));
+    const double q = k2 / k1;
+    v = (k1 == 0.0 || k2 == 0.0) ? NH_DL_ZERO
+        : (q > 0.5 && q < 2.0)   ? log1p((k2 - k1) / k1)
+                                 : log(fabs(q));
   }
   dlnKt[NH_TAB_AT] = v;
 }

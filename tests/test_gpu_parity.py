@@ -662,7 +662,10 @@ def test_abi_step_front_and_lnprob_accept(na):
 
 def test_abi_last_producer_epilogues(na):
     """nh_synchrotron_lnprob and nh_integrate_tables_lnprob (the likelihood + accept as the
-    epilogue of the last producer) against the separate entry points on the same inputs"""
+    epilogue of the last producer) against the separate entry points on the same inputs.  The
+    table half covers nh_integrate_tables_lnprob's FALLBACK: N * nE = 480 < 1024 takes
+    k_integrate_rows, which cannot carry the likelihood, so the entry point launches it
+    separately (test_gpu_integrate.py::test_fused_epilogue_is_reached has the fused launch)"""
     import ctypes as C
     from naima_amd._lib import get_context
     from naima_amd.constants import MEC2_EV
