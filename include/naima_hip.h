@@ -194,6 +194,16 @@ int nh_integrate_tables_plan(int N, int nG, int nK, int nsplit, int want_epilogu
 int nh_synchrotron(nh_ctx* ctx, const double* w, const double* dlw, const double* B_G, int ldB,
                    int N, const double* gam, const double* lx, int nG,
                    const double* E_eV, int nE, double* out, int ldo);
+/* Which kernel nh_synchrotron launches for a shape (host arithmetic only; the launcher asks the
+ * same function): a workgroup of *C = 4/8/16 waves per (walker, tile), *tw <= 64 photon energies
+ * per tile, *ktiles = ceil(nE / *tw) tiles per walker (energy k sits in tile k % *ktiles) and
+ * *lds_bytes of dynamic LDS, 24 nG + 32768 (above 64 KB the launcher raises the kernel's limit
+ * first).  want_epilogue != 0 asks as nh_synchrotron_lnprob does: one tile of 64, the instance
+ * that goes on to the likelihood.  N = 0 launches nothing: all outputs 0.  Sizes that
+ * nh_synchrotron refuses are refused here: nG < 2, nE < 1, N < 0, the epilogue with nE > 64,
+ * more than 150 KB of LDS (nG > 5034). */
+int nh_synchrotron_plan(int N, int nG, int nE, int want_epilogue, int* C, int* tw, int* ktiles,
+                        int* lds_bytes);
 
 /* ---- rows 6,7: radiative.py:547-607 + G12/G34 345-367 -------------------- */
 /* Kt[i][k] (1/s per unit ... as _iso/_ani_ic_on_planck return) for temperature

@@ -88,6 +88,8 @@ _SIGS = {
     "nh_integrate_tables_nsplit": [_i, _i, _i],
     "nh_integrate_tables_plan": [_i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
                                  C.POINTER(_i), C.POINTER(_i)],
+    "nh_synchrotron_plan": [_i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
+                            C.POINTER(_i)],
     "nh_lnprob": [_dp, _dp, _i, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _i, _dp, _dp],
     "nh_move_propose": [_dp, _dp, _dp, _dp, _i, _i, _i, _i, _dp, _dp],
     "nh_move_accept": [_dp, _dp, _dp, _dp, _dp, _dp, _i, _i, _dp, _dp, _dp, _i],

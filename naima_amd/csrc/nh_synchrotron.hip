@@ -200,14 +200,15 @@ __global__ __launch_bounds__(64 * C) void k_synchrotron(
   }
 }
 
-static int launch_synchrotron(nh_ctx* c, const double* w, const double* dlw, const double* B_G,
-                              int ldB, int N, const double* gam, const double* lx, int nG,
-                              const double* E_eV, int nE, double* out, int ldo,
-                              const nh_lnprob_args* L, int syn_comp) {
-  NH_REQUIRE(c && w && dlw && B_G && gam && lx && E_eV && out, "NULL pointer");
-  NH_REQUIRE(N >= 0 && nG >= 2 && nE >= 1 && ldo >= nE && ldB >= 1, "bad sizes");
+// The launcher's choice, from the shape alone (nh_synchrotron_plan, naima_hip.h): the instance
+// k_synchrotron<C, epilogue>, the tile width, the tiles per walker and the dynamic LDS of a
+// workgroup.  NH_SYN_TW / NH_SYN_C (experiments; read once) override tw and C: only C = 4/8/16
+// have instances.
+struct nh_syn_plan { int C, tw, ktiles; size_t shm; };
+static int synchrotron_plan(int N, int nG, int nE, bool want_epi, nh_syn_plan* P) {
+  *P = {0, 0, 0, 0};
+  NH_REQUIRE(N >= 0 && nG >= 2 && nE >= 1, "bad sizes");
   if (N == 0) return NH_OK;
-  nh_prof_scope ps(c, NH_K_SYNCHROTRON);
   const int nseg = nG - 1;
   int C = nseg >= 256 ? 16 : (nseg >= 64 ? 8 : 4);
   // tile width: 64 measured best at every (C, tw) tried on cfg3 (C=16: 20.0 / 24.2 / 28.9 us
@@ -218,23 +219,51 @@ static int launch_synchrotron(nh_ctx* c, const double* w, const double* dlw, con
   // energies, 128 walkers) go faster as 512-thread workgroups of ~33 energies, two per CU, one's
   // set-up and reduction beside the other's nodes: 63.0 -> 53.3 us mean of cfg4's two launches
   // (C, tw = 8, 44: 58.3; 8, 22: 57.4; 16, 33: 61.6; 4, 64: 84.4)
-  if (nE > 64 && !L) {
+  if (nE > 64 && !want_epi) {
     C = min(C, 8);
     const int kt = (nE + 32) / 33;
     tw = (nE + kt - 1) / kt;
   }
   static const int ov_tw = nh_env_int("NH_SYN_TW", 0);
   if (ov_tw > 0) tw = ov_tw;
-  if (L) tw = 64;
+  if (want_epi) tw = 64;
   NH_REQUIRE(tw >= 1 && tw <= 64, "bad tile width");
   const int ktiles = (nE + tw - 1) / tw;
-  NH_REQUIRE(!L || ktiles == 1, "the likelihood epilogue needs all energies in one tile");
+  NH_REQUIRE(!want_epi || ktiles == 1,
+             "the likelihood epilogue needs all energies in one tile");
   const unsigned blocks = (unsigned)(ktiles * N);
   if ((long long)blocks * C > 16384 && C > 4) C /= 2;  // plenty of waves: longer chunks
   static const int ov_C = nh_env_int("NH_SYN_C", 0);
   if (ov_C > 0) C = ov_C;
-  size_t shm = (size_t)(3 * nG + SYN_MAXCH * 64) * sizeof(double);
+  if (C != 16 && C != 8) C = 4;  // (what the launcher's switch falls to)
+  const size_t shm = ((size_t)3 * nG + SYN_MAXCH * 64) * sizeof(double);
   NH_REQUIRE(shm <= 150 * 1024, "electron grid too long for the LDS staging");
+  *P = {C, tw, ktiles, shm};
+  return NH_OK;
+}
+
+extern "C" int nh_synchrotron_plan(int N, int nG, int nE, int want_epilogue, int* C, int* tw,
+                                   int* ktiles, int* lds_bytes) {
+  NH_REQUIRE(C && tw && ktiles && lds_bytes, "NULL pointer");
+  nh_syn_plan P;
+  const int rc = synchrotron_plan(N, nG, nE, want_epilogue != 0, &P);
+  *C = P.C, *tw = P.tw, *ktiles = P.ktiles, *lds_bytes = (int)P.shm;
+  return rc;
+}
+
+static int launch_synchrotron(nh_ctx* c, const double* w, const double* dlw, const double* B_G,
+                              int ldB, int N, const double* gam, const double* lx, int nG,
+                              const double* E_eV, int nE, double* out, int ldo,
+                              const nh_lnprob_args* L, int syn_comp) {
+  NH_REQUIRE(c && w && dlw && B_G && gam && lx && E_eV && out, "NULL pointer");
+  NH_REQUIRE(N >= 0 && nG >= 2 && nE >= 1 && ldo >= nE && ldB >= 1, "bad sizes");
+  nh_syn_plan P;
+  if (const int rc = synchrotron_plan(N, nG, nE, L != nullptr, &P)) return rc;
+  if (N == 0) return NH_OK;
+  nh_prof_scope ps(c, NH_K_SYNCHROTRON);
+  const int C = P.C, tw = P.tw;
+  const unsigned blocks = (unsigned)(P.ktiles * N);
+  const size_t shm = P.shm;
   nh_lnprob_args none = {};
   const nh_lnprob_args& A = L ? *L : none;
 #define NH_LAUNCH_SYN_E(CC, EE)                                                               \
