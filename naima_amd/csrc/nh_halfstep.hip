@@ -1271,6 +1271,7 @@ hs_knobs hs_knobs_read() {
   k.run_tcompact_min = nh_env_int("NH_RUN_TCOMPACT_MIN", k.run_tcompact_min);
   k.run_syn_nodes = hs_env_opt("NH_RUN_SYN_NODES");
   k.run_pipeline = nh_env_int("NH_RUN_PIPELINE", k.run_pipeline);
+  k.run_syn_cut = nh_env_int("NH_RUN_SYN_CUT", k.run_syn_cut);
   k.run_fail_at = nh_env_int("NH_RUN_FAIL_AT", 0);
   k.run_grid = hs_env_opt("NH_RUN_GRID");
   k.run_max_per_wg = hs_env_opt("NH_RUN_MAX_PER_WG");

@@ -23,6 +23,7 @@
 #define HS_O_HX 56           // two ints of the small block: HX_PRE, HX_SPECRD (two walkers in flight)
 enum { HX_PRE = 0, HX_SPECRD = 1 };
 #define HS_O_LNA 48          // in the small per-walker block (proposal coordinates: <= 15 of its first 64 doubles)
+#define HS_O_S2CUT 32        // seven doubles of the FIRST small block: hs_s2_cut (nh_syn2.h), written when the launch begins
 #define HS_RUN_TRAIL 16        // ints of first-row entries per table in LDS (>= tiles of any table)
 #define HS_RUN_PKW 8           // doubles per parameter-pack column in LDS
 
@@ -134,6 +135,7 @@ struct hs_run {
   double s2_z0, s2_invd;  // z = s2_z0 - ln(q) s2_invd: where node 0 sits on the comb below T_top
   double s2_r746;         // (T_top - ln 746) s2_invd - s2_z0: the first live node is ceil(ln(q) s2_invd + this)
   double s2_lnw0;         // ln |n| + ln(E / eV) above this: the weight gamma n scale is not 0 in double
+  hs_s2_cut s2_cut;       // a live range whose head is nothing of the integral starts at x <= 128 (nh_syn2.h: hs_s2_cut_ok)
   int pipeline;           // two walkers in flight (a workgroup with several walkers of a slice): NH_RUN_PIPELINE
   long long* clk;         // the context's span clock (nh_common.h): this launch opens a span, k_run_epilogue closes it
 };
@@ -163,6 +165,7 @@ struct hs_knobs {
   int run_tcompact_min;         // NH_RUN_TCOMPACT_MIN (4)
   hs_opt run_syn_nodes;         // NH_RUN_SYN_NODES
   int run_pipeline;             // NH_RUN_PIPELINE (1)
+  int run_syn_cut;              // NH_RUN_SYN_CUT (1): the log-domain items leave a range's faint head out
   int run_fail_at;              // NH_RUN_FAIL_AT: the launch whose first wait times out (tests; 0)
   hs_opt run_grid;              // NH_RUN_GRID (ignored below 1)
   hs_opt run_max_per_wg;        // NH_RUN_MAX_PER_WG
@@ -177,7 +180,7 @@ static inline hs_knobs hs_knobs_default() {
   k.kmax = 8; k.part_kb = 40; k.split_min_work = 1 << 20;
   k.rowsplit = k.rt = k.syn2 = 1;
   k.run_rt = k.run_grids_in_lds = k.run_ut = k.run_rowsplit = k.run_syn2 = k.run_il = 1;
-  k.run_tcompact_min = 4; k.run_pipeline = 1; k.run_shared_alloc = 1;
+  k.run_tcompact_min = 4; k.run_pipeline = 1; k.run_shared_alloc = 1; k.run_syn_cut = 1;
   return k;
 }
 
@@ -728,6 +731,8 @@ static inline int hs_run_plan(const nh_halfstep_plan* P, bool shared, int rank, 
     const int nG = H.nG[H.syn_grid], Pn = S.s2.par.P;
     R.s2 = S.s2.par;
     R.s2_invd = S.s2.invd; R.s2_lnw0 = S.s2.lnw0; R.s2_z0 = S.s2.z0; R.s2_r746 = S.s2.r746;
+    R.s2_cut = S.s2.cut;
+    R.s2_cut.on = k.run_syn_cut != 0 ? 1 : 0;
     const int off_was = off, hole_was = hole_lo;  // (tentative: undone if it does not fit)
     R.o_s2tab = take((Pn + 1) * HS_S2_STRIDE, true);  // (16-byte aligned: the pieces are read as ds_read_b128)
     // the plan's LDS holds w | dlw of the synchrotron grid and 1/g^2 | its differences | its

@@ -455,6 +455,13 @@ __global__ __launch_bounds__(RT > 0 ? 512 : 1024) void k_half_step_run(const hs_
         sm[R.o_lnt + 2 * tid] = 1.0 / c;
         sm[R.o_lnt + 2 * tid + 1] = log(c);
       }
+      if (tid == 0) {  // hs_s2_cut_ok's constants
+        double* cs = sm + HS_O_S2CUT;
+        cs[0] = R.s2_cut.rcut; cs[1] = R.s2_cut.span; cs[2] = R.s2_cut.lx; cs[3] = R.s2_cut.lne0m;
+        cs[4] = R.s2_cut.margin; cs[5] = R.s2_cut.lntcap;
+        reinterpret_cast<int*>(cs + 6)[0] = R.s2_cut.dref;
+        reinterpret_cast<int*>(cs + 6)[1] = R.s2_cut.on;
+      }
       for (int i = tid; i < nGs; i += T) sm[R.o_s2lg + i] = R.s2_dev[ntb + i];
       for (int i = tid; i < nGs + 2 * HS_S2_GUARD; i += T) {  // (guards: the edge values, any finite number)
         const int ii = min(max(i - HS_S2_GUARD, 0), nGs - 1);
@@ -967,6 +974,29 @@ __global__ __launch_bounds__(RT > 0 ? 512 : 1024) void k_half_step_run(const hs_
                 while (c < nG && !(lv_q * ig2[c] <= 746.0)) ++c;
               }
               lo = c;
+              // (the range's faint head, x from 746 down to 128, is nothing of the integral when the
+              // distribution's own form says so -- nh_syn2.h, hs_s2_cut_ok: the range then starts at
+              // the first node with x <= 128, ~40 nodes later on naima's default grid; decided per
+              // energy, ahead of barrier 2, by the waves that form no weights)
+              // (its constants from LDS, where the launch put them: as kernel arguments they are
+              // fourteen scalar registers held across every phase of the slice loop, and spilled)
+              const double* cs = sm + HS_O_S2CUT;
+              hs_s2_cut C;
+              C.rcut = cs[0]; C.span = cs[1]; C.lx = cs[2]; C.lne0m = cs[3]; C.margin = cs[4]; C.lntcap = cs[5];
+              C.dref = reinterpret_cast<const int*>(cs + 6)[0]; C.on = reinterpret_cast<const int*>(cs + 6)[1];
+              const int ic = hs_s2_cut_node(C, r, nG);
+              if (ic > c) {
+                const bool cut = hs_s2_cut_ok(C, D.kind, r, ic, nG, p.al, p.be, p.a2, lg[0], lg[1]);
+                if (cut) lo = ic;
+                if (R.dbg) {  // (NH_HS_DEBUG: live ranges that start at x <= 128 | that keep their head)
+                  const int ncut = __popcll(__builtin_amdgcn_ballot_w64(cut));
+                  const int nkept = __popcll(__builtin_amdgcn_ballot_w64(!cut));
+                  if (lane == __builtin_ctzll(__builtin_amdgcn_ballot_w64(true))) {
+                    atomicAdd(reinterpret_cast<unsigned long long*>(R.dbg) + 256 * 64 * 8 + 11 * 16 + 0, (unsigned long long)ncut);
+                    atomicAdd(reinterpret_cast<unsigned long long*>(R.dbg) + 256 * 64 * 8 + 11 * 16 + 1, (unsigned long long)nkept);
+                  }
+                }
+              }
             } else {
               // (a field that is not positive: ln q is NaN -- the search itself, whose answer for a
               // negative q is "every node", for a NaN "none")

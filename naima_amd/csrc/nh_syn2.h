@@ -204,6 +204,75 @@ __device__ HS_S2_INLINE void hs_syn2_item(int ix, int lane, int nA, int Cd, int 
   part_s[ch * nEs + a] = acc * (sq[3 * nEs + a] * nh_rcp(ilx_here));
 }
 
+// ---- the faint head of a live range (resident loop) ----------------------------------------------
+// A range starts at the first node with x <= 746, where exp(-x) stops being an exact 0.  From there
+// down to x ~ 100 the integrand is e^-x times a ratio of particle weights of a few e-folds: nothing
+// of the integral, 27 instructions per node.  The range may start at the first node with
+// x <= HS_S2_XCUT instead when every node it leaves out lies at least 60 ln 2 + ln nG below BOTH of
+// two neighbouring kept nodes k, k + 1 (the first two with x <= HS_S2_XREF), in the natural
+// exponent ln w + g(t) - x: a segment is the logarithmic mean of its end points times lx, so the
+// segments left out sum to less than nG lx max(u_left_out) <= 2^-60 lx min(u_k, u_k+1), which is
+// 2^-60 of ONE kept segment -- and the integrand has one sign.
+// The bound comes from the distribution's own form, not from the nodes: with L = ln w as a
+// function of ln E, i a node left out and j = k or k + 1,
+//     L_i - L_j <= S (ln E_j - ln E_i) + T,
+// S the largest slope -dL/dlnE between them (alpha - 1 for a power law, the larger index of a
+// broken one, alpha - 1 + 2 beta ln(E/e_0) at either end for a log-parabola: linear in ln E), T the
+// cut-off's (E_j/e_c)^beta (what node i loses to ITS cut-off only helps).  The kept nodes' T is
+// not evaluated: it is required to lie under HS_S2_TCAP, which costs a product and a comparison.
+// The same function on the host (tests) and in the kernel: comparisons that a NaN fails.
+#define HS_S2_XCUT 128.0
+#define HS_S2_XREF 32.0
+#define HS_S2_TCAP 16.0
+struct hs_s2_cut {  // wave-uniform, formed by hs_s2_prepare
+  double rcut;    // comb steps from x = 746 to x = X_CUT: the range starts at ceil(r + rcut), r the crossing of 746
+  double span;    // comb steps from node ceil(r) - 1 to past node k + 1, whatever the fractions
+  double lx;      // ln(E_i+1 / E_i)
+  double lne0m;   // ln(E_0 / eV) - lx: ln E at the comb position r is below lne0m + r lx
+  double margin;  // X_CUT - X_REF - (max g over the nodes left out - min g over k, k + 1) - 60 ln 2 - ln nG - slack
+  double lntcap;  // ln HS_S2_TCAP
+  int dref;       // k = ceil(r + rcut) + dref
+  int on;         // 0: never cut (NH_RUN_SYN_CUT=0)
+};
+// the first node with x <= X_CUT of a range whose x crosses 746 at comb position r (nG: none)
+__host__ __device__ static inline int hs_s2_cut_node(const hs_s2_cut& C, double r, int nG) {
+  const double rc = r + C.rcut;
+  return rc > 0.0 ? (rc < (double)nG ? (int)ceil(rc) : nG) : 0;  // (a NaN: node 0, which is never past the live one)
+}
+// may the range whose x crosses 746 at comb position r (its first live node: ceil(r)) start at node
+// ic = ceil(r + rcut) instead?  al, be, a2: the particle row's alpha (alpha_1), beta, alpha_2 as
+// pd_core takes them; lg0, lg1: ln e_0, ln e_cutoff (eV)
+__host__ __device__ static inline bool hs_s2_cut_ok(const hs_s2_cut& C, int kind, double r, int ic, int nG,
+                                                    double al, double be, double a2, double lg0, double lg1) {
+  if (!C.on || r != r || ic + C.dref + 1 > nG - 1) return false;  // (k and k + 1 are nodes of the grid)
+  const double e_lo = fma(r, C.lx, C.lne0m), e_hi = fma(C.span, C.lx, e_lo);
+  double S, rem = C.margin;
+  bool ok = true;
+  switch (kind) {
+    case NH_PD_POWERLAW:
+    case NH_PD_ECPL:
+      S = al - 1.0;
+      break;
+    case NH_PD_BROKENPL:
+    case NH_PD_ECBPL:
+      S = (al > a2 ? al : a2) - 1.0;
+      ok = al == al && a2 == a2;
+      break;
+    default: {  // NH_PD_LOGPARABOLA
+      const double s0 = fma(2.0 * be, e_lo - lg0, al - 1.0), s1 = fma(2.0 * be, e_hi - lg0, al - 1.0);
+      S = s0 > s1 ? s0 : s1;
+      ok = s0 == s0 && s1 == s1;
+    } break;
+  }
+  if (kind == NH_PD_ECPL || kind == NH_PD_ECBPL) {
+    // (E/e_c)^beta rises with E for beta >= 0 and falls otherwise: its largest value on [e_lo, e_hi]
+    ok = ok && be * ((be >= 0.0 ? e_hi : e_lo) - lg1) <= C.lntcap;
+    rem -= HS_S2_TCAP;
+  }
+  // (an L that rises with E, S < 0, is bounded by its value at the nearest point: 0)
+  return ok && S == S && rem >= 0.0 && (S > 0.0 ? S : 0.0) * (C.span * C.lx) <= rem;
+}
+
 // ---- the table of nh_syn2.h, built on the host when the loop is created -------------------------
 // rho(t) = ln(Gtilde(x) e^x) - t / 3 - ln 1.808,  x = e^t   (radiative.py:300-311); the table holds
 // Lambda (rho + ln 1.808)
@@ -252,8 +321,20 @@ struct hs_s2_host {
   // the resident loop's: (T_top - ln 746) invd - z0 (the first live node is ceil(ln(q) invd + this));
   // ln |n| + ln(E / eV) above lnw0: the weight gamma n scale is not 0 in double
   double r746, lnw0;
+  hs_s2_cut cut;             // the resident loop's: where a live range may start instead (hs_s2_cut_ok)
   std::vector<double> data;  // (P + 1) HS_S2_STRIDE table entries | nG node constants
 };
+// g(t) = ln(Gtilde(x) e^x) = t / 3 + ln 1.808 + rho(t): its largest value on [t0, t1] (sign = 1) or
+// minus its smallest (sign = -1), on a scan far finer than g varies
+static inline long double hs_s2_g_extreme(long double t0, long double t1, int sign) {
+  long double best = -1e300L;
+  const int n = 4096;
+  for (int i = 0; i <= n; ++i) {
+    const long double t = t0 + (t1 - t0) * i / n;
+    best = fmaxl(best, sign * (t / 3.0L + logl(1.808L) + hs_s2_rho(t)));
+  }
+  return best;
+}
 static inline bool hs_s2_prepare(const double* gam, int nG, double scale, int min_nodes, hs_s2_host& o) {
   bool ok = nG >= min_nodes && gam[0] > 0.0 && scale > 0.0;
   long double lx = 0.0L, dev = 0.0L;
@@ -295,5 +376,25 @@ static inline bool hs_s2_prepare(const double* gam, int nG, double scale, int mi
   o.lnw0 = (double)(-1075.0L * logl(2.0L) + logl((long double)NH_MEC2_EV / (long double)scale));
   o.r746 = (double)(((long double)HS_S2_TTOP - logl(746.0L)) / (2.0L * lx) -
                     ((long double)HS_S2_TTOP + 2.0L * logl((long double)gam[0])) / (2.0L * lx));
+  {
+    // hs_s2_cut_ok's constants.  Node ic = ceil(r + rcut) is the first with x <= X_CUT; k = ic + dref
+    // has x <= X_REF (one comb step to spare), k + 1 sits below r + rcut + dref + 2, so x there is
+    // above X_CUT e^(-2 lx (dref + 2)); ln E is taken from comb position r - 1 (below every node
+    // left out) to r - 1 + span.  The slack: a crossing found by logarithm may call a node with
+    // x = X_CUT (1 - 1e-4) one that is left out; 0.01 for the roundings and the scan.
+    const long double d2 = 2.0L * lx, lc = logl((long double)HS_S2_XCUT), lr = logl((long double)HS_S2_XREF);
+    hs_s2_cut& c = o.cut;
+    c.rcut = (double)((logl(746.0L) - lc) / d2);
+    c.dref = (int)ceill((lc - lr) / d2) + 1;
+    c.span = c.rcut + c.dref + 3.0;
+    c.lx = (double)lx;
+    c.lne0m = (double)(logl((long double)gam[0]) + logl((long double)NH_MEC2_EV) - lx);
+    const long double gmax = hs_s2_g_extreme(lc - 1e-4L, logl(746.0L), 1);
+    const long double gmin = -hs_s2_g_extreme(lc - d2 * (c.dref + 2), lr, -1);
+    c.margin = (double)((long double)HS_S2_XCUT * (1.0L - 1e-4L) - (long double)HS_S2_XREF - (gmax - gmin) -
+                        60.0L * logl(2.0L) - logl((long double)nG) - 0.01L);
+    c.lntcap = log(HS_S2_TCAP);
+    c.on = 1;
+  }
   return true;
 }
