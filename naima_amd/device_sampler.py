@@ -25,11 +25,12 @@ import weakref
 
 import numpy as np
 
-from . import _lib, shared_merge
+from . import _lib, loop_books, shared_merge
 from .step_plan import AcceptHook, Front, StepPlan
 from . import units as u
 from .darray import DEbl, DMat, DPars, DVec
 from .dist import shard_bounds, shard_counts
+from .loop_books import Books, EnsembleCopy, JournalEntry, KeptBlob, LaunchQueue
 from .move_ring import MoveRing
 
 _GAVE_UP = ("a launch of the resident loop gave up waiting for a walker's record (status %d): its "
@@ -185,7 +186,7 @@ class DeviceLoop:
         self.nacc = ctx.empty((self.N,), dtype=np.int32)
         ctx.call("nh_memset", self.nacc, 0, self.nacc.nbytes)
         self.graph = None
-        self.cur_blobs = None      # list of (device buffer [N][m], m, unit, trailing shape)
+        self.cur_blobs = None      # list of loop_books.KeptBlob
         self.const_blobs = []      # (position, value) of blobs that are plain numbers
         self.hist = []             # pending device history blocks
         self.warm = 0
@@ -203,8 +204,7 @@ class DeviceLoop:
         # locked memory the launch's epilogue writes, no stream operation), and settles all of
         # them before a call returns -- a launch that gave up later in a run costs the replay of
         # two blocks of moves at most, by the per-launch kernel (sample)
-        self._rl_count = 0     # launches queued so far (the library counts them the same way)
-        self._rl_pending = []
+        self._rl = LaunchQueue()
         # copies of the current blobs as a launch WITHOUT a history found them (such a launch
         # writes the blobs of accepted moves straight into the current-blob arrays): what a
         # launch that gave up -- or ran void behind one that did -- is rolled back to
@@ -345,20 +345,21 @@ class DeviceLoop:
             self.blobs_in_kernel = True  # the half-step launch keeps the blobs itself
             return
         if self.new_blobs is None:
-            self.new_blobs = [self.ctx.empty((self.nloc, m)) for _, m, _, _ in self.cur_blobs]
+            self.new_blobs = [self.ctx.empty((self.nloc, b.m)) for b in self.cur_blobs]
             if self.sharded:  # every rank keeps every walker's blobs
-                self.all_blobs = [self.ctx.empty((self.ns, m)) for _, m, _, _ in self.cur_blobs]
-        for nb, (cur, m, _, _), b in zip(self.new_blobs, self.cur_blobs, blobs):
+                self.all_blobs = [self.ctx.empty((self.ns, b.m)) for b in self.cur_blobs]
+        for nb, kept, b in zip(self.new_blobs, self.cur_blobs, blobs):
             own, ptr, mb, _, _ = self._blob_dense(b)
-            self.ctx.call("nh_scatter_rows", nb, m, ptr, mb, self.ident, None, 0, self.nloc, m)
+            self.ctx.call("nh_scatter_rows", nb, kept.m, ptr, mb, self.ident, None, 0, self.nloc,
+                          kept.m)
             del own
 
     def _part_accept(self):
         ctx = self.ctx
         if self.fused and self.sharded and self.blobs_in_kernel and self.send_width:
             nb = len(self.cur_blobs)
-            cur = (C.c_void_p * nb)(*[c_.ptr for c_, _, _, _ in self.cur_blobs])
-            mm = (C.c_int * nb)(*[m for _, m, _, _ in self.cur_blobs])
+            cur = (C.c_void_p * nb)(*[b.cur.ptr for b in self.cur_blobs])
+            mm = (C.c_int * nb)(*[b.m for b in self.cur_blobs])
             ctx.call("nh_move_accept_rows", self.coords, self.logp, self.blk, self.cursor,
                      self.recv_rows, self.send_width, self.ns, self.ndim, self.accepted, self.nacc,
                      self.sel, 0, nb, cur, mm)
@@ -371,8 +372,9 @@ class DeviceLoop:
         if self.s.store_blobs and self.cur_blobs and not self.blobs_in_kernel:
             src, lo, n = (self.all_blobs, 0, self.ns) if self.sharded else \
                 (self.new_blobs, self.lo, self.nloc)
-            for b, (cur, m, _, _) in zip(src, self.cur_blobs):
-                ctx.call("nh_scatter_rows", cur, m, b, m, self.sel, self.accepted, lo, n, m)
+            for b, kept in zip(src, self.cur_blobs):
+                ctx.call("nh_scatter_rows", kept.cur, kept.m, b, kept.m, self.sel, self.accepted,
+                         lo, n, kept.m)
         if self.fused and not self.mega:
             self._front()
 
@@ -451,12 +453,12 @@ class DeviceLoop:
             if self._hook.total is None:
                 self._hook.total = ctx.empty((self.nloc,))  # persistent: the plan points at it
             if self.s.store_blobs and self.cur_blobs:
-                self._hook.blobs = [(cur.ptr, m, self.blobhist_ptr + 8 * i)
-                                    for i, (cur, m, _, _) in enumerate(self.cur_blobs)]
+                self._hook.blobs = [(b.cur.ptr, b.m, self.blobhist_ptr + 8 * i)
+                                    for i, b in enumerate(self.cur_blobs)]
                 if self.sharded:
                     # the blobs travel with the log-probabilities: ONE all-gather of rows
                     # { lnprob | blob 0 | blob 1 ... } per half-step
-                    self.send_width = 1 + sum(m for _, m, _, _ in self.cur_blobs)
+                    self.send_width = 1 + sum(b.m for b in self.cur_blobs)
                     self._hook.send_width = self.send_width
                     self.send_rows = ctx.empty((max(self.nloc, 1), self.send_width))
                     self.recv_rows = ctx.empty((self.ns, self.send_width))
@@ -498,8 +500,8 @@ class DeviceLoop:
             if self.s.store_blobs and self.cur_blobs:
                 # blobs of the proposals follow their log-probabilities: the walker a rank
                 # evaluates changes every step, so every rank keeps all of them
-                for nb, ab, (cur, m, _, _) in zip(self.new_blobs, self.all_blobs, self.cur_blobs):
-                    self._gather_rows(nb.ptr, ab, self.ns, m)
+                for nb, ab, kept in zip(self.new_blobs, self.all_blobs, self.cur_blobs):
+                    self._gather_rows(nb.ptr, ab, self.ns, kept.m)
 
     def _half_step_body(self):
         self._part_evaluate()
@@ -528,16 +530,14 @@ class DeviceLoop:
             ident = ctx.array(np.arange(lo, hi, dtype=np.int32), dtype=np.int32)
             for i, b in enumerate(blobs):
                 own, ptr, m, unit, trail = self._blob_dense(b)
-                cur = old[i][0] if i < len(old) and old[i][1] == m else ctx.empty((self.N, m))
+                cur = old[i].cur if i < len(old) and old[i].m == m else ctx.empty((self.N, m))
                 if self.sharded:
                     self._gather_rows(ptr, cur, self.N, m)
                 else:
                     ctx.call("nh_scatter_rows", cur, m, ptr, m, ident, None, 0, hi - lo, m)
-                self.cur_blobs.append((cur, m, unit, trail))
+                self.cur_blobs.append(KeptBlob(cur, m, unit, trail))
                 units.append(unit)
-            for j, _ in self.const_blobs:
-                units.insert(j, None)
-            s.blob_units = units
+            s.blob_units = loop_books.with_const_blobs(units, self.const_blobs, lambda v: None)
         lp = self.logp.get()
         if np.any(np.isnan(lp)):
             raise ValueError("Probability function returned NaN")
@@ -549,10 +549,8 @@ class DeviceLoop:
         if not self.cur_blobs:
             return None
         self._sync_cur_blobs()  # (a shared ensemble: collective -- every rank asks, or none)
-        out = [cur.get().reshape((self.N,) + trail) for cur, m, _, trail in self.cur_blobs]
-        for j, v in self.const_blobs:
-            out.insert(j, np.full((self.N,), v))
-        return out
+        out = [b.cur.get().reshape((self.N,) + b.trail) for b in self.cur_blobs]
+        return loop_books.with_const_blobs(out, self.const_blobs, lambda v: np.full((self.N,), v))
 
     # ------------------------------------------------------------------- loop
     def sample(self, initial_state, iterations, store, yield_every=1, thin_by=1):
@@ -560,14 +558,8 @@ class DeviceLoop:
         launches write every step's row, as the blob bookkeeping of the step kernels needs; with
         thin_by > 1 they write them into a staging block that is reused, and every thin_by-th row
         is copied to the compact block that is kept (_sample_thinned)."""
-        from .sampler import State
-        s, ctx = self.s, self.ctx
-        cont = isinstance(initial_state, DeviceState) and initial_state._loop is self
-        if not cont:  # (else: continue from the ensemble already in HBM)
-            st = State(initial_state)
-            if st.coords.shape != (self.N, self.ndim):
-                raise ValueError("incompatible input dimensions")
-            self._init_state(st.coords, st.log_prob)
+        s = self.s
+        cont = self._adopt(initial_state)
         iterations, thin_by = int(iterations), int(thin_by)
         # several ranks: merging the ranks' rows (shared_merge.merge_history_rows) needs every step's
         # row and flags on the host, so the block stays full-rate and flush slices it after the merge
@@ -578,45 +570,47 @@ class DeviceLoop:
                 self._shared_snapshot()
             # (the steps the call has MADE, kept up to date as it goes: a caller that breaks out of
             # the generator early must not have the full count replayed -- ADVICE r5)
-            jentry = [0, bool(store), yield_every, thin_by]
+            jentry = JournalEntry(0, bool(store), yield_every, thin_by)
             self._sh_journal.append(jentry)
         block = None
         if store and iterations > 0 and (thin_by == 1 or host_thin):
-            block = self._new_block(iterations * thin_by, shared=self.sharded and s.comm.size > 1)
-            if host_thin:
-                block["thin_by"] = thin_by
+            block = self._new_block(iterations * thin_by, shared=self.sharded and s.comm.size > 1,
+                                    thin_by=thin_by if host_thin else 1)
             self.hist.append(block)
-        if not cont:
-            self._sync_cur_blobs()
         if thin_by == 1:
             yield from self._steps(iterations, yield_every, block, jentry)
         else:
             yield from self._sample_thinned(iterations, thin_by, store, yield_every, block, jentry)
 
-    def _new_block(self, rows, shared=False):
+    def _adopt(self, initial_state):
+        """the ensemble a call starts from -> whether it is the one already in HBM (a DeviceState
+        of this loop); any other state is checked, uploaded and evaluated"""
+        from .sampler import State
+        cont = isinstance(initial_state, DeviceState) and initial_state._loop is self
+        if not cont:
+            st = State(initial_state)
+            if st.coords.shape != (self.N, self.ndim):
+                raise ValueError("incompatible input dimensions")
+            self._init_state(st.coords, st.log_prob)
+            self._sync_cur_blobs()
+        return cont
+
+    @property
+    def _kept(self):
+        """the blobs a call keeps the history of"""
+        return (self.cur_blobs or []) if self.s.store_blobs else []
+
+    def _new_block(self, rows, shared=False, thin_by=1):
         """a history block of `rows` rows in HBM: coords, log-prob and every kept blob; `shared`:
         with what the merge of several ranks' rows needs"""
-        s, ctx, N = self.s, self.ctx, self.N
-        block = dict(n=0, coords=ctx.empty((rows, N * self.ndim)),
-                     logp=ctx.empty((rows, N)),
-                     blobs=[ctx.empty((rows, N * m)) for _, m, _, _ in
-                            (self.cur_blobs or [])] if s.store_blobs else [])
         if shared:
             # a shared ensemble's launches: who moved (and accepted) what, per row; the
             # blobs as they stood before the first row (rows of rejected moves are filled
-            # from the row before when the ranks' histories are merged)
+            # from the row before when the ranks' histories are merged: host copies where the
+            # last merge left them, no launch)
             self._sync_cur_blobs()
-            block["own"] = ctx.empty((rows, N), dtype=np.int32)
-            block["shared_rows"] = []  # [row0, row1) of every shared launch
-            block["cur0"] = []
-            if block["blobs"] and self._cur_host is not None:
-                block["cur0"] = self._cur_host  # (host copies the last merge left: no launch)
-            elif block["blobs"]:
-                for cur, m, _, _ in self.cur_blobs or []:
-                    c0 = ctx.empty((N, m))
-                    ctx.call("nh_copy", c0, cur, 8 * N * m)
-                    block["cur0"].append(c0)
-        return block
+        return loop_books.new_block(self.ctx, self.N, self.ndim, self._kept, rows, thin_by, shared,
+                                    self._cur_host)
 
     def sample_monitored(self, initial_state, max_rows, check_every, thin_by, on_check):
         """up to ``max_rows`` stored rows into ONE history block of that many rows (the memory of a
@@ -626,31 +620,23 @@ class DeviceLoop:
         chain where it is, in HBM; a true answer ends the call.  With thin_by > 1 the block is the
         compact one, in stored rows (_sample_thinned's staging, one staging block per internal
         call).  The books are those of plain calls: the block is a pending history block like any
-        other and holds ``block["n"]`` rows.  One GPU only -> the last state"""
-        from .sampler import State
+        other and holds ``block.n`` rows.  One GPU only -> the last state"""
         s = self.s
         if self.sharded:
             raise NotImplementedError("a monitored run with walkers sharded over several ranks")
-        cont = isinstance(initial_state, DeviceState) and initial_state._loop is self
-        if not cont:  # (as sample does)
-            st = State(initial_state)
-            if st.coords.shape != (self.N, self.ndim):
-                raise ValueError("incompatible input dimensions")
-            self._init_state(st.coords, st.log_prob)
+        self._adopt(initial_state)
         max_rows, check_every, thin_by = int(max_rows), int(check_every), int(thin_by)
         block = self._new_block(max_rows)
         self.hist.append(block)
-        if not cont:
-            self._sync_cur_blobs()
-        while block["n"] < max_rows:
-            g = min(check_every, max_rows - block["n"])
+        while block.n < max_rows:
+            g = min(check_every, max_rows - block.n)
             if thin_by == 1:
                 for _ in self._steps(g, 1 << 30, block, None):
                     pass
             else:
                 for _ in self._sample_thinned(g, thin_by, True, 1 << 30, None, None, compact=block):
                     pass
-            if on_check(block["coords"], block["n"]):
+            if on_check(block.coords, block.n):
                 break
         return DeviceState(self, s._rng)
 
@@ -664,7 +650,7 @@ class DeviceLoop:
         t rows fit, a stored row is t-1 steps without a history and one step with it, and the
         staging block holds one row.  `block` (several ranks): the full-rate block, thinned on
         the host by flush.  `compact` (a monitored run): the pending block that takes the rows,
-        from its row compact["n"] on, instead of a new one.  thin_info says what was done."""
+        from its row compact.n on, instead of a new one.  thin_info says what was done."""
         s, ctx, N = self.s, self.ctx, self.N
         group = rows if yield_every >= rows else max(1, int(yield_every))
         info = dict(thin_by=t, where="host" if block is not None else "none", stage_rows=0,
@@ -673,9 +659,7 @@ class DeviceLoop:
         stage = None
         split = False
         if store and rows > 0 and block is None:
-            widths = [N * self.ndim, N]
-            if s.store_blobs:
-                widths += [N * m for _, m, _, _ in (self.cur_blobs or [])]
+            widths = [N * self.ndim, N] + [N * b.m for b in self._kept]
             budget = int(float(os.environ.get("NAIMA_AMD_THIN_STAGE_MB", "512")) * (1 << 20))
 
             def alloc(r):  # (what the context's pool sets aside for r rows)
@@ -697,7 +681,7 @@ class DeviceLoop:
 
         def call(steps, blk):
             if blk is stage and stage is not None:
-                stage["n"] = 0
+                stage.n = 0
             for _ in self._steps(steps, 1 << 30, blk, jentry):
                 pass
             info["calls"].append((steps, steps if blk is not None else 0))
@@ -721,26 +705,21 @@ class DeviceLoop:
     def _compact(self, stage, compact, first, stride, nrows):
         """rows first, first + stride, ... of the staging block -> the compact block's next nrows
         rows: one launch for the chain, the log-probability and (up to six) blob histories"""
-        pairs = [(stage["coords"], compact["coords"]), (stage["logp"], compact["logp"])] + \
-            list(zip(stage["blobs"], compact["blobs"]))
-        for i in range(0, len(pairs), 8):
-            part = pairs[i:i + 8]
-            segs = (_lib.nh_thin_seg * len(part))(*[
-                _lib.nh_thin_seg(a.ptr, b.ptr, a.shape[1]) for a, b in part])
-            self.ctx.call("nh_hist_thin", segs, len(part), first, stride, nrows, compact["n"])
-        compact["n"] += nrows
+        for segs in stage.thin_segs(compact):
+            self.ctx.call("nh_hist_thin", segs, len(segs), first, stride, nrows, compact.n)
+        compact.n += nrows
         self._changes += 1
 
     def _steps(self, iterations, yield_every, block, jentry):
         """`iterations` ensemble steps from the ensemble in HBM, their rows appended to `block`
-        (None: no history) from its row block["n"] on"""
+        (None: no history) from its row block.n on"""
         # the launches append the chain history themselves (the nh_hist descriptor) when the
         # call keeps one and the launch's plan exists; else one pair of copies per step ...
         dev_hist = self.fused and block is not None and not (self.mega and self._hs is None)
         # ... and the blobs' histories too, in the one-launch mode
         blob_dev_hist = dev_hist and self.blobs_in_kernel
         # several steps per launch need whatever the call keeps to be kept by the launches
-        whole = (block is None or dev_hist) and not (block is not None and block["blobs"] and
+        whole = (block is None or dev_hist) and not (block is not None and block.blobs and
                                                      not blob_dev_hist)
         # the whole call as launches of the resident loop, one per block of moves: nothing of the
         # per-launch kernel's bookkeeping (history descriptor words, slice counter) is needed
@@ -759,15 +738,15 @@ class DeviceLoop:
         s.iteration += g
         s.steps_total += g
         if jentry is not None:
-            jentry[0] += g
+            jentry.made += g
         if block is not None:
-            block["n"] += g
+            block.n += g
         self._changes += 1
 
     def _sample_resident(self, iterations, block, jentry):
         """the call as launches of the resident loop, up to KSTEPS steps each, a launch checked
-        when the one behind it is queued (_rl_settle) -> the steps made: fewer than `iterations`
-        when a launch gave up, and the per-launch loop makes the rest"""
+        when the one behind it is queued (LaunchQueue.settle) -> the steps made: fewer than
+        `iterations` when a launch gave up, and the per-launch loop makes the rest"""
         ring = self.ring
         moves = self.s.moves(pinned=True)
         it = 0
@@ -776,24 +755,24 @@ class DeviceLoop:
             # the device (uploaded ahead by `launched`) unless this is the first call
             want = min(ring.KSTEPS, iterations - it)
             slice0 = ring.reserve(moves, want)
-            if len(self._rl_pending) >= 2:
+            if self._rl.queued >= 2:
                 # launch n + 1 is queued only once launch n - 1 is known to have ended well (launch
                 # n is running meanwhile: the device does not wait for this)
-                gave_up = self._rl_settle(keep=1)
+                gave_up = self._rl.settle(1, self._launch_report)
                 if gave_up is not None:
                     return self._rollback(gave_up)
             rec = self._run_resident(slice0, 2 * want, block)
             if rec is None:
                 return it  # (gave up: the per-launch loop replays these steps)
             if not self.shared:  # (a shared loop's launches are checked where all ranks are)
-                rec["it"] = it
-                self._rl_pending.append(rec)
+                rec.it = it
+                self._rl.push(rec)
             ring.launched(moves, want)
             it += want
             self._advance(want, block, jentry)
-            if it >= iterations and self._rl_pending:
+            if it >= iterations and self._rl.queued:
                 # the call's last launches: known to have ended well before the state is handed out
-                gave_up = self._rl_settle(keep=0)
+                gave_up = self._rl.settle(0, self._launch_report)
                 if gave_up is not None:
                     return self._rollback(gave_up)
             yield DeviceState(self, self.s._rng)
@@ -806,11 +785,7 @@ class DeviceLoop:
         s, ctx, ring, N = self.s, self.ctx, self.ring, self.N
         if self.fused:
             # (the per-launch kernel's history descriptor: where its launches append the chain)
-            words = [block["coords"].ptr, block["logp"].ptr, 0, block["coords"].shape[0]] \
-                if dev_hist else [0, 0, 0, 0]
-            if blob_dev_hist:
-                words = words + [hb.ptr for hb in block["blobs"]]
-            words = (words + [0, 0, 0, 0])[:8]
+            words = block.words(dev_hist, blob_dev_hist) if block is not None else [0] * 8
             ctx.call("nh_set_words", self.histd, (C.c_longlong * 8)(*words), 8)
         moves = s.moves(pinned=True)
         if it < iterations:
@@ -826,7 +801,7 @@ class DeviceLoop:
                 if self.mega and self._hs is not None:
                     # (the one-launch kernel writes the cursor itself, every launch)
                     ctx.call("nh_half_step_begin_block", self._hs.handle, 0,
-                             block["n"] if dev_hist else 0)
+                             block.n if dev_hist else 0)
                     if self._plan.stage is not None:  # (its other launch: StepPlan.stage_a)
                         ctx.call("nh_half_step_begin_block", self._plan.stage.handle, 0, 0)
                 else:
@@ -839,7 +814,7 @@ class DeviceLoop:
             mark, mark_pending = ring.block_mark(), True
             k = 0
             while k < K:
-                self._pos["slice"], self._pos["steps"] = 2 * k, (block["n"] - k) if dev_hist else 0
+                self._pos["slice"], self._pos["steps"] = 2 * k, (block.n - k) if dev_hist else 0
                 # several steps per graph launch when nothing has to happen on the host
                 # between them (history is kept by the kernel, nobody reads the states)
                 g = 1
@@ -868,7 +843,7 @@ class DeviceLoop:
                         self.multi_graphs[key] = self.multi_graph = self._capture_steps(k, g)
                     ctx.graph_launch(self.multi_graphs[key])
                 elif (self.split and self.graph2 is not None and self.fused and
-                        yield_every >= 2 and whole and not (block is not None and block["blobs"])):
+                        yield_every >= 2 and whole and not (block is not None and block.blobs)):
                     # sharded, nobody looks at the intermediate states: the accept of a
                     # half-step and the evaluation of the next are ONE graph, with the
                     # all-gather between two such graphs (two host calls per half-step
@@ -883,15 +858,9 @@ class DeviceLoop:
                     mark_pending = False
                 k += g
                 it += g
-                if block is not None:
-                    kk = block["n"]
-                    if not dev_hist:
-                        ctx.call("nh_copy", block["coords"].ptr + 8 * kk * N * self.ndim,
-                                 self.coords, 8 * N * self.ndim)
-                        ctx.call("nh_copy", block["logp"].ptr + 8 * kk * N, self.logp, 8 * N)
-                    if not blob_dev_hist:
-                        for hb, (cur, m, _, _) in zip(block["blobs"], self.cur_blobs or []):
-                            ctx.call("nh_copy", hb.ptr + 8 * kk * N * m, cur, 8 * N * m)
+                if block is not None and not (dev_hist and blob_dev_hist):
+                    block.copy_row(ctx, N, self.ndim, self.coords, self.logp, self.cur_blobs or [],
+                                   state=not dev_hist, blobs=not blob_dev_hist)
                 self._advance(g, block, jentry)
                 if yield_every < 2:
                     self._flush_pending()
@@ -908,9 +877,9 @@ class DeviceLoop:
         """the history row of the step the per-launch kernel closed last, which it leaves to the
         next launch of the block of moves: there is none"""
         self.ctx.call("nh_hist_append", self.coords, self.logp, self.N, self.ndim, self.histd,
-                      block["n"] - 1)
+                      block.n - 1)
         if blobs_too:
-            self.ctx.call("nh_half_step_append_blobs", self._hs.handle, block["n"] - 1)
+            self.ctx.call("nh_half_step_append_blobs", self._hs.handle, block.n - 1)
 
     # ------------------------------------------------------------- resident loop
     def _resident_ok(self):
@@ -938,7 +907,7 @@ class DeviceLoop:
                 self.resident_reason = _lib._lib.nh_last_error().decode()
                 return False
             self._run = h
-            self._rl_count, self._rl_pending = 0, []  # (the library numbers a loop's launches from 1)
+            self._rl.reset()  # (the library numbers a loop's launches from 1)
             self._adopt_run(hs, h)
         return True
 
@@ -1037,10 +1006,10 @@ class DeviceLoop:
         stamps = np.empty(self.N, dtype=np.int32)
         _lib._chk(_lib._lib.nh_half_step_run_counters(self.ctx.h, self._run, None,
                                                       stamps.ctypes.data, 2))
-        hosts = [cur.get().reshape(self.N, m) for cur, m, _, _ in self.cur_blobs or []]
+        hosts = [b.cur.get().reshape(self.N, b.m) for b in self.cur_blobs or []]
         shared_merge.merge_current_blobs(self.s.comm.group, self.s.comm.rank, stamps, hosts)
-        for (cur, _, _, _), host in zip(self.cur_blobs or [], hosts):
-            cur.set(host.ravel())
+        for b, host in zip(self.cur_blobs or [], hosts):
+            b.cur.set(host.ravel())
         self._cur_host = hosts  # (valid until a launch changes the blobs again)
 
     def _run_resident(self, slice0, nslices, block):
@@ -1049,21 +1018,15 @@ class DeviceLoop:
         ctx, hs = self.ctx, self._hs
         if self.shared:
             self._acc_dirty = True
-            own = block.get("own") if block is not None else None
+            own = block.own if block is not None else None
             _lib._chk(_lib._lib.nh_half_step_run_hist_flags(self._run, own.ptr if own is not None
                                                             else None))
             if self.s.store_blobs and self.cur_blobs:
                 self._cur_dirty = True
                 self._cur_host = None
             if own is not None:
-                block["shared_rows"].append((block["n"], block["n"] + nslices // 2))
-        hc = hl = None
-        hb, row0, cap = None, 0, 0
-        if block is not None:
-            hc, hl = block["coords"].ptr, block["logp"].ptr
-            row0, cap = block["n"], block["coords"].shape[0]
-            if block["blobs"]:
-                hb = (C.c_void_p * 4)(*([b.ptr for b in block["blobs"]] + [None] * 4)[:4])
+                block.shared_rows.append((block.n, block.n + nslices // 2))
+        hist_args = block.run_args() if block is not None else loop_books.NO_HISTORY
         books = self._checkpoint(block)
         probation = not self.shared and self._resident_trust < 2
         if probation:
@@ -1075,12 +1038,11 @@ class DeviceLoop:
             # with one launch per half-step.  (A shared ensemble: the ranks agree in
             # _create_shared_run / bench.py's rehearsal and raise together on a later time-out; a
             # one-GPU loop's later launches are checked a launch behind: _sample_resident.)
-            books["counts"] = self._read_counts(reset=False)
+            books.counts = self._read_counts(reset=False)
         if block is None and not self.shared and self.s.store_blobs and self.cur_blobs:
-            books["snap"] = self._snapshot_cur_blobs()
-        ctx.call("nh_half_step_run", hs.handle, self._run, slice0, nslices, hc, hl, hb, row0, cap)
-        self._rl_count += 1
-        books["launch"] = self._rl_count  # (the library numbers a loop's launches the same way)
+            books.snap = self._snapshot_cur_blobs()
+        ctx.call("nh_half_step_run", hs.handle, self._run, slice0, nslices, *hist_args)
+        books.launch = self._rl.launched()  # (the library numbers a loop's launches the same way)
         if probation:
             st = self.resident_status()
             if st != 0:
@@ -1101,13 +1063,13 @@ class DeviceLoop:
         (k_run_epilogue leaves the ensemble, the counters and the blobs as a launch that gave up
         found them).  Back to the books `rec` holds, the move stream made again up to its step;
         the per-launch loop takes over for good -> the step of the call to carry on from"""
-        void = sum(1 for r in self._rl_pending if r["launch"] >= rec["launch"])
-        self._rl_pending = []
+        void = self._rl.void_from(rec)
+        self._rl.drop()
         self.ctx.sync()  # (the void launches behind it: nothing of theirs may still be running)
-        self._leave_resident(_GAVE_UP % rec["status"], "%d block(s) of moves are replayed "
+        self._leave_resident(_GAVE_UP % rec.status, "%d block(s) of moves are replayed "
                              "and the run continues with one launch per half-step" % void, void, rec,
                              rewind=True)
-        return rec["it"]
+        return rec.it
 
     def _leave_resident(self, reason, then, failed, books, rewind=False):
         """the resident loop given up for good: `failed` launches of it void, the books back to
@@ -1119,29 +1081,17 @@ class DeviceLoop:
         self.resident_failed_launches += failed
         self._restore(books)
         if rewind:
-            self._rewind_moves(books["steps_total"])
+            self._rewind_moves(books.steps_total)
 
     def _checkpoint(self, block=None, counts=None):
         """the host's books as one record for _restore (`counts`: the device's NaN / forbidden
         counters to put back, when known here)"""
-        s = self.s
-        return dict(iteration=s.iteration, steps_total=s.steps_total, nlc=s.n_lnprob_calls,
-                    nwe=s.n_walker_evals, rl=self.resident_launches, nan_pending=self._nan_pending,
-                    forbidden_pending=self._forbidden_pending, hist_len=len(self.hist),
-                    block=block, block_n=block["n"] if block is not None else None,
-                    counts=counts, snap=None)
+        return Books.take(self.s, self, block, counts)
 
     def _restore(self, books):
-        s = self.s
-        self._read_counts(reset=False, set_to=books["counts"])  # (the replay counts them again)
-        self._restore_cur_blobs(books["snap"])  # (what launches that gave up may have written)
-        s.iteration, s.steps_total = books["iteration"], books["steps_total"]
-        s.n_lnprob_calls, s.n_walker_evals = books["nlc"], books["nwe"]
-        self.resident_launches = books["rl"]
-        self._nan_pending, self._forbidden_pending = books["nan_pending"], books["forbidden_pending"]
-        self.hist = self.hist[:books["hist_len"]]  # (what predates the checkpoint stays)
-        if books["block"] is not None:
-            books["block"]["n"] = books["block_n"]
+        self._read_counts(reset=False, set_to=books.counts)  # (the replay counts them again)
+        self._restore_cur_blobs(books.snap)  # (what launches that gave up may have written)
+        books.put_back(self.s, self)
 
     def _rewind_moves(self, steps):
         """the move stream made again from the seed (a fresh generator, every upload of the old one
@@ -1158,18 +1108,15 @@ class DeviceLoop:
     def _snapshot_cur_blobs(self):
         """device copies of the current blobs, in stream order ahead of the launch about to be
         queued (one of four sets: at most three launches are ever unsettled) -> the set's index"""
-        k = self._rl_count % len(self._cur_snaps)
-        if self._cur_snaps[k] is None:
-            self._cur_snaps[k] = [self.ctx.empty((self.N, m)) for _, m, _, _ in self.cur_blobs]
-        for dst, (cur, m, _, _) in zip(self._cur_snaps[k], self.cur_blobs):
-            self.ctx.call("nh_copy", dst, cur, 8 * self.N * m)
+        k = self._rl.count % len(self._cur_snaps)
+        self._cur_snaps[k] = loop_books.copy_blobs(self.ctx, self.N, self.cur_blobs,
+                                                   self._cur_snaps[k])
         return k
 
     def _restore_cur_blobs(self, k):
         if k is None or self._cur_snaps[k] is None:
             return
-        for src, (cur, m, _, _) in zip(self._cur_snaps[k], self.cur_blobs):
-            self.ctx.call("nh_copy", cur, src, 8 * self.N * m)
+        loop_books.copy_blobs(self.ctx, self.N, self.cur_blobs, self._cur_snaps[k], back=True)
         self._cur_host = None
 
     def _before_read(self):
@@ -1184,13 +1131,13 @@ class DeviceLoop:
         are still unsettled -- a caller iterating sample() launch by launch: wait for them; one that
         gave up is replayed when the iteration goes on, and until then the state on the device is
         the one BEFORE it"""
-        if self._rl_pending and self._run:
-            rec = self._rl_settle(keep=0)
+        if self._rl.queued and self._run:
+            rec = self._rl.settle(0, self._launch_report)
             if rec is not None:
                 raise _lib.NaimaHipError(
                     "a launch of the resident loop gave up waiting for a walker's record (status %d); "
                     "its block of moves is replayed when the iteration continues -- read the state "
-                    "after that" % rec["status"])
+                    "after that" % rec.status)
 
     # ------------------------------------------------ a shared ensemble: kept state and replay
     def _shared_snapshot(self):
@@ -1199,17 +1146,10 @@ class DeviceLoop:
         ctx = self.ctx
         self._flush_pending()
         # (the device's counters: drained at the kept state, the replay counts again)
-        snap = dict(self._checkpoint(counts=(0, 0)), coords=ctx.empty((self.N * self.ndim,)),
-                    logp=ctx.empty((self.N,)), nacc=ctx.empty((self.N,), dtype=np.int32), blobs=[])
-        ctx.call("nh_copy", snap["coords"], self.coords, 8 * self.N * self.ndim)
-        ctx.call("nh_copy", snap["logp"], self.logp, 8 * self.N)
-        ctx.call("nh_copy", snap["nacc"], self.nacc, 4 * self.N)
-        if self.s.store_blobs and self.cur_blobs:
-            self._sync_cur_blobs()  # (every rank's current blobs whole before they are kept)
-            for cur, m, _, _ in self.cur_blobs:
-                b = ctx.empty((self.N, m))
-                ctx.call("nh_copy", b, cur, 8 * self.N * m)
-                snap["blobs"].append(b)
+        snap = self._checkpoint(counts=(0, 0))
+        self._sync_cur_blobs()  # (every rank's current blobs whole before they are kept)
+        snap.ensemble = EnsembleCopy.take(ctx, self.N, self.ndim, self.coords, self.logp, self.nacc,
+                                          self._kept)
         self._sh_snap = snap
         self._sh_journal = []
 
@@ -1245,23 +1185,17 @@ class DeviceLoop:
         self._acc_shared, self._acc_dirty = 0.0, False
         self._cur_dirty, self._cur_host = False, None
         self._sh_snap, self._sh_journal = None, []
-        ctx.call("nh_copy", self.coords, snap["coords"], 8 * self.N * self.ndim)
-        ctx.call("nh_copy", self.logp, snap["logp"], 8 * self.N)
-        ctx.call("nh_copy", self.nacc, snap["nacc"], 4 * self.N)
-        for b, (cur, m, _, _) in zip(snap["blobs"], self.cur_blobs or []):
-            ctx.call("nh_copy", cur, b, 8 * self.N * m)
+        snap.ensemble.put_back(ctx, self.coords, self.logp, self.nacc, self.cur_blobs or [])
         self._leave_resident(
             "a launch of the resident loop over the shared ensemble gave up waiting for a record "
             "(status %d%s)" % (bad, "" if bad == mine else ", on another rank"),
             "every rank goes back %d step(s) to the last ensemble all of them held and carries on "
-            "with one launch and one all-gather per half-step" % (s.steps_total - snap["steps_total"]),
-            max(1, self.resident_launches - snap["rl"]), snap, rewind=True)
+            "with one launch and one all-gather per half-step" % (s.steps_total - snap.steps_total),
+            max(1, self.resident_launches - snap.rl), snap, rewind=True)
         self._replaying = True
         try:
-            for made, store, yield_every, tb in journal:
-                # (`made` counts steps: the same rows are stored again, every tb-th; steps past
-                # the last stored row of a call that was left early are made without a history)
-                for n, keep, by in ((made // tb, store, tb), (made % tb, False, 1)):
+            for jentry in journal:
+                for n, keep, by in jentry.replay_calls():
                     if n > 0:
                         for _ in self.sample(DeviceState(self, s._rng), n, keep,
                                              yield_every=1 << 30, thin_by=by):
@@ -1271,19 +1205,13 @@ class DeviceLoop:
         finally:
             self._replaying = False
 
-    def _rl_settle(self, keep):
-        """wait until all but the last `keep` queued launches are known to have ended; None, or
-        the record of the first one that gave up (it and everything queued behind it are void)"""
-        while len(self._rl_pending) > keep:
-            rec = self._rl_pending[0]
-            done, st, before = _lib._i(0), _lib._i(0), (C.c_int * 2)()
-            _lib._chk(_lib._lib.nh_half_step_run_report(self.ctx.h, self._run, rec["launch"], 1,
-                                                        C.byref(done), C.byref(st), None, None, before))
-            if st.value != 0:
-                rec["status"], rec["counts"] = st.value, (before[0], before[1])
-                return rec
-            self._rl_pending.pop(0)
-        return None
+    def _launch_report(self, launch):
+        """wait until launch number `launch` of the resident loop has ended -> (its status, the
+        (NaN, forbidden) counts as it found them): what LaunchQueue.settle asks"""
+        done, st, before = _lib._i(0), _lib._i(0), (C.c_int * 2)()
+        _lib._chk(_lib._lib.nh_half_step_run_report(self.ctx.h, self._run, launch, 1,
+                                                    C.byref(done), C.byref(st), None, None, before))
+        return st.value, (before[0], before[1])
 
     def _read_counts(self, reset, set_to=None):
         """(NaN log-probabilities, proposals forbidden by the prior) the kernels have counted on
@@ -1514,32 +1442,22 @@ class DeviceLoop:
             return
         self._meet()
         s = self.s
+        # (the ranks' rows of a shared loop's block are merged at full rate, before a thinned call's
+        # rows are thinned)
+        merge = functools.partial(shared_merge.merge_history_rows, s.comm.group, s.comm.rank) \
+            if self.shared else None
         for block in self.hist:
-            n = block["n"]
-            if n == 0:
+            rows = block.host_rows(self.N, self.ndim, self.cur_blobs or [], merge)
+            if rows is None:
                 continue
-            c = block["coords"].get()[:n].reshape(n, self.N, self.ndim)
-            l = block["logp"].get()[:n].reshape(n, self.N)
-            per = [hb.get()[:n].reshape(n, self.N, m)
-                   for hb, (cur, m, _, trail) in zip(block["blobs"], self.cur_blobs or [])]
-            if self.shared and block.get("own") is not None:
-                cur0 = [b_ if isinstance(b_, np.ndarray) else b_.get() for b_ in block["cur0"]]
-                shared_merge.merge_history_rows(
-                    s.comm.group, s.comm.rank, block["own"].get()[:n].reshape(n, self.N),
-                    block["shared_rows"], cur0, c, l, per)
-            tb = block.get("thin_by", 1)
-            if tb > 1:  # (several ranks: a thinned call's rows, full-rate up to here)
-                c, l, per = c[tb - 1::tb], l[tb - 1::tb], [a[tb - 1::tb] for a in per]
-                n = c.shape[0]
-                if n == 0:
-                    continue
+            c, l, per = rows
+            n = c.shape[0]
             s._chain.extend(list(c))
             s._logp.extend(list(l))
-            if block["blobs"]:
-                per = [a.reshape((n, self.N) + trail)
-                       for a, (cur, m, _, trail) in zip(per, self.cur_blobs)]
-                for j, v in self.const_blobs:
-                    per.insert(j, np.full((n, self.N), v))
+            if block.blobs:
+                per = [a.reshape((n, self.N) + b.trail) for a, b in zip(per, self.cur_blobs)]
+                per = loop_books.with_const_blobs(per, self.const_blobs,
+                                                  lambda v: np.full((n, self.N), v))
                 if s._blobs is None:
                     s._blobs = [[] for _ in per]
                 for j, a in enumerate(per):

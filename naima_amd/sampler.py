@@ -252,11 +252,11 @@ class EnsembleSampler(InfoCritMixin, PredictiveMixin, EvidenceMixin):
         if dev is None or thin != 1 or self.comm.size > 1 or len(self._chain) or len(dev.hist) != 1:
             return None
         b = dev.hist[0]
-        if b["n"] < 1 or b.get("own") is not None or b.get("thin_by", 1) != 1:
+        if not b.plain:
             return None
         dev._meet()
-        return DeviceChain(matrix_on(b["coords"], b["n"], self.nwalkers * self.ndim),
-                           self.nwalkers, self.ndim, matrix_on(b["logp"], b["n"], self.nwalkers))
+        return DeviceChain(matrix_on(b.coords, b.n, self.nwalkers * self.ndim),
+                           self.nwalkers, self.ndim, matrix_on(b.logp, b.n, self.nwalkers))
 
     def get_ess(self, kind="bulk", discard=0, thin=1):
         """The bulk or tail effective sample size of each parameter

@@ -57,7 +57,7 @@ def main():
         t1 = time.perf_counter()
     dev = s._dev
     info = getattr(dev, "thin_info", None)
-    kept_rows = sum(b["coords"].shape[0] for b in dev.hist)
+    kept_rows = sum(b.coords.shape[0] for b in dev.hist)
     t2 = time.perf_counter()
     chain = s.get_chain()
     t3 = time.perf_counter()
@@ -76,11 +76,11 @@ def main():
                 ctx.sync()
                 a = time.perf_counter()
                 for _ in range(20):
-                    compact["n"] = 0
+                    compact.n = 0
                     dev._compact(stage, compact, t - 1, t, c)
                 ctx.sync()
                 times.append((time.perf_counter() - a) / 20 * 1e6)
-            row = 8 * nw * (nd + 1 + sum(m for _, m, _, _ in dev.cur_blobs))
+            row = 8 * nw * (nd + 1 + sum(b.m for b in dev.cur_blobs))
             out["compaction_us"] = float(np.median(times[1:]))
             out["compaction_rows"] = c
             out["compaction_gb_per_s"] = 2 * c * row / (out["compaction_us"] * 1e-6) / 1e9
