@@ -1162,6 +1162,73 @@ int nh_bridge_sums(nh_ctx* ctx, const double* l1, long long N1, const double* l2
                    double lstar, double s1, double s2, double r, double* out, double* f1,
                    double* f2);
 
+/* ---- reweighting a finished fit: PSIS weights and weighted reductions -------------------------
+ * What importance reweighting of the samples already held needs: the log-ratio of a new target
+ * from columns of the pointwise matrix, Pareto-smoothed self-normalised log-weights (Vehtari,
+ * Simpson, Gelman, Yao & Gabry), weighted moments and order statistics, and an equal-weight
+ * sample by systematic resampling.  FP64; every matrix is a row-major DEVICE matrix [M][ld] with
+ * ncol <= ld columns in use; every other array is a DEVICE array unless marked host; results stay
+ * on the device.  Stream-ordered on the context's stream, no host synchronisation, library
+ * scratch, 64-bit row indices.  Deterministic: integer atomics only; every floating-point sum has
+ * an order fixed by the shapes alone (in a sorted column, by the sorted values), so repeated calls
+ * are bit-identical.
+ * Every entry point that takes a matrix: NH_EINVAL for a null argument, M == 0, M >= 2^31,
+ *   ncol < 1, ncol > ld.
+ * A WEIGHT COLUMN is a pointer lw to its first entry and a row stride ldw >= 1 (NH_EINVAL
+ *   otherwise), holding NORMALISED log-weights (a column of nh_psis_weights' lw).  A row with
+ *   lw = -inf has weight zero: it is left out of every reduction below whatever its value, a NaN
+ *   included.  Every other row counts as a row of positive weight, w = exp(lw).
+ * nh_row_sums_select: out[s * ldo] = sign * sum_j L[s][cols[j]] for s < M, added in the order of
+ *   cols (host int [n]; a column may repeat); n == 0 writes zeros (cols may be NULL then).
+ *   NH_EINVAL also: n < 0, a column outside [0, ncol), sign other than +1 or -1, ldo < 1.
+ * nh_psis_weights: per column k of the log-ratios lr, with x_s = lr[s][k] - max_s lr[s][k], Mt the
+ *   tail length and lsel [ncol] the order statistic of rank M - Mt - 1 of every column of lr
+ *   (nh_column_select): cut = max(lsel[k] - max_k, log(DBL_MIN)); the tail is the n <= Mt rows
+ *   with x > cut, sorted by (value, row index); the fit and the smoothing are nh_psis_columns'
+ *   (n <= 4, always for Mt == 0: pareto_k = +inf and nothing is smoothed -- plain self-normalised
+ *   weights).  Writes lw[s * ldw + k] = x_s - logsumexp_s(x) (columns ncol..ldw-1 are not
+ *   touched), pareto_k [ncol], n_tail (int64 [ncol]) = n, ess [ncol] = 1 / sum_s exp(2 lw) (Kish)
+ *   and lmean [ncol] = logsumexp_s(lr) - log M of the RAW ratios, the estimate of
+ *   log(Z_new / Z_old).  An entry -inf is legal: weight zero, never a tail row.  A column that
+ *   holds a NaN or a +inf, or no finite entry, gets NaN in every row of lw and in pareto_k, ess and
+ *   lmean, and n_tail = 0: no partial result; status (int32 [ncol]) counts its NaN and +inf
+ *   entries (M for a column of -inf alone), 0 for a column that got weights.
+ *   NH_EINVAL also: ncol > ldw, Mt outside [0, M), Mt > NH_PSIS_MAX_TAIL.
+ * nh_weighted_moments: out [3][ncol] = per column the number of rows of positive weight (as a
+ *   double), the weighted mean sum w x / sum w and the weighted variance sum w (x - mean)^2 /
+ *   sum w.  Two passes, per-chunk partials added in chunk order (the tiling of
+ *   nh_column_moments).  Equal values have that value as their mean and variance exactly 0; a
+ *   non-finite value in a row of positive weight, or no such row, makes mean and variance NaN.
+ * nh_weighted_select: the rows of positive weight of a column sorted ascending by (value, row
+ *   index), -0.0 == +0.0; c_i the inclusive running sum of w in that order, C the last one.
+ *   out[j][col] ([nq][ncol]) = the value of the first i with c_i >= q[j] * C and c_i > 0.  A NaN
+ *   value under positive weight, or C not positive, gives NaN in the column's nq entries.  The
+ *   sort is nh_rank_columns' (its scratch rule too: columns in groups above the budget); the
+ *   running sum's order depends on M alone and it never decreases.
+ *   NH_EINVAL also: q[j] (host double [nq]) outside [0, 1], nq outside [1, 16].
+ * nh_resample_systematic: with c_i the inclusive running sum of w over the M rows IN ROW ORDER and
+ *   C the last one, idx[j] (int64 [n_out]) = the first i with c_i >= ((u0 + j) / n_out) * C and
+ *   w_i > 0: row i is drawn floor(n_out w_i / C) or one more times, the indices never decrease.
+ *   Without a positive C every idx[j] is -1.  NH_EINVAL: a null argument, M == 0, M >= 2^31,
+ *   ldw < 1, u0 outside [0, 1), n_out outside [1, 2^31).
+ * nh_gather_rows: out[j * ldo + c] = x[idx[j] * ld + c] for j < n_out, c < ncol; idx (int64
+ *   [n_out]) must hold rows of x.  NH_EINVAL: a null argument, n_out outside [1, 2^31), ncol < 1,
+ *   ncol > ld, ncol > ldo. */
+int nh_row_sums_select(nh_ctx* ctx, const double* L, long long M, int ncol, long long ld,
+                       const int* cols /*host*/, int n, int sign, double* out, long long ldo);
+int nh_psis_weights(nh_ctx* ctx, const double* lr, long long M, int ncol, long long ld, int Mt,
+                    const double* lsel, double* lw, long long ldw, double* pareto_k,
+                    long long* n_tail, double* ess, double* lmean, int* status);
+int nh_weighted_moments(nh_ctx* ctx, const double* x, long long M, int ncol, long long ld,
+                        const double* lw, long long ldw, double* out);
+int nh_weighted_select(nh_ctx* ctx, const double* x, long long M, int ncol, long long ld,
+                       const double* lw, long long ldw, const double* q /*host*/, int nq,
+                       double* out);
+int nh_resample_systematic(nh_ctx* ctx, const double* lw, long long ldw, long long M, double u0,
+                           long long n_out, long long* idx);
+int nh_gather_rows(nh_ctx* ctx, const double* x, long long ld, const long long* idx,
+                   long long n_out, int ncol, double* out, long long ldo);
+
 #ifdef __cplusplus
 }
 #endif

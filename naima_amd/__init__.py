@@ -25,6 +25,7 @@ from . import posterior  # noqa: F401
 from . import infocrit  # noqa: F401
 from . import predictive  # noqa: F401
 from . import evidence  # noqa: F401
+from . import reweight  # noqa: F401
 from .datatable import validate_data_table  # noqa: F401
 
 __version__ = "0.1.0"

@@ -192,6 +192,12 @@ _SIGS = {
     "nh_mvn_logpdf": [_dp, _dp, _ll, _ll, _ll, _ll, _i, _i, _dp, _dp, _dp, _dp],
     "nh_bridge_l2": [_dp, _dp, _dp, _ll, _dp, _i, _dp],
     "nh_bridge_sums": [_dp, _dp, _ll, _dp, _ll, _d, _d, _d, _d, _dp, _dp, _dp],
+    "nh_row_sums_select": [_dp, _dp, _ll, _i, _ll, C.POINTER(_i), _i, _i, _dp, _ll],
+    "nh_psis_weights": [_dp, _dp, _ll, _i, _ll, _i, _dp, _dp, _ll, _dp, _dp, _dp, _dp, _dp],
+    "nh_weighted_moments": [_dp, _dp, _ll, _i, _ll, _dp, _ll, _dp],
+    "nh_weighted_select": [_dp, _dp, _ll, _i, _ll, _dp, _ll, C.POINTER(_d), _i, _dp],
+    "nh_resample_systematic": [_dp, _dp, _ll, _ll, _d, _ll, _dp],
+    "nh_gather_rows": [_dp, _dp, _ll, _dp, _ll, _i, _dp, _ll],
 }
 EXPORTS = tuple(_SIGS) + ("nh_last_error", "nh_version", "nh_ssc_table_bytes")
 

@@ -12,6 +12,7 @@ from . import units as u
 from .datatable import DataTable
 from .infocrit import InfoCritMixin
 from .predictive import PredictiveMixin
+from .reweight import ReweightMixin
 
 __all__ = ["save_run", "read_run", "save_results_table", "find_ML", "save_diagnostic_plots"]
 
@@ -160,9 +161,10 @@ def save_run(filename, sampler, compression=True, clobber=False):
     return filename
 
 
-class _Result(InfoCritMixin, PredictiveMixin):
+class _Result(InfoCritMixin, PredictiveMixin, ReweightMixin):
     """what read_run returns: chain / log-prob / blobs with emcee's accessor names, and the
-    sampler's get_pointwise_log_likelihood / waic / loo / get_posterior_predictive / ppc"""
+    sampler's get_pointwise_log_likelihood / waic / loo / get_posterior_predictive / ppc /
+    reweight / influence"""
 
     def __init__(self, chain, log_prob, blobs, blob_units, data, labels, run_info, accf):
         self._chain, self._lp, self._blobs = chain, log_prob, blobs

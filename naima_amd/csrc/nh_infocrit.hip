@@ -36,23 +36,9 @@
 // in the tail, by the sorted values), so repeated calls give bit-identical results.  Row indices
 // are 64-bit, M < 2^31.  Every launch is on the context's stream; nothing synchronises with the
 // host.
-#include "nh_colred.h"
-
-#include <cfloat>
+#include "nh_gpd.h"
 
 namespace {
-
-constexpr int CRIT_TAIL_MAX = NH_PSIS_MAX_TAIL;      // tail entries a workgroup's LDS is sized for
-constexpr int CRIT_MAX_CAND = 96;                    // 30 + floor(sqrt(4096)) = 94 candidates b_j
-constexpr double CRIT_LOG_TINY = -708.3964185322641; // log(DBL_MIN)
-
-__device__ __forceinline__ double crit_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-__device__ __forceinline__ double crit_wave_allsum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // ---------------------------------------------------------------- pointwise terms
 __global__ __launch_bounds__(PO_THREADS) void k_crit_pointwise(
@@ -246,29 +232,6 @@ __global__ __launch_bounds__(PO_THREADS) void k_crit_split(
   }
 }
 
-// an order-preserving 64-bit key of a double that is not NaN, and back (nh_select.hip)
-__device__ __forceinline__ unsigned long long crit_key(double v) {
-  unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double crit_value(unsigned long long k) {
-  unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  return __longlong_as_double((long long)b);
-}
-
-// the sum / the maximum of one value per thread, the same in every thread (a fixed tree)
-template <typename F>
-__device__ __forceinline__ double crit_block_reduce(double v, double* red, int tid, F op) {
-  __syncthreads();  // (red may still be read from the reduction before)
-  red[tid] = v;
-  for (int s = PO_THREADS >> 1; s > 0; s >>= 1) {
-    __syncthreads();
-    if (tid < s) red[tid] = op(red[tid], red[tid + s]);
-  }
-  __syncthreads();
-  return red[0];
-}
-
 // one workgroup per column: sort the tail, fit, smooth, finish the two log-sum-exps
 __global__ __launch_bounds__(PO_THREADS) void k_crit_tail(
     const double* __restrict__ L, int ncol, long long ld, long long nch, int cap,
@@ -276,105 +239,19 @@ __global__ __launch_bounds__(PO_THREADS) void k_crit_tail(
     const double* __restrict__ part, const double* __restrict__ tx, const int* __restrict__ trow,
     const unsigned* __restrict__ cnt, double* __restrict__ pareto_k, long long* __restrict__ n_tail,
     double* __restrict__ elpd) {
-  __shared__ unsigned long long key[CRIT_TAIL_MAX];  // the sort's keys, then the tail's x
-  __shared__ double tt[CRIT_TAIL_MAX];               // t_i = exp(x_i) - exp(cut)
-  __shared__ int row[CRIT_TAIL_MAX];
-  __shared__ double bj[CRIT_MAX_CAND], lj[CRIT_MAX_CAND], wj[CRIT_MAX_CAND];
-  __shared__ double red[PO_THREADS];
-  __shared__ double bpost;
-  double* xs = reinterpret_cast<double*>(key);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  CRIT_TAIL_LDS(s);
+  const int tid = threadIdx.x;
   const int c = blockIdx.x;
   const int n = (int)min(cnt[c], (unsigned)min(cap, CRIT_TAIL_MAX));
   const double lmin = stats[4 * ncol + c];
   const double cut = crit_cut(lmin, lsel[c]);
   const double ecut = exp(cut);
-
-  // ---- the list, padded to a power of two with keys behind every value, sorted by (value, row)
-  int P = 2;
-  while (P < n) P <<= 1;
-  for (int i = tid; i < P; i += PO_THREADS) {
-    key[i] = i < n ? crit_key(tx[(long long)c * cap + i]) : ~0ull;
-    row[i] = i < n ? trow[(long long)c * cap + i] : 0x7fffffff;
-  }
-  for (int k = 2; k <= P; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      __syncthreads();
-      for (int i = tid; i < P; i += PO_THREADS) {
-        const int o = i ^ j;
-        if (o > i) {  // (each pair belongs to one thread)
-          const unsigned long long ka = key[i], kb = key[o];
-          const int ra = row[i], rb = row[o];
-          const bool gt = ka > kb || (ka == kb && ra > rb);
-          if (gt == ((i & k) == 0)) {
-            key[i] = kb; key[o] = ka;
-            row[i] = rb; row[o] = ra;
-          }
-        }
-      }
-    }
-  }
-  __syncthreads();
-  for (int i = tid; i < n; i += PO_THREADS) {
-    const double xv = crit_value(key[i]);
-    xs[i] = xv;  // (in place: the same eight bytes, this thread's own)
-    tt[i] = exp(xv) - ecut;
-  }
-  __syncthreads();
-
-  // ---- Zhang & Stephens' fit on the sorted t
-  double kpar = INFINITY, sigma = 0.0;
-  if (n > 4) {  // (n is the workgroup's: every barrier below is met by all threads)
-    const double dn = (double)n;
-    const int m = 30 + (int)floor(sqrt(dn));
-    if (tid < m) {
-      double b = 1.0 - sqrt((double)m / ((double)(tid + 1) - 0.5));
-      b /= 3.0 * tt[(int)(dn / 4.0 + 0.5) - 1];
-      b += 1.0 / tt[n - 1];
-      bj[tid] = b;
-    }
-    __syncthreads();
-    for (int j = wave; j < m; j += PO_THREADS / 64) {  // a wave per candidate
-      const double b = bj[j];
-      double s = 0.0;
-      for (int i = lane; i < n; i += 64) s += log1p(-b * tt[i]);
-      s = crit_wave_allsum(s);
-      if (lane == 0) {
-        const double kk = s / dn;
-        lj[j] = dn * (log(-(b / kk)) - kk - 1.0);
-      }
-    }
-    __syncthreads();
-    if (tid < m) {
-      double s = 0.0;
-      for (int i = 0; i < m; ++i) s += exp(lj[i] - lj[tid]);
-      const double w = 1.0 / s;
-      wj[tid] = (w >= 10.0 * DBL_EPSILON) ? w : 0.0;  // (dropped; a NaN weight too)
-    }
-    __syncthreads();
-    if (tid == 0) {
-      double sw = 0.0, b = 0.0;
-      for (int j = 0; j < m; ++j) sw += wj[j];
-      for (int j = 0; j < m; ++j) b += bj[j] * (wj[j] / sw);
-      bpost = b;
-    }
-    __syncthreads();
-    const double b = bpost;
-    double s = 0.0;
-    for (int i = tid; i < n; i += PO_THREADS) s += log1p(-b * tt[i]);
-    s = crit_block_reduce(s, red, tid, [](double p, double q) { return p + q; });
-    const double kp = s / dn;
-    sigma = -kp / b;
-    kpar = (dn * kp + 5.0) / (dn + 10.0);
-    if (po_finite(kpar)) {  // the tail becomes the fitted distribution's quantiles
-      for (int i = tid; i < n; i += PO_THREADS) {
-        const double lp = log1p(-((double)i + 0.5) / dn);
-        const double g = fabs(kpar) < DBL_EPSILON ? -lp : expm1(-kpar * lp) / kpar;
-        const double v = log(g * sigma + ecut);
-        xs[i] = v > 0.0 ? 0.0 : v;  // (a NaN stays one)
-      }
-    }
-  }
+  // ---- the tail sorted by (value, row), fitted and smoothed (nh_gpd.h)
+  const double kpar = crit_tail_fit(s, tx + (long long)c * cap, trow + (long long)c * cap, n, ecut, tid);
+  double* xs = reinterpret_cast<double*>(s.key);
+  double* tt = s.tt;
+  double* red = s.red;
+  const int* row = s.row;
 
   // ---- lw = x - logsumexp(x), elpd = logsumexp(lw + L): the tail's share of both sums, the
   // second one shifted by the tail's largest exponent (smoothing may lift x + L above min)

@@ -15,38 +15,18 @@
 //                   into status (one integer atomic per wave);
 //   eight passes of a least-significant-digit radix sort of the row INDEX (8-bit digits; the key
 //   is read through the index, so an element costs 16 bytes of scratch: key, and the index twice):
-//     k_rank_hist     per-workgroup digit histogram in LDS (integer LDS atomics) -> counts
-//                     [column][digit][workgroup];
-//     k_rank_scan     one workgroup per column: exclusive scan in (digit, workgroup) order;
-//     k_rank_scatter  stable scatter: a tile is walked in chunks of 256 in order; within a chunk a
-//                     lane's offset is the number of lower lanes of its wave with the same digit
-//                     (eight ballots) plus the counts of the lower waves -- no atomics, so equal
-//                     digits keep their order and every pass is reproducible bit for bit;
+//   k_rank_hist, k_rank_scan and k_rank_scatter of nh_radix.h, which nh_reweight.hip shares;
 //   k_rank_ties     position i of the sorted run finds the first and last position of its key (a
 //                     few neighbours, then a binary search) and writes (first + last) / 2 + 1
 //                     through the index; a column with a non-finite value is written NaN throughout.
 // Every launch is on the context's stream; nothing synchronises with the host.
-#include "nh_common.h"
-
-#include <algorithm>
+#include "nh_radix.h"
 
 namespace {
 
-constexpr int RK_THREADS = 256;
-constexpr int RK_WAVES = RK_THREADS / 64;
-constexpr int RK_CHUNKS = 16;                     // chunks of RK_THREADS elements per tile
-constexpr int RK_TILE = RK_THREADS * RK_CHUNKS;   // elements of a column per workgroup
 constexpr int RK_NEAR = 4;                        // neighbours looked at before the binary search
-constexpr size_t RK_BUDGET = (size_t)256 << 20;   // scratch per group of columns
 
 __device__ __forceinline__ double rk_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-// finite doubles in their order, -0.0 == +0.0 (non-finite values never get a rank)
-__device__ __forceinline__ unsigned long long rk_key(double v) {
-  if (v == 0.0) v = 0.0;  // -0.0 -> +0.0
-  unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
 
 __device__ __forceinline__ long long rk_src(long long e, long long row0, long long ld,
                                             long long cstride, int npool, int p) {
@@ -70,103 +50,6 @@ __global__ __launch_bounds__(RK_THREADS) void k_rank_keys(const double* __restri
   unsigned long long m = __builtin_amdgcn_ballot_w64(bad);
   if (m && (threadIdx.x & 63) == 0)
     __hip_atomic_fetch_add(status + p, (int)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ unsigned rk_digit(const unsigned long long* __restrict__ keys,
-                                             const unsigned* __restrict__ idx, long long i, int shift) {
-  unsigned long long k = keys[idx ? (long long)idx[i] : i];
-  return (unsigned)(k >> shift) & 255u;
-}
-
-// counts[(g * 256 + d) * nblk + b] = keys of column g's tile b with digit d
-__global__ __launch_bounds__(RK_THREADS) void k_rank_hist(const unsigned long long* __restrict__ keys,
-                                                          const unsigned* __restrict__ idx_in,
-                                                          long long S, int shift, unsigned nblk,
-                                                          unsigned* __restrict__ counts) {
-  __shared__ unsigned hist[256];
-  const unsigned long long* kc = keys + (long long)blockIdx.y * S;
-  const unsigned* ic = idx_in ? idx_in + (long long)blockIdx.y * S : nullptr;
-  hist[threadIdx.x] = 0u;
-  __syncthreads();
-  long long i0 = (long long)blockIdx.x * RK_TILE;
-  for (int c = 0; c < RK_CHUNKS; ++c) {
-    long long i = i0 + c * RK_THREADS + threadIdx.x;
-    if (i < S)
-      __hip_atomic_fetch_add(hist + rk_digit(kc, ic, i, shift), 1u, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_WORKGROUP);
-  }
-  __syncthreads();
-  counts[((long long)blockIdx.y * 256 + threadIdx.x) * nblk + blockIdx.x] = hist[threadIdx.x];
-}
-
-// one workgroup per column: counts -> where each (digit, tile) starts in the sorted column
-__global__ __launch_bounds__(256) void k_rank_scan(unsigned* __restrict__ counts, unsigned nblk) {
-  __shared__ unsigned scan[256];
-  int t = threadIdx.x;
-  unsigned* cd = counts + ((long long)blockIdx.x * 256 + t) * nblk;
-  unsigned tot = 0u;
-  for (unsigned b = 0; b < nblk; ++b) tot += cd[b];
-  scan[t] = tot;
-  __syncthreads();
-  for (int off = 1; off < 256; off <<= 1) {  // inclusive Hillis-Steele scan of the 256 digits
-    unsigned v = t >= off ? scan[t - off] : 0u;
-    __syncthreads();
-    scan[t] += v;
-    __syncthreads();
-  }
-  unsigned run = scan[t] - tot;
-  for (unsigned b = 0; b < nblk; ++b) {
-    unsigned n = cd[b];
-    cd[b] = run;
-    run += n;
-  }
-}
-
-__global__ __launch_bounds__(RK_THREADS) void k_rank_scatter(const unsigned long long* __restrict__ keys,
-                                                             const unsigned* __restrict__ idx_in,
-                                                             unsigned* __restrict__ idx_out,
-                                                             long long S, int shift, unsigned nblk,
-                                                             const unsigned* __restrict__ counts) {
-  __shared__ unsigned base[256];             // where the next key of each digit goes
-  __shared__ unsigned wcnt[RK_WAVES][256];   // this chunk's keys per (wave, digit)
-  const unsigned long long* kc = keys + (long long)blockIdx.y * S;
-  const unsigned* ic = idx_in ? idx_in + (long long)blockIdx.y * S : nullptr;
-  unsigned* oc = idx_out + (long long)blockIdx.y * S;
-  const int t = threadIdx.x, w = t >> 6, lane = t & 63;
-  base[t] = counts[((long long)blockIdx.y * 256 + t) * nblk + blockIdx.x];
-  for (int q = 0; q < RK_WAVES; ++q) wcnt[q][t] = 0u;
-  __syncthreads();
-  const unsigned long long below = (1ull << lane) - 1ull;
-  long long i0 = (long long)blockIdx.x * RK_TILE;
-  for (int c = 0; c < RK_CHUNKS; ++c) {
-    long long i = i0 + c * RK_THREADS + t;
-    if (i0 + c * RK_THREADS >= S) break;  // (uniform over the workgroup)
-    bool live = i < S;
-    unsigned src = 0u, d = 0u;
-    if (live) {
-      src = ic ? ic[i] : (unsigned)i;
-      d = (unsigned)(kc[src] >> shift) & 255u;
-    }
-    // the live lanes of this wave with this lane's digit
-    unsigned long long same = __builtin_amdgcn_ballot_w64(live);
-    for (int b = 0; b < 8; ++b) {
-      unsigned long long m = __builtin_amdgcn_ballot_w64((d >> b) & 1u);
-      same &= ((d >> b) & 1u) ? m : ~m;
-    }
-    unsigned before = (unsigned)__popcll(same & below);
-    if (live && before == 0u) wcnt[w][d] = (unsigned)__popcll(same);  // one writer per (wave, digit)
-    __syncthreads();
-    if (live) {
-      unsigned pos = base[d] + before;
-      for (int q = 0; q < w; ++q) pos += wcnt[q][d];
-      oc[pos] = src;
-    }
-    __syncthreads();
-    unsigned n = 0u;
-    for (int q = 0; q < RK_WAVES; ++q) { n += wcnt[q][t]; wcnt[q][t] = 0u; }
-    base[t] += n;
-    __syncthreads();
-  }
 }
 
 // r[idx[i]] = the mean of the 1-based positions the key of sorted position i occupies
@@ -344,45 +227,24 @@ extern "C" int nh_rank_columns(nh_ctx* ctx, const double* x, long long row0, lon
   int rc = rk_check_pool(__func__, row0, nrows, ld, cstride, npool, ncolp);
   if (rc) return rc;
   const long long S = nrows * npool;
-  const unsigned nblk = (unsigned)((S + RK_TILE - 1) / RK_TILE);
-  // per column: keys 8 S | two index buffers 4 S each | counts 256 nblk words
-  const size_t per_col = (size_t)S * 16 + (size_t)nblk * 256 * 4;
-  size_t budget = RK_BUDGET;
-  if (const char* e = getenv("NAIMA_AMD_RANK_SCRATCH_KIB")) budget = (size_t)std::max(1, atoi(e)) << 10;
-  int G = (int)std::min<size_t>(std::max<size_t>(budget / per_col, 1), 65535);
-  G = std::min(G, ncolp);
+  const int G = rk_group(S, ncolp, 0);
   void* base = nullptr;
-  rc = nh_scratch(ctx, per_col * G, &base);
+  rc = nh_scratch(ctx, rk_bytes_per_column(S) * G, &base);
   if (rc) return rc;
-  char* b = (char*)base;
-  auto* keys = (unsigned long long*)b;
-  auto* ia = (unsigned*)(b + (size_t)G * S * 8);
-  auto* ib = (unsigned*)(b + (size_t)G * S * 12);
-  auto* counts = (unsigned*)(b + (size_t)G * S * 16);
+  const rk_buffers b(base, S, G);
   hipStream_t s = ctx->stream;
   NH_CHECK_HIP(hipMemsetAsync(status, 0, (size_t)ncolp * sizeof(int), s));
   const unsigned eb = (unsigned)((S + RK_THREADS - 1) / RK_THREADS);
   for (int c0 = 0; c0 < ncolp; c0 += G) {
     const int g = std::min(G, ncolp - c0);
     hipLaunchKernelGGL(k_rank_keys, dim3(eb, g), dim3(RK_THREADS), 0, s, x, row0, ld, cstride, npool,
-                       S, c0, keys, status);
+                       S, c0, b.keys, status);
     NH_CHECK_HIP(hipGetLastError());
     const unsigned* in = nullptr;
-    unsigned* out = ia;
-    for (int shift = 0; shift < 64; shift += 8) {
-      hipLaunchKernelGGL(k_rank_hist, dim3(nblk, g), dim3(RK_THREADS), 0, s, keys, in, S, shift, nblk,
-                         counts);
-      NH_CHECK_HIP(hipGetLastError());
-      hipLaunchKernelGGL(k_rank_scan, dim3(g), dim3(256), 0, s, counts, nblk);
-      NH_CHECK_HIP(hipGetLastError());
-      hipLaunchKernelGGL(k_rank_scatter, dim3(nblk, g), dim3(RK_THREADS), 0, s, keys, in, out, S, shift,
-                         nblk, counts);
-      NH_CHECK_HIP(hipGetLastError());
-      in = out;
-      out = out == ia ? ib : ia;
-    }
-    hipLaunchKernelGGL(k_rank_ties, dim3(eb, g), dim3(RK_THREADS), 0, s, keys, in, S, c0, ncolp, status,
-                       r);
+    rc = rk_sort(s, b, S, g, &in);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_rank_ties, dim3(eb, g), dim3(RK_THREADS), 0, s, b.keys, in, S, c0, ncolp,
+                       status, r);
     NH_CHECK_HIP(hipGetLastError());
   }
   return NH_OK;

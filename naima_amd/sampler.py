@@ -22,6 +22,7 @@ from .dist import LocalComm, shard_bounds, shard_counts
 from .evidence import EvidenceMixin
 from .infocrit import InfoCritMixin
 from .predictive import PredictiveMixin
+from .reweight import ReweightMixin
 
 __all__ = ["EnsembleSampler", "State", "get_sampler", "run_sampler"]
 
@@ -50,7 +51,7 @@ def _split_blob(b):
     return np.asarray(b, dtype=float), None
 
 
-class EnsembleSampler(InfoCritMixin, PredictiveMixin, EvidenceMixin):
+class EnsembleSampler(InfoCritMixin, PredictiveMixin, EvidenceMixin, ReweightMixin):
     """Stretch-move ensemble sampler over a *batched* log-probability.
 
     log_prob_fn(coords[n, ndim], *args) -> lnp[n]  or  (lnp[n], blob0[n,...], ...)
