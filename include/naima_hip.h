@@ -1229,6 +1229,64 @@ int nh_resample_systematic(nh_ctx* ctx, const double* lw, long long ldw, long lo
 int nh_gather_rows(nh_ctx* ctx, const double* x, long long ld, const long long* idx,
                    long long n_out, int ncol, double* out, long long ldo);
 
+/* ---- S Nelder-Mead searches in lock-step (nh_simplex.hip; naima_amd/optimize.py) -------------
+ * The bookkeeping of S independent simplexes in HBM; the function evaluation between the calls
+ * is the caller's.  Simplex s minimises over its FREE coordinates -- those d with
+ * frozen[s * ndim + d] == 0, n_free(s) of them, 1 <= n_free(s) <= nmax <= ndim -- with the others
+ * pinned at value[s * ndim + d] (frozen == value == NULL: every coordinate is free), and follows
+ * naima's prefit algorithm (relative xtol / ftol; rho = 1, chi = 2, psi = sigma = 1/2; initial
+ * simplex x 1.05, or 0.00025 where the coordinate is 0) on that reduced function decision for
+ * decision and bit for bit, with two rules fixed: a function value that is NaN counts as +inf,
+ * and the sort is stable (ties keep their order; the replaced point is last before the sort).
+ * `state` is device memory of nh_simplex_bytes(S, ndim, nmax) bytes (0: sizes out of range) that
+ * the caller owns; every call takes the same (S, ndim, nmax).  ndim <= NH_SIMPLEX_MAX_DIM, the
+ * step kernels' own limit, and S * (nmax + 1) * ndim < 2^31.  A parameter block qT[ndim][n] is
+ * n columns of ndim coordinates, column c at qT[d * n + c] (the layout of the step loop's qT).
+ * A FUNCTION COLUMN is a pointer f and a stride fstride >= 1: the value of column c is
+ * f[c * fstride], negated first where is_logp != 0 (f is a log-probability to MAXIMISE).
+ *   nh_simplex_init_points  x0 [S][ndim]; maxiter, maxfev < 0: 200 * n_free(s).  Writes the state
+ *       and the initial points qT[ndim][(nmax + 1) * S], point p of simplex s in column p * S + s
+ *       (p > n_free(s): the start itself).  A simplex with n_free outside [1, nmax] gets status 3
+ *       and is never touched again.
+ *   nh_simplex_adopt        takes those columns' values: sort, nfev = n_free + 1, nit = 1.
+ *   nh_simplex_propose      qT[ndim][4 * S]: reflection, expansion, outside and inside contraction
+ *       of simplex s in columns s, S + s, 2 S + s, 3 S + s; a finished simplex writes its best
+ *       point four times and its state is not touched again.
+ *   nh_simplex_update       takes those columns' values (qT as propose wrote it): accepts one of
+ *       the four and re-sorts, or flags the simplex for a shrink; nfev counts what the sequential
+ *       algorithm would have evaluated; then the stopping rules: status 0 converged, 1 maxfev,
+ *       2 maxiter, -1 still active.
+ *   nh_simplex_counts       (host int [2]) = { simplexes still active, simplexes flagged for a
+ *       shrink } as the last adopt / update / shrink_adopt left them: an 8-byte download.  Both
+ *       come from a scan in index order, not from atomics.
+ *   nh_simplex_shrink_points  for the nshrink = counts[1] flagged simplexes, k-th in index order:
+ *       moves the points of rank j >= 1 half way to the best and writes them to
+ *       qT[ndim][nmax * nshrink], column (j - 1) * nshrink + k (j > n_free: the best point).
+ *   nh_simplex_shrink_adopt   takes those columns' values, nfev += n_free, sorts, clears the flag
+ *       and applies the stopping rules.
+ *   nh_simplex_result       x [S][ndim] the best point, fun [S] its value (of the MINIMISED
+ *       function), ints (int32 [4][S]) = nfev, nit, status, n_free.
+ * Every launch is on the context's stream; only nh_simplex_counts synchronises. */
+#define NH_SIMPLEX_MAX_DIM 64
+long long nh_simplex_bytes(int S, int ndim, int nmax);
+int nh_simplex_init_points(nh_ctx* ctx, void* state, int S, int ndim, int nmax, const double* x0,
+                           const int* frozen, const double* value, int maxiter, int maxfev,
+                           double* qT);
+int nh_simplex_adopt(nh_ctx* ctx, void* state, int S, int ndim, int nmax, const double* f,
+                     long long fstride, int is_logp, double xtol, double ftol);
+int nh_simplex_propose(nh_ctx* ctx, void* state, int S, int ndim, int nmax, double* qT);
+int nh_simplex_update(nh_ctx* ctx, void* state, int S, int ndim, int nmax, const double* qT,
+                      const double* f, long long fstride, int is_logp, double xtol, double ftol);
+int nh_simplex_counts(nh_ctx* ctx, const void* state, int S, int ndim, int nmax,
+                      int* counts /*host*/);
+int nh_simplex_shrink_points(nh_ctx* ctx, void* state, int S, int ndim, int nmax, int nshrink,
+                             double* qT);
+int nh_simplex_shrink_adopt(nh_ctx* ctx, void* state, int S, int ndim, int nmax, int nshrink,
+                            const double* f, long long fstride, int is_logp, double xtol,
+                            double ftol);
+int nh_simplex_result(nh_ctx* ctx, const void* state, int S, int ndim, int nmax, double* x,
+                      double* fun, int* ints);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,13 +19,14 @@ from .radiative import (Bremsstrahlung, InverseCompton, PionDecay,  # noqa: F401
 from .analysis import (find_ML, read_run, save_diagnostic_plots,  # noqa: F401
                        save_results_table, save_run)
 from .plot import (plot_blob, plot_chain, plot_corner, plot_data, plot_fit,  # noqa: F401
-                   plot_ppc)
+                   plot_ppc, plot_profile)
 from . import autocorr  # noqa: F401
 from . import posterior  # noqa: F401
 from . import infocrit  # noqa: F401
 from . import predictive  # noqa: F401
 from . import evidence  # noqa: F401
 from . import reweight  # noqa: F401
+from . import optimize  # noqa: F401
 from .datatable import validate_data_table  # noqa: F401
 
 __version__ = "0.1.0"

@@ -23,6 +23,7 @@ NH_RANK_POOLED, NH_RANK_CHAIN = 0, 1   # nh_rank_normal_scores' layouts
 NH_RANK_FOLD, NH_RANK_LE = 0, 1        # nh_rank_transform's modes
 NH_PSIS_MAX_TAIL = 4096  # nh_psis_columns' cap on the tail length (include/naima_hip.h)
 NH_EVID_MAX_DIM = 32     # nh_chain_cov's, nh_mvn_*'s cap on the dimension (include/naima_hip.h)
+NH_SIMPLEX_MAX_DIM = 64  # nh_simplex_*'s cap on ndim, the step kernels' own (include/naima_hip.h)
 NH_K_NAMES = ("particle_weights", "integrate_tables", "synchrotron", "tables", "lnprob",
               "ic_seed_walkers", "glue", "integrate_rows", "half_step")
 PD_KIND = {"PowerLaw": 0, "ExponentialCutoffPowerLaw": 1, "BrokenPowerLaw": 2,
@@ -198,8 +199,16 @@ _SIGS = {
     "nh_weighted_select": [_dp, _dp, _ll, _i, _ll, _dp, _ll, C.POINTER(_d), _i, _dp],
     "nh_resample_systematic": [_dp, _dp, _ll, _ll, _d, _ll, _dp],
     "nh_gather_rows": [_dp, _dp, _ll, _dp, _ll, _i, _dp, _ll],
+    "nh_simplex_init_points": [_dp, _dp, _i, _i, _i, _dp, _dp, _dp, _i, _i, _dp],
+    "nh_simplex_adopt": [_dp, _dp, _i, _i, _i, _dp, _ll, _i, _d, _d],
+    "nh_simplex_propose": [_dp, _dp, _i, _i, _i, _dp],
+    "nh_simplex_update": [_dp, _dp, _i, _i, _i, _dp, _dp, _ll, _i, _d, _d],
+    "nh_simplex_counts": [_dp, _dp, _i, _i, _i, C.POINTER(_i)],
+    "nh_simplex_shrink_points": [_dp, _dp, _i, _i, _i, _i, _dp],
+    "nh_simplex_shrink_adopt": [_dp, _dp, _i, _i, _i, _i, _dp, _ll, _i, _d, _d],
+    "nh_simplex_result": [_dp, _dp, _i, _i, _i, _dp, _dp, _dp],
 }
-EXPORTS = tuple(_SIGS) + ("nh_last_error", "nh_version", "nh_ssc_table_bytes")
+EXPORTS = tuple(_SIGS) + ("nh_last_error", "nh_version", "nh_ssc_table_bytes", "nh_simplex_bytes")
 
 _lib = None
 
@@ -268,6 +277,8 @@ def load():
     lib.nh_version.restype = _i
     lib.nh_ssc_table_bytes.restype = _ll
     lib.nh_ssc_table_bytes.argtypes = [_i, _i, _i]
+    lib.nh_simplex_bytes.restype = _ll
+    lib.nh_simplex_bytes.argtypes = [_i, _i, _i]
     _lib = lib
     return lib
 

@@ -268,10 +268,16 @@ def read_run(filename, modelfn=None):
     return res
 
 
-def find_ML(sampler):
+def find_ML(sampler, refine=False):
     """(max log-probability, its parameter vector): the most probable sample of the chain
     (the first return values of analysis-time ``find_ML`` in the reference, which
-    ``save_results_table`` stores as ``MaxLogLikelihood`` / ``ML_pars``; no refit)"""
+    ``save_results_table`` stores as ``MaxLogLikelihood`` / ``ML_pars``; no refit).
+    ``refine=True``: the refitted point instead -- ``sampler.fit_ml(prior=True)``, simplex
+    searches from the most probable samples under the sampler's own log-probability (on the
+    GPU, ``naima_amd.optimize``), which is never worse than the best sample it starts from."""
+    if refine:
+        ml = sampler.fit_ml(prior=True)
+        return float(ml.fun), ml.x
     lp = np.asarray(sampler.get_log_prob())
     chain = np.asarray(sampler.get_chain())
     idx = np.unravel_index(np.argmax(lp), lp.shape)
@@ -344,7 +350,7 @@ def save_diagnostic_plots(outname, sampler, modelidxs=None, pdf=False, sed=True,
 
 def save_results_table(outname, sampler, convert_log=True, last_step=False, include_blobs=True,
                        overwrite=False, information_criteria=False, diagnostics=False,
-                       goodness_of_fit=False, evidence=None):
+                       goodness_of_fit=False, evidence=None, profile=False):
     """Write ``<outname>_results.ecsv``: median and 16th/84th-percentile distances of every
     parameter (plus the de-logged value for ``log10(x)`` / ``log(x)`` labels and every
     scalar blob), with the run information, the most probable parameters and the BIC as
@@ -360,7 +366,11 @@ def save_results_table(outname, sampler, convert_log=True, last_step=False, incl
     and ``logZ_forbidden_fraction``: a result of ``naima_amd.evidence.bridge_sampling``, or True
     for ``sampler.log_evidence()`` with its defaults (a sampler only: a read run has no
     log-probability function; and mind that module's docstring on proper priors and
-    ``log_prior_norm``).  Returns the table as a dict of columns + ``meta``."""
+    ``log_prior_norm``).  ``profile=True`` adds the maximum-likelihood refit ``ML_refit`` and
+    ``ML_refit_pars`` (``sampler.fit_ml()``, flat prior) and the Delta lnL = 1/2 profile-likelihood
+    interval of every parameter, ``<label>_profile_lo`` / ``_hi`` (``sampler.profile_likelihood``;
+    null where the grid does not bracket it).  Returns the table as a dict of columns +
+    ``meta``."""
     import os
 
     import yaml
@@ -421,6 +431,15 @@ def save_results_table(outname, sampler, convert_log=True, last_step=False, incl
             meta["logZ_forbidden_fraction"] = float(evidence["forbidden_fraction"])
         except (TypeError, KeyError, IndexError):
             raise ValueError("evidence must be True or a result of evidence.bridge_sampling")
+    if profile:
+        if not hasattr(sampler, "profile_likelihood"):
+            raise ValueError("profile=True needs a sampler with a log-probability function")
+        ml = sampler.fit_ml()
+        meta["ML_refit"], meta["ML_refit_pars"] = float(ml.fun), [float(x) for x in ml.x]
+        for label, pr in zip(labels, sampler.profile_likelihood(list(range(len(labels))), ml=ml)):
+            lo, hi = pr.interval(0.683)
+            meta[label + "_profile_lo"] = None if np.isnan(lo) else float(lo)
+            meta[label + "_profile_hi"] = None if np.isnan(hi) else float(hi)
     for k, v in dict(getattr(sampler, "run_info", {})).items():
         meta[k] = v.tolist() if isinstance(v, np.ndarray) else (v.item() if isinstance(
             v, np.generic) else v)

@@ -734,6 +734,36 @@ def plot_ppc(sampler, modelidx=0, confs=(0.68, 0.95), seed=0, sed=True, figure=N
     return f
 
 
+def plot_profile(result, figure=None):
+    """A profile likelihood (``optimize.ProfileResult``, or a list of them, one panel each):
+    2 Delta lnL against the parameter, with the 1 sigma and 2 sigma lines at 1 and 4 and the
+    68.3 % interval shaded where the grid brackets it."""
+    import warnings
+
+    import matplotlib.pyplot as plt
+    results = list(result) if isinstance(result, (list, tuple)) else [result]
+    if not results or not all(hasattr(r, "delta_chi2") for r in results):
+        raise ValueError("plot_profile takes a ProfileResult or a list of them")
+    f = plt.figure() if figure is None else figure
+    for k, r in enumerate(results):
+        ax = f.add_subplot(1, len(results), k + 1)
+        ax.plot(r.grid, r.delta_chi2, marker="o", ms=3, lw=1, color=color_cycle[0])
+        for level, ls in ((1.0, "--"), (4.0, ":")):
+            ax.axhline(level, color="k", lw=1, ls=ls)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            lo, hi = r.interval(0.683)
+        if np.isfinite(lo) and np.isfinite(hi):
+            ax.axvspan(lo, hi, color=color_cycle[0], alpha=0.15, lw=0)
+        ax.axvline(r.ml.x[r.par], color=color_cycle[3], lw=1)
+        ax.set_xlabel(r.label)
+        finite = r.delta_chi2[np.isfinite(r.delta_chi2)]
+        ax.set_ylim(0.0, max(6.0, min(float(finite.max()) if finite.size else 6.0, 25.0)))
+        if k == 0:
+            ax.set_ylabel(r"$2\,\Delta\ln\mathcal{L}$")
+    return f
+
+
 def plot_corner(sampler, show_ML=True, **kwargs):
     """Corner plot of the chain (plot.py:1393-1439): through ``corner.corner`` when the corner
     package is installed; else, after a warning, the built-in figure ``posterior.corner`` draws

@@ -21,6 +21,7 @@ from . import units as u
 from .dist import LocalComm, shard_bounds, shard_counts
 from .evidence import EvidenceMixin
 from .infocrit import InfoCritMixin
+from .optimize import OptimizeMixin
 from .predictive import PredictiveMixin
 from .reweight import ReweightMixin
 
@@ -51,7 +52,8 @@ def _split_blob(b):
     return np.asarray(b, dtype=float), None
 
 
-class EnsembleSampler(InfoCritMixin, PredictiveMixin, EvidenceMixin, ReweightMixin):
+class EnsembleSampler(InfoCritMixin, PredictiveMixin, EvidenceMixin, ReweightMixin,
+                      OptimizeMixin):
     """Stretch-move ensemble sampler over a *batched* log-probability.
 
     log_prob_fn(coords[n, ndim], *args) -> lnp[n]  or  (lnp[n], blob0[n,...], ...)
