@@ -899,6 +899,38 @@ int nh_ebl_apply(nh_ctx* ctx, const double* tab, int ldt, int nrows, const doubl
                  const nh_lazy* z /*host*/, const nh_comp* comps /*host*/, int ncomp,
                  const double* colfac, int N, int m, double* out, int ldo);
 
+/* ---- gamma-gamma pair-production absorption on photon fields, per walker ---------------------
+ * (new: the reference has none.)  Breit-Wheeler cross section on the seed-photon-field grammar of
+ * InverseCompton; tau(E) = sum over fields of L_f * a_f * kappa_f(E).  FP64, deterministic, no
+ * atomics, no scratch.
+ * nh_pairabs_rows: out[r*ldo+k] = kappa of ONE field at x[k] = E_k / (m_e c^2) (DEVICE), one
+ *   wave per (row, energy), a fixed composite Gauss-Legendre rule in t, s = cosh^2 t:
+ *   NH_PAIR_THERMAL  per dilution factor w = u / (a T^4), 1/cm: T_K (and theta, rad; NULL =
+ *                    isotropic) are lazy values evaluated at the ROW index, so nrows = 1 with
+ *                    constants is the row all walkers share and nrows = N one row per walker;
+ *                    k_to_mec2 = k_B / (m_e c^2) per kelvin.  T <= 0, NaN or inf: a NaN row.
+ *   NH_PAIR_MONO     per photon, cm^2: seed_E_eV[1] (DEVICE), sbar(E E0 / m^2)
+ *   NH_PAIR_TABLE    the opacity itself, 1/cm: trapz_loglog over the ns >= 2 nodes seed_E_eV[ns]
+ *                    (eV), seed_dens[ns] (1/(eV cm3)) (DEVICE) of dens_i * sbar(E E_i / m^2)
+ *   With theta the field comes from one direction: (1 - cos theta) sigma(E eps (1 - cos theta) /
+ *   (2 m^2)) replaces sbar; theta = 0 gives 0 and -theta the bits of theta.
+ * nh_pairabs_apply: out[w*ldo+k] = exp(-tau_w[k]) * colfac[k] * sum_j comps[j] (ncomp 0..8; no
+ *   terms: the transmission itself; write_tau: tau itself, which takes no terms and no colfac),
+ *   tau_w[k] = sum_f L_f(w) a_f(w) kappa_f[w*ld_f + k] added in the order given (ld_f = 0: the
+ *   shared row).  a_f = dens (photons/cm3, or 1), or for a thermal field dens / (a_rad T_K^4) with
+ *   dens in erg/cm3.  A walker with L or dens negative, NaN or +-inf, or a thermal field's T <= 0,
+ *   NaN or inf, gets a NaN row; L = 0 or dens = 0 gives exactly 1. */
+enum { NH_PAIR_THERMAL = 0, NH_PAIR_MONO = 1, NH_PAIR_TABLE = 2 };
+typedef struct { const double* kappa; long long ld; nh_lazy L_cm; nh_lazy dens; nh_lazy T_K;
+                 int thermal; int pad; } nh_pair_field;
+int nh_pairabs_rows(nh_ctx* ctx, int kind, double k_to_mec2, const nh_lazy* T_K /*host*/,
+                    const nh_lazy* theta /*host or NULL*/, const double* seed_E_eV,
+                    const double* seed_dens, int ns, const double* x, int nE, int nrows,
+                    double* out, int ldo);
+int nh_pairabs_apply(nh_ctx* ctx, const nh_pair_field* fields /*host*/, int nfields /* <= 8 */,
+                     const nh_comp* comps /*host*/, int ncomp, const double* colfac, int write_tau,
+                     int N, int m, double* out, int ldo);
+
 /* ---- thinning a chain history on the device (emcee's thin_by) -------------------------------
  * For every segment (row-major DEVICE matrices of doubles, `width` columns each):
  *   dst row (dst_row0 + k) := src row (first + k*stride),  k < nrows.

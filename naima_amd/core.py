@@ -11,7 +11,7 @@ import numpy as np
 
 from . import units as u
 from ._lib import get_context
-from .darray import DMat, DPars, DVec, LazyPrior
+from .darray import DMat, DPars, DVec, LazyPrior, lift_factor
 
 __all__ = ["normal_prior", "uniform_prior", "log_uniform_prior", "lnprob", "lnprobmodel",
            "get_sampler", "run_sampler"]
@@ -248,7 +248,8 @@ def _lnprob_device(pars, data, modelfunc, priorfunc):
             lp = LazyPrior(pars.ctx, pars.n, [], float(lp))
     modelout = modelfunc(pars, data)
     if isinstance(modelout, (tuple, list)):
-        model, blob = modelout[0], tuple(modelout)
+        # (a scalar absorber's factor among the blobs: its device form, one row per walker)
+        model, blob = modelout[0], tuple(lift_factor(b, pars.n) for b in modelout)
     else:
         model, blob = modelout, (modelout, np.nan)  # core.py:108-110
     if not isinstance(model.value, DMat):

@@ -33,6 +33,12 @@ class nh_comp(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("ld", C.c_longlong), ("scale", C.c_double)]
 
 
+class nh_pair_field(C.Structure):
+    """include/naima_hip.h: one photon field of nh_pairabs_apply"""
+    _fields_ = [("kappa", C.c_void_p), ("ld", C.c_longlong), ("L_cm", nh_lazy), ("dens", nh_lazy),
+                ("T_K", nh_lazy), ("thermal", C.c_int), ("pad", C.c_int)]
+
+
 class nh_grid(C.Structure):
     _fields_ = [("e_eV", C.c_void_p), ("xg", C.c_void_p), ("w", C.c_void_p), ("dlw", C.c_void_p),
                 ("unit_scale", C.c_double), ("nG", C.c_int), ("pad", C.c_int),
@@ -208,14 +214,14 @@ class DVec:
         return DVec(self.ctx, out, out.ptr, self.n)
 
     def __mul__(self, o):
-        if _defer(o) or isinstance(o, (DMat, DEbl)):  # (a matrix takes the per-walker factor)
+        if _defer(o) or isinstance(o, (DMat, DFactor)):  # (a matrix takes the per-walker factor)
             return NotImplemented
         return self._scale(float(o)) if _is_number(o) else self._binary("mul", o)
 
     __rmul__ = __mul__
 
     def __truediv__(self, o):
-        if _defer(o) or isinstance(o, (DMat, DEbl)):
+        if _defer(o) or isinstance(o, (DMat, DFactor)):
             return NotImplemented
         return self._scale(1.0 / float(o)) if _is_number(o) else self._binary("div", o)
 
@@ -365,7 +371,8 @@ class DMat:
             return NotImplemented
         if _is_number(o):
             return self._scaled(float(o))
-        if isinstance(o, DEbl):  # per-walker, per-energy factor (EBL absorption at a free z)
+        o = lift_factor(o, self.shape[0])  # (an absorption with nothing free: N equal rows)
+        if isinstance(o, DFactor):  # per-walker, per-energy factor (absorption at a free z, L ...)
             return o.apply(self)
         if isinstance(o, DVec):  # per-walker factor (a target density that is a fit parameter)
             if o.n != self.shape[0]:
@@ -386,7 +393,7 @@ class DMat:
             return self._scaled(1.0 / float(o))
         if isinstance(o, DVec):  # per-walker divisor: the reciprocal stays lazy, a row factor
             return self.__mul__(1.0 / o)
-        if isinstance(o, (DMat, DEbl)):
+        if isinstance(o, (DMat, DFactor)):
             return NotImplemented
         return self.__mul__(1.0 / np.asarray(o, dtype=float))
 
@@ -459,18 +466,39 @@ class DMat:
         return self.get()[k]
 
 
-class DEbl:
-    """lazy (N, nE) EBL factor: row row(z_w) of a walker-independent table Tab[400][nE]
-    (nh_ebl_table, cached per set of energies) for a lazy per-walker redshift z.  Times a
-    ``DMat`` it is one ``nh_ebl_apply`` launch that also forms the matrix's linear combination;
-    ``.get()`` gathers the rows themselves."""
+class FactorRow(np.ndarray):
+    """the (n_e,) factor of an absorption model whose values are all scalars: a host array that
+    remembers its device form.  ``device(N)`` is the ``DFactor`` of N equal rows, which a ``DMat``
+    multiplies with and the device loop keeps as a blob, so that a model function with nothing
+    free in its absorber stays on the device.  Arrays derived from it are plain numbers."""
+    _make = None
+
+    def __new__(cls, values, make):
+        a = np.asarray(values, dtype=float).view(cls)
+        a._make = make
+        return a
+
+    def __array_finalize__(self, obj):
+        self._make = None
+
+    def device(self, N):
+        return self._make(int(N)) if self._make is not None else None
+
+
+def lift_factor(b, n):
+    """a ``FactorRow`` as its device factor over n walkers; anything else as it is"""
+    if isinstance(b, FactorRow) and b._make is not None:
+        return b.device(n)
+    return b
+
+
+class DFactor:
+    """a lazy (N, nE) per-walker, per-energy factor of a device flux (an absorption): a subclass
+    gives ``apply(m)`` -- the ``DMat`` of factor * m, or of the factor itself without m, in one
+    launch that also forms m's linear combination -- and ``shape``"""
     __array_priority__ = 30000
     __array_ufunc__ = None
     ndim = 2
-
-    def __init__(self, ctx, tab, zl, z, nE):
-        self.ctx, self.tab, self.zl, self.z = ctx, tab, zl, z
-        self.shape = (z.n, int(nE))
 
     @property
     def size(self):
@@ -479,22 +507,16 @@ class DEbl:
     def __len__(self):
         return self.shape[0]
 
-    def apply(self, m=None):
-        """DMat of Tab[row(z_w)][k] * (m[w][k], or 1 without m): one nh_ebl_apply launch"""
-        N, nE = self.shape
-        comps, ncomp, cf = None, 0, None
-        if m is not None:
-            if m.shape != self.shape:
-                raise ValueError("EBL factor of shape %r times a device matrix of shape %r"
-                                 % (self.shape, m.shape))
-            self.ctx.flush(*[t[0] for t in m.terms])
-            comps, ncomp = m.comps(), len(m.terms)
-            cf = self.ctx.const(m.colfac) if m.colfac is not None else None
-        out = self.ctx.empty((N, nE))
-        lz = self.z.lazy()
-        self.ctx.call("nh_ebl_apply", self.tab, nE, self.zl.shape[0] + 1, self.zl,
-                      self.zl.shape[0], C.byref(lz), comps, ncomp, cf, N, nE, out, nE)
-        return DMat.from_buffer(self.ctx, out, N, nE)
+    def _terms_of(self, m):
+        """(comps, ncomp, colfac) of the matrix to multiply; its held-back launches flushed"""
+        if m is None:
+            return None, 0, None
+        if m.shape != self.shape:
+            raise ValueError("%s factor of shape %r times a device matrix of shape %r"
+                             % (self._what, self.shape, m.shape))
+        self.ctx.flush(*[t[0] for t in m.terms])
+        cf = self.ctx.const(m.colfac) if m.colfac is not None else None
+        return m.comps(), len(m.terms), cf
 
     def __mul__(self, o):
         if _defer(o):
@@ -513,6 +535,64 @@ class DEbl:
 
     def __getitem__(self, k):
         return self.get()[k]
+
+
+class DEbl(DFactor):
+    """lazy (N, nE) EBL factor: row row(z_w) of a walker-independent table Tab[400][nE]
+    (nh_ebl_table, cached per set of energies) for a lazy per-walker redshift z.  Times a
+    ``DMat`` it is one ``nh_ebl_apply`` launch that also forms the matrix's linear combination;
+    ``.get()`` gathers the rows themselves."""
+    _what = "EBL"
+
+    def __init__(self, ctx, tab, zl, z, nE):
+        self.ctx, self.tab, self.zl, self.z = ctx, tab, zl, z
+        self.shape = (z.n, int(nE))
+
+    def apply(self, m=None):
+        """DMat of Tab[row(z_w)][k] * (m[w][k], or 1 without m): one nh_ebl_apply launch"""
+        N, nE = self.shape
+        comps, ncomp, cf = self._terms_of(m)
+        out = self.ctx.empty((N, nE))
+        lz = self.z.lazy()
+        self.ctx.call("nh_ebl_apply", self.tab, nE, self.zl.shape[0] + 1, self.zl,
+                      self.zl.shape[0], C.byref(lz), comps, ncomp, cf, N, nE, out, nE)
+        return DMat.from_buffer(self.ctx, out, N, nE)
+
+
+class DPairAbs(DFactor):
+    """lazy (N, nE) pair-production transmission exp(-tau) (or, with ``tau``, the opacity
+    itself): tau_w[k] = sum_f L_f(w) a_f(w) kappa_f[row_f(w)][k] over at most 8 photon fields.
+    ``fields`` is a list of (kappa, per_walker, L_cm, dens, T_K or None): kappa the DeviceArray
+    of nh_pairabs_rows -- one shared row, or with ``per_walker`` one row per walker --, the
+    others a number or a ``DVec``.  Times a ``DMat`` it is one ``nh_pairabs_apply`` launch that
+    also forms the matrix's linear combination."""
+    _what = "pair-absorption"
+
+    def __init__(self, ctx, fields, N, nE, tau=False):
+        if len(fields) > 8:
+            raise ValueError("at most 8 photon fields in one absorption factor, got %d"
+                             % len(fields))
+        self.ctx, self.fields, self.tau = ctx, list(fields), bool(tau)
+        self.shape = (int(N), int(nE))
+
+    @staticmethod
+    def _lazy(v):
+        return v.lazy() if isinstance(v, DVec) else lazy_const(v)
+
+    def apply(self, m=None):
+        N, nE = self.shape
+        if self.tau and m is not None:
+            raise TypeError("an opacity is not a factor of a flux: multiply with the transmission")
+        comps, ncomp, cf = self._terms_of(m)
+        arr = (nh_pair_field * max(len(self.fields), 1))()
+        for j, (kappa, per_walker, L, dens, T) in enumerate(self.fields):
+            arr[j] = nh_pair_field(kappa.ptr, nE if per_walker else 0, self._lazy(L),
+                                   self._lazy(dens), self._lazy(T if T is not None else 0.0),
+                                   int(T is not None), 0)
+        out = self.ctx.empty((N, nE))
+        self.ctx.call("nh_pairabs_apply", arr, len(self.fields), comps, ncomp, cf,
+                      int(self.tau), N, nE, out, nE)
+        return DMat.from_buffer(self.ctx, out, N, nE)
 
 
 class LazyPrior:
@@ -574,4 +654,4 @@ class LazyPrior:
 
 
 def is_device(x):
-    return isinstance(x, (DVec, DMat, DPars, LazyPrior, DEbl))
+    return isinstance(x, (DVec, DMat, DPars, LazyPrior, DFactor))

@@ -28,7 +28,7 @@ import numpy as np
 from . import _lib, loop_books, shared_merge
 from .step_plan import AcceptHook, Front, StepPlan
 from . import units as u
-from .darray import DEbl, DMat, DPars, DVec
+from .darray import DFactor, DMat, DPars, DVec, lift_factor
 from .dist import shard_bounds, shard_counts
 from .loop_books import Books, EnsembleCopy, JournalEntry, KeptBlob, LaunchQueue
 from .move_ring import MoveRing
@@ -282,7 +282,7 @@ class DeviceLoop:
         self.s.n_walker_evals += n
         rows = bool(self._hook and self._hook.rows_active) and self.ctx._accept_hook is self._hook
         total = res[0] if rows else res[0].dense()  # (rows: exchanged as they are)
-        blobs = list(res[1:])
+        blobs = [lift_factor(b, n) for b in res[1:]]
         # plain numbers among the blobs (lnprob's (model, nan) for a model that returns no
         # blob of its own, core.py:108-110) are the same for every walker and every step:
         # they are not kept in HBM but put back where they belong when the blobs are read
@@ -295,7 +295,7 @@ class DeviceLoop:
         unit = None
         if isinstance(b, u.Quantity):
             b, unit = b.value, b.unit
-        if isinstance(b, DEbl):  # (a transmission blob: its rows gathered, one launch)
+        if isinstance(b, DFactor):  # (a transmission blob: its rows gathered, one launch)
             b = b.apply()
         if isinstance(b, DMat):
             own, ptr = b.buffer()

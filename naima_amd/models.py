@@ -11,6 +11,7 @@ import numpy as np
 
 from . import units as u
 from ._lib import NH_PD_NPAR, PD_KIND, get_context
+from .constants import AR_CGS, C_CGS, HBAR_CGS, MEC2_ERG, MEC2_EV
 from .validator import validate_physical_type, validate_scalar_or_batch
 
 __all__ = ["PowerLaw", "ExponentialCutoffPowerLaw", "BrokenPowerLaw",
@@ -486,3 +487,266 @@ class EblAbsorptionModel(TableModel):
             else:
                 taus[i] = np.log10(float(np.asarray(self(ev[i] * u.eV).value)))
         return np.exp(-taus)
+
+
+# k_B / (m_e c^2) per kelvin, from the radiation constant a = pi^2 k_B^4 / (15 (hbar c)^3)
+_K_TO_MEC2 = (15.0 * AR_CGS * (HBAR_CGS * C_CGS) ** 3 / np.pi ** 2) ** 0.25 / MEC2_ERG
+
+
+def _pa_value(ctx, q, unit):
+    """the value of a Quantity in ``unit``: a float, or a DVec.  A 1-D host array is uploaded
+    as it was given and converted as a device value is, lazily, so that a host batch and the
+    same numbers held on the device give the same bits."""
+    from .darray import DVec
+    v = q.value
+    if not isinstance(v, DVec):
+        v = np.asarray(v, dtype=float)
+        if v.ndim > 1 or (v.ndim == 1 and v.size == 0):
+            raise TypeError("a per-walker value must be a non-empty 1-D array, got shape %r"
+                            % (v.shape,))
+        if v.size == 1:  # (a scalar, or a batch of one walker)
+            return float(np.ravel(q.to(unit).value)[0])
+        d = ctx.array(v)
+        v = DVec(ctx, d, d.ptr, v.shape[0])
+    return u.Quantity(v, q.unit).to(unit).value
+
+
+_pa_rows = {}  # the (n_e,) rows of scalar models, by content (PairAbsorptionModel._result)
+
+
+class PairAbsorptionModel:
+    """Absorption of gamma rays by pair production (gamma gamma -> e+ e-, the Breit-Wheeler
+    cross section) on photon fields along the line of sight: inside the Galaxy on the CMB and
+    the dust fields above ~100 TeV, in a binary or a compact nebula on the source's own field.
+
+    ``seed_photon_fields`` follows the grammar of ``InverseCompton``: 'CMB' | 'FIR' | 'NIR' |
+    [name, T, u] | [name, T, u, theta] | [name, E, density] (monochromatic: energy density) |
+    [name, E[], density[]] (tabulated).  The three-element forms are isotropic; with ``theta``
+    the field comes from one direction and 1 - cos(theta) enters (theta = 0: no absorption).
+    ``path_length`` is one length, or a sequence with one length per field.
+
+    ``opacity(e)`` is tau(E) = sum over the fields of L * dtau/dl and ``transmission(e)`` is
+    exp(-tau), the factor to multiply a flux with (for scalars a ``darray.FactorRow``: an
+    ndarray that a device flux multiplies with, and the device loop keeps as a blob, as N equal
+    rows from nh_pairabs_apply).  T, u and theta of a thermal field, the
+    density of a monochromatic field and every path length may each be a scalar, a 1-D host
+    array (one value per walker) or a device parameter (``pars[4] * u.kpc`` in a model function
+    on the device loop); the results are then an (n_e,) ndarray, an (N, n_e) ndarray, or a lazy
+    device factor (``darray.DPairAbs``) that multiplies a device flux in one launch.  All three
+    come from the same kernels (nh_pairabs_rows / nh_pairabs_apply): the opacity per unit
+    length and density of a field whose shape every walker shares is built once per set of
+    energies and cached; a thermal field with a per-walker T or theta gets a row per walker at
+    every evaluation.  The energies of monochromatic and tabulated fields are the same for every
+    walker.
+
+    Scalars are validated as in the reference's models (``ValueError`` for a negative or
+    non-finite value, a temperature that is not positive).  A walker of a batch whose path
+    length, energy density or density is negative, NaN or infinite, or whose temperature is
+    <= 0, NaN or infinite, gets a NaN row: a prior that excludes it gives -inf, and without one
+    the sampler's ``nan_policy`` applies."""
+
+    def __init__(self, seed_photon_fields, path_length):
+        from .radiative import InverseCompton
+        from .validator import validate_physical_type, validate_scalar
+        self._check_seed_energies(seed_photon_fields)
+        self.seed_photon_fields = InverseCompton._process_input_seed(seed_photon_fields)
+        nf = len(self.seed_photon_fields)
+        if nf > 8:
+            raise ValueError("at most 8 photon fields, got %d" % nf)
+        if isinstance(path_length, (list, tuple)):
+            lengths = list(path_length)
+            if len(lengths) != nf:
+                raise ValueError("path_length has %d entries for %d photon fields"
+                                 % (len(lengths), nf))
+        else:
+            lengths = [path_length] * nf
+        for name, L in zip(self.seed_photon_fields, lengths):
+            validate_physical_type("{0}-path_length".format(name), L, "length")
+            if not (L.on_device or np.ndim(L.value) > 0):
+                validate_scalar("{0}-path_length".format(name), L, domain="positive",
+                                physical_type="length")
+        self.path_length = lengths
+        for name, seed in self.seed_photon_fields.items():
+            if seed["type"] == "thermal":
+                T = seed["T"]
+                if not (T.on_device or np.ndim(T.value) > 0) and not T.value > 0:
+                    raise ValueError("{0}-T value should be strictly positive".format(name))
+            elif seed["energy"].size == 1:
+                d = seed["photon_density"]
+                if not d.on_device and np.size(d.value) == 1:
+                    validate_scalar("{0}-density".format(name),
+                                    u.Quantity(float(np.ravel(d.value)[0]), d.unit),
+                                    domain="positive", physical_type="pressure")
+            elif seed["photon_density"].on_device or np.ndim(seed["photon_density"].value) != 1:
+                raise NotImplementedError(
+                    "%s-density must be the same for every walker of a batch (the tabulated "
+                    "field's opacity is shared); evaluate walkers with different %s-density in "
+                    "separate calls" % (name, name))
+
+    @staticmethod
+    def _check_seed_energies(seed_photon_fields):
+        """the energies of a monochromatic or tabulated field are walker-independent"""
+        if type(seed_photon_fields) is not list:
+            return
+        for s in seed_photon_fields:
+            if type(s) is list and len(s) in (3, 4) and isinstance(s[1], u.Quantity) \
+                    and s[1].unit.physical_type != "temperature" \
+                    and (s[1].on_device or np.ndim(s[1].value) > 1):
+                raise NotImplementedError(
+                    "%s-energy must be the same for every walker of a batch (the field's opacity "
+                    "is shared); evaluate walkers with different %s-energy in separate calls"
+                    % (s[0], s[0]))
+
+    # -- what is given per walker ----------------------------------------------------------
+    def _given(self):
+        """every Quantity that may be given per walker"""
+        qs = list(self.path_length)
+        for seed in self.seed_photon_fields.values():
+            if seed["type"] == "thermal":
+                qs += [seed["T"], seed["u"]]
+            elif seed["energy"].size == 1:
+                qs.append(seed["photon_density"])
+            if not seed["isotropic"]:
+                qs.append(seed["theta"])
+        return qs
+
+    @property
+    def on_device(self):
+        return any(q.on_device for q in self._given())
+
+    @property
+    def batch_size(self):
+        """walkers of the batch (None: scalars everywhere)"""
+        n = None
+        for q in self._given():
+            k = np.shape(q.value)[0] if np.ndim(q.value) == 1 and np.size(q.value) > 1 else (
+                q.value.n if q.on_device else None)
+            if k is not None:
+                if n is not None and k != n:
+                    raise ValueError("inconsistent walker-batch sizes: %d vs %d" % (n, k))
+                n = k
+        return n
+
+    def _values(self, ctx):
+        """per field: (seed, L [cm], dens, T [K] or None, theta [rad] or None) as floats or
+        DVecs; dens is u [erg/cm3] of a thermal field, photons/cm3 of a monochromatic one and
+        1 for a tabulated one"""
+        out = []
+        for (name, seed), L in zip(self.seed_photon_fields.items(), self.path_length):
+            Lv = _pa_value(ctx, L, "cm")
+            th = None if seed["isotropic"] else _pa_value(ctx, seed["theta"], "rad")
+            if seed["type"] == "thermal":
+                out.append((seed, Lv, _pa_value(ctx, seed["u"], "erg/cm3"),
+                            _pa_value(ctx, seed["T"], "K"), th))
+            elif seed["energy"].size == 1:
+                d = seed["photon_density"]
+                if not d.on_device and np.size(d.value) == 1:
+                    d = u.Quantity(float(np.ravel(d.value)[0]), d.unit)
+                out.append((seed, Lv, _pa_value(ctx, d, "eV/cm3")
+                            / float(seed["energy"].to("eV").value[0]), None, th))
+            else:
+                out.append((seed, Lv, 1.0, None, th))
+        return out
+
+    # -- the kernels -------------------------------------------------------------------------
+    @staticmethod
+    def _rows_launch(ctx, direct, kind, T, theta, se, sn, ns, xd, nE, nrows, out):
+        """one nh_pairabs_rows launch: a cached table build is called directly and is never
+        recorded in a plan; per-walker rows go through ctx.call, so a step plan records them"""
+        import ctypes as C
+
+        from . import _lib
+        from .darray import DPairAbs
+        lT = DPairAbs._lazy(T if T is not None else 0.0)
+        lth = DPairAbs._lazy(theta) if theta is not None else None
+        args = (kind, _K_TO_MEC2, C.byref(lT), C.byref(lth) if lth is not None else None,
+                se.ptr if se is not None else None, sn.ptr if sn is not None else None, ns,
+                xd.ptr, nE, nrows, out.ptr, nE)
+        if direct:
+            _lib._chk(_lib._lib.nh_pairabs_rows(ctx.h, *args))
+        else:
+            ctx.call("nh_pairabs_rows", *args)
+
+    def _kappa(self, ctx, seed, T, theta, xd, nE, N):
+        """(kappa DeviceArray, per_walker) of one field at the energies xd"""
+        from ._lib import NH_PAIR_MONO, NH_PAIR_TABLE, NH_PAIR_THERMAL
+        from .darray import DVec
+        if seed["type"] == "thermal" and (isinstance(T, DVec) or isinstance(theta, DVec)):
+            out = ctx.empty((N, nE))
+            self._rows_launch(ctx, False, NH_PAIR_THERMAL, T, theta, None, None, 0, xd, nE, N, out)
+            return out, True
+        if isinstance(theta, DVec):
+            raise NotImplementedError(
+                "theta of a monochromatic or tabulated field must be the same for every walker "
+                "of a batch (the field's opacity is shared); evaluate walkers with different "
+                "theta in separate calls")
+        if seed["type"] == "thermal":
+            key = ("pairabs", "T", T, theta, xd.ptr)
+            build_args = (NH_PAIR_THERMAL, T, theta, None, None, 0)
+        else:
+            se = ctx.const(np.atleast_1d(seed["energy"].to("eV").value).astype(float))
+            mono = se.shape[0] == 1
+            sn = None if mono else ctx.const(
+                np.asarray(seed["photon_density"].to("1/(eV cm3)").value, dtype=float))
+            key = ("pairabs", "A", se.ptr, None if mono else sn.ptr, theta, xd.ptr)
+            build_args = (NH_PAIR_MONO if mono else NH_PAIR_TABLE, None, theta, se, sn,
+                          se.shape[0])
+
+        def build():
+            out = ctx.empty((1, nE))
+            self._rows_launch(ctx, True, *build_args, xd, nE, 1, out)
+            return out, xd, build_args  # (the entry keeps the arrays its key points at)
+
+        return ctx.table(key, build)[0], False
+
+    def _factor(self, e, tau, rows=None):
+        """(the DPairAbs at energies e, the batch size or None); ``rows``: that many equal rows
+        of a model whose values are all scalars"""
+        from .darray import DPairAbs
+        e = _validate_ene(e)
+        x = np.atleast_1d(e.to("eV").value).astype(float).ravel() / MEC2_EV
+        ctx = get_context()
+        xd = ctx.const(x)
+        N = self.batch_size
+        N1 = (rows or 1) if N is None else N
+        fields = []
+        for seed, L, dens, T, theta in self._values(ctx):
+            kappa, per_walker = self._kappa(ctx, seed, T, theta, xd, x.size, N1)
+            fields.append((kappa, per_walker, L, dens, T))
+        return DPairAbs(ctx, fields, N1, x.size, tau=tau), N
+
+    def _result(self, e, tau):
+        f, N = self._factor(e, tau)
+        if self.on_device:
+            return f
+        if N is not None:
+            return f.get()
+        # scalars everywhere: the row is remembered by what it depends on, so that a model
+        # function with nothing free in its absorber downloads nothing at its later evaluations
+        # (none is possible while a graph is captured)
+        x = np.atleast_1d(_validate_ene(e).to("eV").value).astype(float).ravel()
+        key = (id(f.ctx), tau, x.tobytes()) + tuple(
+            (seed["type"], L, dens, T, theta,
+             None if seed["type"] == "thermal" else (
+                 seed["energy"].to("eV").value.tobytes(),
+                 np.asarray(seed["photon_density"].value, dtype=float).tobytes(),
+                 str(seed["photon_density"].unit)))
+            for seed, L, dens, T, theta in self._values(f.ctx))
+        row = _pa_rows.get(key)
+        if row is None:
+            if len(_pa_rows) >= 64:
+                _pa_rows.clear()
+            row = _pa_rows[key] = f.get()[0]
+        if tau:
+            return row.copy()
+        from .darray import FactorRow
+        return FactorRow(row, lambda n: self._factor(e, False, rows=n)[0])
+
+    def opacity(self, e):
+        """tau(E): (n_e,) for scalars, (N, n_e) for a host batch, a lazy device factor
+        for device values"""
+        return self._result(e, True)
+
+    def transmission(self, e):
+        """exp(-tau(E)), the factor to multiply a flux with; shapes as for ``opacity``"""
+        return self._result(e, False)

@@ -113,14 +113,15 @@ def _split_model(blob, energy, modelidx):
 def _evaluate_device(ctx, sampler, pars, data, modelidx):
     """one model call on device parameters -> (modelx, unit, DeviceMatrix), or None when the model
     cannot take them (what EnsembleSampler._probe_device catches)"""
-    from .darray import DEbl, DMat, DPars
+    from .darray import DFactor, DMat, DPars, lift_factor
     n = len(pars)
     try:
         out = sampler.modelfn(DPars(ctx, ctx.array(np.ascontiguousarray(pars.T)), pars.shape[1], n),
                               data)
         modelx, q = _split_model(_pick(out, modelidx), data["energy"], modelidx)
-        if isinstance(q.value, DEbl):  # (a transmission blob)
-            q = q.__class__(q.value.apply(), q.unit)
+        v = lift_factor(q.value, n)
+        if isinstance(v, DFactor):  # (a transmission blob)
+            q = q.__class__(v.apply(), q.unit)
         if not isinstance(q.value, DMat):
             raise TypeError("a host array for device parameters")
         d = q.value.dense()

@@ -440,10 +440,10 @@ class EnsembleSampler(InfoCritMixin, PredictiveMixin, EvidenceMixin, ReweightMix
             res = self.log_prob_fn(DPars(ctx, ctx.array(c), self.ndim, c.shape[1]), *self.args)
             if self.store_blobs:
                 from . import units as u
-                from .darray import DEbl, DMat, DVec
+                from .darray import DFactor, DMat, DVec, lift_factor
                 for b in res[1:]:
-                    v = b.value if isinstance(b, u.Quantity) else b
-                    if not isinstance(v, (DMat, DVec, DEbl, float, int)):
+                    v = lift_factor(b.value if isinstance(b, u.Quantity) else b, c.shape[1])
+                    if not isinstance(v, (DMat, DVec, DFactor, float, int)):
                         why = "a blob of type %s cannot be kept in HBM" % type(v).__name__
         except NotImplementedError as e:  # grid-/table-shaping parameters per walker
             why = str(e)

@@ -422,6 +422,8 @@ class Quantity(_QuantityBase):
             return 1.0, other
         if getattr(other, "__array_priority__", 0) == 30000:
             return other, dimensionless_unscaled
+        if getattr(other, "_make", None) is not None:  # (darray.FactorRow: keeps its device form)
+            return other, dimensionless_unscaled
         return np.asarray(other, dtype=float), dimensionless_unscaled
 
     def __mul__(self, other):

@@ -5,7 +5,7 @@ import numpy as np
 
 from . import units as u
 from ._lib import get_context
-from .darray import DEbl, DMat, DVec
+from .darray import DFactor, DMat, DVec
 from .core import sed_conversion  # noqa: F401  (re-export, utils.py:219-282)
 from .datatable import (build_data_table, generate_energy_edges,  # noqa: F401
                         validate_data_table)
@@ -31,7 +31,7 @@ def trapz_loglog(y, x, axis=-1, intervals=False):
     x = np.asarray(x, dtype=float)
     if x.ndim != 1:
         raise ValueError("x must be one-dimensional")
-    if isinstance(y, (DMat, DEbl)):
+    if isinstance(y, (DMat, DFactor)):
         res = _trapz_loglog_device(y, x, axis, intervals)
         unit = y_unit * x_unit
         if unit.dims == u.dimensionless_unscaled.dims and unit.scale == 1.0:
@@ -69,7 +69,7 @@ def _trapz_loglog_device(m, x, axis, intervals):
     if axis not in (-1, 1):
         raise ValueError("a device matrix is integrated along its energy axis (axis=-1 or 1), "
                          "not axis=%r" % (axis,))
-    if isinstance(m, DEbl):  # a bare transmission factor: its rows gathered first
+    if isinstance(m, DFactor):  # a bare transmission factor: its rows gathered first
         m = m.apply()
     N, n = m.shape
     if n != x.size:
