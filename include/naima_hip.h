@@ -274,6 +274,22 @@ int nh_table_pion_lut(nh_ctx* ctx, const double* Ep_GeV, int nG, const double* E
 int nh_pion_kelner06(nh_ctx* ctx, int kind, const double* params, int N, const double* E_eV,
                      int nE, double Etrans_eV, int mixed, double* out, int ldo,
                      double* nhat_out, double* wp_TeV_out);
+/* SecondaryLeptonsKelner06._spectrum (no reference counterpart): the secondary electrons and
+ * neutrinos of the same collisions, pp -> pi+- -> mu nu -> e nu nu, KAB06 Eq. 62-69 at
+ * E >= Etrans_eV and the delta-functional approximation of its section IV below.
+ * out[w*ldo + k] = differential luminosity 1/(s eV) for nh = 1 cm^-3 at E_eV[k] of
+ * product 0: electrons (e+ + e-), 1: nu_e, 2: nu_mu (= electrons + the pion decay's muon
+ * neutrino), 3: all flavours; neutrinos and antineutrinos together, at the source.
+ * `match` (the host sets it when an energy lies below Etrans): each of the three components
+ * (e, nu_e, numu1) of the delta branch is scaled to meet its full calculation at Etrans
+ * (nu_e meets F_e); nhat_out[N][3], in that order, may be NULL (match = 0: all 1).
+ * params: the [N][8] particle rows of nh_particle_weights (eV).  Fixed Gauss-Legendre rule
+ * on nh_pion_kelner06's panels, within 1e-8 of the converged integrals.  EINVAL: a kind
+ * outside the enum, product outside 0..3, nE < 1, ldo < nE, Etrans_eV <= 0, 3 (nE + 2)
+ * doubles beyond 60 KiB of LDS.  N = 0 is no error. */
+int nh_pp_leptons_kelner06(nh_ctx* ctx, int kind, const double* params, int N,
+                           const double* E_eV, int nE, double Etrans_eV, int match, int product,
+                           double* out, int ldo, double* nhat_out);
 
 /* model[w][k] = sum_j cscale[j] * comp_j[w*ldc + k]        (1/(s cm2 eV))
  * m' = model*conv[k] (SED<->differential factor, utils.py:219-282)

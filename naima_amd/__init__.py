@@ -15,7 +15,7 @@ from .models import (BrokenPowerLaw, ExponentialCutoffBrokenPowerLaw,  # noqa: F
                      ExponentialCutoffPowerLaw, LogParabola, PowerLaw, TableModel,
                      EblAbsorptionModel, PairAbsorptionModel)
 from .radiative import (Bremsstrahlung, InverseCompton, PionDecay,  # noqa: F401
-                        PionDecayKelner06, Synchrotron)
+                        PionDecayKelner06, SecondaryLeptonsKelner06, Synchrotron)
 from .analysis import (find_ML, read_run, save_diagnostic_plots,  # noqa: F401
                        save_results_table, save_run)
 from .plot import (plot_blob, plot_chain, plot_corner, plot_data, plot_fit,  # noqa: F401

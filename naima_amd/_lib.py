@@ -99,6 +99,7 @@ _SIGS = {
     "nh_step_front": [_dp, _dp, _dp, _dp, _dp, _dp, _i, _i, _i, _i, _dp, _dp, _dp, _i, _i, _dp, _dp,
                       _i, _dp, _i, _dp],
     "nh_pion_kelner06": [_dp, _i, _dp, _i, _dp, _i, _d, _i, _dp, _i, _dp, _dp],
+    "nh_pp_leptons_kelner06": [_dp, _i, _dp, _i, _dp, _i, _d, _i, _i, _dp, _i, _dp],
     "nh_synchrotron_lnprob": [_dp, _dp, _dp, _dp, _i, _i, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i,
                               _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _i, _dp, _dp],
     "nh_integrate_tables_lnprob": [_dp, _dp, _dp, _i, _i, _dp, _dp, _dp, _i, _dp, _dp, _i, _i,

@@ -1480,3 +1480,98 @@ class PionDecayKelner06(BaseRadiative):
             return u.Quantity(DVec(ctx, wp, wp.ptr, N), u.TeV).to("erg")
         v = wp.get()
         return u.Quantity(v if self.is_batched else v[0], u.TeV).to("erg")
+
+    def secondaries(self, product="nu_mu"):
+        """The neutrinos or secondary electrons of the same proton population:
+        :class:`SecondaryLeptonsKelner06` on this distribution, ``nh`` and ``Etrans``"""
+        return SecondaryLeptonsKelner06(self.particle_distribution, nh=self.nh,
+                                        Etrans=self.Etrans, product=product)
+
+
+class SecondaryLeptonsKelner06(BaseRadiative):
+    """Neutrinos and secondary electrons of pp collisions, from the charged pions
+    (pp -> pi -> mu nu -> e nu nu), with the parametrisation of Kelner, Aharonian & Bugayov 2006
+    -- the companion of :class:`PionDecayKelner06`, which gives the gamma rays of the same
+    collisions.  The reference has no counterpart.
+
+    ``product`` chooses the spectrum, particles and antiparticles together, at the source:
+
+    ============  ================================================================
+    ``electron``  e+ + e- (KAB06 Eq. 62-65)
+    ``nu_e``      electron neutrinos (above ``Etrans`` the same spectrum: F_nue ~= F_e)
+    ``nu_mu``     muon neutrinos: those of the muon decay (the electrons' spectrum)
+                  plus those of the pion decay (Eq. 66-69)
+    ``nu_all``    all flavours: ``nu_mu + nu_e``
+    ============  ================================================================
+
+    After averaged oscillations over astrophysical distances the flux of each flavour at Earth
+    is about ``nu_all / 3``.
+
+    Above ``Etrans`` (default 0.1 TeV) the spectra are KAB06's full calculation, whose fits hold
+    for proton energies 0.1 TeV <= Ep <= 1e5 TeV and x = E / Ep >= 1e-3.  (Eq. 64 has no value
+    below Ep = 36 GeV, where the electron term is continued by zero.)  Below ``Etrans`` they are
+    the delta-functional approximation of KAB06 section IV: pions of energy K_pi (Ep - m_p) that
+    decay as relativistic particles.  It is restricted to pion energies above m_pi and, like
+    KAB06, neglects the masses on the lepton side, so below about 1 GeV it is a rough guide only.
+
+    Each of the three components (electrons, nu_e, the pion decay's nu_mu) of the delta branch is
+    scaled by its own ``nhat`` to meet the full calculation at ``Etrans`` (nu_e meets the
+    electrons' F_e).  Unlike :class:`PionDecayKelner06` this is done whenever an energy lies
+    below ``Etrans``, also when none lies above it, so a spectrum evaluated in pieces is the
+    spectrum evaluated at once and is always continuous at ``Etrans``.  After a host evaluation
+    ``nhat`` holds the factors in the order (electron, nu_e, nu_mu of the pion decay), shape
+    ``(3,)`` or ``(N, 3)``.
+
+    Every (walker, energy) is one wave of ``nh_pp_leptons_kelner06`` with the fixed rule of
+    ``nh_pion_kelner06``, within 1e-8 of the converged integrals.  ``nh`` may be per walker, and
+    the parameters may live on the device (a blob of a ``device=True`` fit)."""
+    param_names = ["nh", "Etrans", "product"]
+    _walker_scalars = ("nh",)
+    products = ("electron", "nu_e", "nu_mu", "nu_all")
+
+    def __init__(self, particle_distribution, nh=1.0 / u.cm ** 3, Etrans=0.1 * u.TeV,
+                 product="nu_mu", **kwargs):
+        self.particle_distribution = particle_distribution
+        if _per_walker(nh):
+            validate_physical_type("nh", nh, "number density")
+            self.nh = nh
+        else:
+            self.nh = validate_scalar("nh", nh, physical_type="number density")
+        self.Etrans = validate_scalar("Etrans", Etrans, domain="positive", physical_type="energy")
+        if product not in self.products:
+            raise ValueError("product must be one of %s (got %r)"
+                             % (", ".join(repr(p) for p in self.products), product))
+        self.product = product
+        self.__dict__.update(**kwargs)
+
+    def _own_batch_sizes(self):
+        return (_batch_of(self.nh),)
+
+    def _own_device_values(self):
+        return (self.nh,)
+
+    def _spectrum(self, energy):
+        pd = self.particle_distribution
+        if not hasattr(pd, "device_rows"):
+            raise TypeError("SecondaryLeptonsKelner06 needs an analytic naima_amd.models particle "
+                            "distribution (got %r)" % (type(pd).__name__,))
+        E = _validate_ene(energy)
+        E_eV = np.atleast_1d(E.to("eV").value).astype(float)
+        ctx = get_context()
+        N = self.batch_size
+        rows = pd.device_rows(ctx, N, amplitude_to=_PER_EV)
+        nE = E_eV.size
+        Etr = float(self.Etrans.to("eV").value)
+        match = bool(np.any(E_eV * 1e-12 < Etr * 1e-12))  # (in TeV, as the kernel decides it)
+        out, nhat = ctx.empty((N, nE)), ctx.empty((N, 3))
+        ctx.call("nh_pp_leptons_kelner06", PD_KIND[pd.kind], rows, N, ctx.const(E_eV), nE, Etr,
+                 int(match), self.products.index(self.product), out, nE, nhat)
+        if not self.on_device:
+            nh_ = nhat.get()
+            self.nhat = nh_ if self.is_batched else nh_[0]
+        dens = self.nh.to("1/cm3").value
+        if _per_walker(self.nh):
+            self.specpp = self._result(ctx, out, N, nE, E, rows=dens)
+        else:
+            self.specpp = self._result(ctx, out, N, nE, E, scale=float(dens))
+        return self.specpp
