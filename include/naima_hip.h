@@ -114,7 +114,8 @@ int nh_timer_stop(nh_ctx* ctx, double* elapsed_ms);
 enum { NH_K_PDIST = 0, NH_K_INTEGRATE = 1, NH_K_SYNCHROTRON = 2, NH_K_TABLES = 3,
        NH_K_LNPROB = 4, NH_K_SSC = 5, NH_K_GLUE = 6 /* pack, move, scatter, lincomb */,
        NH_K_ROWS = 7 /* k_integrate_rows (We/Wp) */,
-       NH_K_HALFSTEP = 8 /* k_half_step: the whole half-step in one launch */, NH_K_COUNT = 9 };
+       NH_K_HALFSTEP = 8 /* k_half_step: the whole half-step in one launch */,
+       NH_K_COOLING = 9 /* nh_cooled_electrons, nh_cooled_weights */, NH_K_COUNT = 10 };
 int nh_profile_enable(nh_ctx* ctx, int on);
 /* HIP-event time of an empty kernel: the fixed cost an event pair adds per launch */
 int nh_profile_calibrate(nh_ctx* ctx, int reps, double* overhead_us);
@@ -946,6 +947,44 @@ int nh_pairabs_rows(nh_ctx* ctx, int kind, double k_to_mec2, const nh_lazy* T_K 
 int nh_pairabs_apply(nh_ctx* ctx, const nh_pair_field* fields /*host*/, int nfields /* <= 8 */,
                      const nh_comp* comps /*host*/, int ncomp, const double* colfac, int write_tau,
                      int N, int m, double* out, int ldo);
+
+/* ---- cooled electron populations, per walker -------------------------------------------------
+ * (new: the reference has none.)  An injection rate Q(E) [1/(eV s)] switched on for age_s under
+ * the loss rate b(E) = (4/3) sigma_T c (B^2/8 pi) gamma^2 + sum_f u_f loss_f(E) [eV/s] leaves
+ *   n(E_i) = int_{E_i}^{E*} Q dE / b(E_i),  int_{E_i}^{E*} dE / b = age  (E* = E_max if never),
+ * in the power-law-per-segment picture of trapz_loglog on the grid e_eV[nC] (DEVICE, ascending):
+ * suffix sums of the segment terms, E* and the partial integral of Q by the segment's closed
+ * forms (log branch for |slope + 1| <= 1e-10, a zero node ends a segment).  Injection above
+ * e_eV[nC-1] is ignored.  FP64, the same bits at every call.
+ * nh_cooled_electrons: n_out[w*nC + i], one workgroup per walker.  Q[w*ldq + i] (DEVICE), ldq = 0:
+ *   one row for all walkers.  B_G (gauss), age_s (s; +inf: the steady state) and u[nf] (erg/cm3)
+ *   are lazy per-walker values (host structs).  loss[f*nC + i] (DEVICE): eV/s per erg/cm3 of
+ *   field f at node i; nf <= 8.  A walker with age <= 0 or NaN, B NaN or +-inf, a u that is
+ *   negative, NaN or inf, B <= 0 and no positive u, or b not positive and finite at every node
+ *   gets a NaN row and adds 1 to status[0] (DEVICE int).  Q == 0 gives exact zeros.
+ *   EINVAL: nC outside 2..2048 (40 B of LDS per node), nf outside 0..8, 0 < ldq < nC.
+ *   N = 0 is no error.
+ * nh_cooled_weights: the rows n[N][nC] on the grid e_c[nC] resampled at e_eV[nG] by log-log
+ *   linear interpolation: w[w*nG + g] = xg[g] * unit_scale * n(e_eV[g]) and dlw[g] =
+ *   ln|w[g+1]/w[g]| (dlw[nG-1] = 0), the inputs of nh_integrate_tables and nh_synchrotron.
+ *   Exactly 0 outside [e_c[0], e_c[nC-1]] and inside a segment with a zero node; a target node
+ *   that IS a grid node takes its value unchanged; dlw = 1e300 where w[g] or w[g+1] is zero or the
+ *   ratio is not finite.
+ * nh_cooled_ic_rows: Kt[i*ld + k] = the isotropic Khangulyan+14 kernel (Eq. 14, what
+ *   nh_table_ic_planck tabulates) of the electron gam[i] on a Planck field of T_K at the outgoing
+ *   photon energy gam[i] * z[k] (in m_e c^2; z[nE], gam[nC] DEVICE): every electron on its own
+ *   photon grid, one launch.  trapz_loglog of z K over z, times gam^2 m_e c^2 [eV] / (a_rad T^4),
+ *   is the loss rate per unit energy density that nh_cooled_electrons takes as `loss`.
+ *   EINVAL: T_K <= 0, ld < nE. */
+int nh_cooled_ic_rows(nh_ctx* ctx, const double* gam, int nC, const double* z, int nE, double T_K,
+                      double* Kt, int ld);
+int nh_cooled_electrons(nh_ctx* ctx, const double* Q, long long ldq, int N, const double* e_eV,
+                        int nC, const nh_lazy* B_G /*host*/, const double* loss, int nf,
+                        const nh_lazy* u /*host [nf]*/, const nh_lazy* age_s /*host*/,
+                        double* n_out, int* status);
+int nh_cooled_weights(nh_ctx* ctx, const double* n, const double* e_c, int nC, int N,
+                      const double* e_eV, const double* xg, int nG, double unit_scale, double* w,
+                      double* dlw);
 
 /* ---- thinning a chain history on the device (emcee's thin_by) -------------------------------
  * For every segment (row-major DEVICE matrices of doubles, `width` columns each):

@@ -26,7 +26,7 @@ NH_PSIS_MAX_TAIL = 4096  # nh_psis_columns' cap on the tail length (include/naim
 NH_EVID_MAX_DIM = 32     # nh_chain_cov's, nh_mvn_*'s cap on the dimension (include/naima_hip.h)
 NH_SIMPLEX_MAX_DIM = 64  # nh_simplex_*'s cap on ndim, the step kernels' own (include/naima_hip.h)
 NH_K_NAMES = ("particle_weights", "integrate_tables", "synchrotron", "tables", "lnprob",
-              "ic_seed_walkers", "glue", "integrate_rows", "half_step")
+              "ic_seed_walkers", "glue", "integrate_rows", "half_step", "cooling")
 PD_KIND = {"PowerLaw": 0, "ExponentialCutoffPowerLaw": 1, "BrokenPowerLaw": 2,
            "ExponentialCutoffBrokenPowerLaw": 3, "LogParabola": 4}
 PP_MODEL = {"Geant4": 0, "Pythia8": 1, "SIBYLL": 2, "QGSJET": 3}
@@ -178,6 +178,9 @@ _SIGS = {
     "nh_ebl_apply": [_dp, _dp, _i, _i, _dp, _i, _dp, _dp, _i, _dp, _i, _i, _dp, _i],
     "nh_pairabs_rows": [_dp, _i, _d, _dp, _dp, _dp, _dp, _i, _dp, _i, _i, _dp, _i],
     "nh_pairabs_apply": [_dp, _dp, _i, _dp, _i, _dp, _i, _i, _i, _dp, _i],
+    "nh_cooled_electrons": [_dp, _dp, _ll, _i, _dp, _i, _dp, _dp, _i, _dp, _dp, _dp, _dp],
+    "nh_cooled_ic_rows": [_dp, _dp, _i, _dp, _i, _d, _dp, _i],
+    "nh_cooled_weights": [_dp, _dp, _dp, _i, _i, _dp, _dp, _i, _d, _dp, _dp],
     "nh_column_moments": [_dp, _dp, _ll, _i, _ll, _dp, _dp],
     "nh_group_moments": [_dp, _dp, _ll, _ll, _ll, _i, _i, _i, _i, _dp, _dp],
     "nh_hist_columns": [_dp, _dp, _ll, _i, _ll, _dp, _i, C.POINTER(_i), _i, _dp, _dp],

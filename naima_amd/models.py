@@ -11,11 +11,11 @@ import numpy as np
 
 from . import units as u
 from ._lib import NH_PD_NPAR, PD_KIND, get_context
-from .constants import AR_CGS, C_CGS, HBAR_CGS, MEC2_ERG, MEC2_EV
+from .constants import AR_CGS, C_CGS, ERG_TO_EV, HBAR_CGS, MEC2_ERG, MEC2_EV, R0_CM
 from .validator import validate_physical_type, validate_scalar_or_batch
 
 __all__ = ["PowerLaw", "ExponentialCutoffPowerLaw", "BrokenPowerLaw",
-           "ExponentialCutoffBrokenPowerLaw", "LogParabola"]
+           "ExponentialCutoffBrokenPowerLaw", "LogParabola", "CooledElectrons"]
 
 
 def _validate_ene(ene):
@@ -750,3 +750,432 @@ class PairAbsorptionModel:
     def transmission(self, e):
         """exp(-tau(E)), the factor to multiply a flux with; shapes as for ``opacity``"""
         return self._result(e, False)
+
+
+# ---- cooled electron populations ---------------------------------------------------------------
+_SIGMA_T_CGS = 8.0 * np.pi / 3.0 * R0_CM ** 2
+# synchrotron loss rate [eV/s] = _COOL_SYN B[G]^2 E[eV]^2: (4/3) sigma_T c (B^2 / 8 pi) gamma^2
+_COOL_SYN = (4.0 / 3.0) * _SIGMA_T_CGS * C_CGS / (8.0 * np.pi) * ERG_TO_EV / (MEC2_EV * MEC2_EV)
+_COOL_MAX_NODES = 2048  # nh_cooled_electrons keeps 40 B of LDS per node
+
+
+def _cool_zgrid(x0, per_decade=200, edge_per_decade=100):
+    """the outgoing photon energies, as fractions z = E_ph / E_e of the electron's energy, over
+    which an electron's inverse-Compton emissivity on a Planck field is integrated to its loss
+    rate; x0 = 4 gamma kT / (m_e c^2) of the LOWEST electron energy.  Log-spaced in z from 1e-4
+    of the Thomson peak of that electron (below the peak z^2 K ~ z^2: 1e-8 of the integral is left
+    out) to 1/2, then log-spaced in 1 - z down to 1e-7, which resolves the Klein-Nishina edge at
+    z -> 1 (its width is 1 / (4 gamma kT) >= 1e-5 for the fields and energies in reach)."""
+    z_lo = 1e-4 * x0 / (1.0 + x0)
+    l0, l1 = np.log10(z_lo), np.log10(0.5)
+    lower = np.logspace(l0, l1, max(2, int(per_decade * (l1 - l0))))
+    upper = 1.0 - np.logspace(l1, -7.0, max(2, int(edge_per_decade * (l1 + 7.0))))[1:]
+    return np.concatenate([lower, upper])
+
+
+def _cool_loss_scale(T_K):
+    """(energy-weighted integral of the IC kernel over E_ph / mec2) -> eV/s per erg/cm3"""
+    return MEC2_EV / (AR_CGS * T_K ** 4)
+
+
+class CooledElectrons:
+    """The electron population that an injection rate Q(E) leaves after a time ``age`` of
+    synchrotron and inverse-Compton cooling -- the break energy is no free parameter but follows
+    from ``B``, the photon fields and the age:
+
+        n(E) = int_E^E* Q dE' / b(E),   int_E^E* dE' / b = age   (E* = Emax if never reached),
+        b(E) = (4/3) sigma_T c (B^2 / 8 pi) gamma^2 + sum_f u_f l_f(E)
+
+    with l_f the inverse-Compton loss per unit energy density of field f, Klein-Nishina included:
+    the energy-weighted integral of the emissivity that ``InverseCompton`` itself uses for a
+    thermal field of that temperature, so cooling and emission of one fit agree.  ``age=np.inf`` is
+    the steady state.  Losses are continuous, B and the injection constant in time, and injection
+    above ``Emax`` is ignored: the population falls to zero at ``Emax``.
+
+    ``injection`` is one of the five analytic distributions with an amplitude in 1/(energy time)
+    (``PowerLaw(1e36 / u.eV / u.s, ...)``), a ``SecondaryLeptonsKelner06(..., product="electron")``
+    (its source spectrum is the rate), or a pair ``(energies, rates)`` with rates of shape (nC,)
+    or (N, nC), host or device; the energies of a pair ARE the solve grid (``Emin``, ``Emax`` and
+    ``n_per_decade`` are not used then).  ``B``, ``age`` and the energy density u of every field
+    may each be a scalar, a 1-D host array (one value per walker) or a device parameter
+    (``pars[0] * u.uG``, ``10 ** pars[1] * u.yr``).  ``seed_photon_fields`` follows
+    ``InverseCompton``'s grammar for thermal fields; a field given with an angle cools like the
+    isotropic field of the same T and u (the electrons are isotropic).  The temperatures are the
+    same for every walker; the loss table of each is built in the constructor (two launches per
+    field), once per temperature and grid, and cached in HBM.
+
+    The solve runs on the model's own log-uniform grid (2 .. 2048 nodes) in one launch,
+    ``nh_cooled_electrons``, one workgroup per walker; ``Synchrotron``, ``InverseCompton`` and
+    ``Bremsstrahlung`` resample it onto their particle grids (``nh_cooled_weights``).  A walker
+    with age <= 0 or NaN, B NaN, B <= 0 and no positive u, or a negative or non-finite u gets a
+    NaN row: put a prior on them.  The amplitude is a rate, so ``set_We`` does not apply;
+    ``compute_We`` gives the energy the population holds.  Changing a parameter of the injection
+    object after the first evaluation is not seen: build a new model."""
+    kind = "cooled"
+    _cached = ("_solved", "_w_dev", "_host_rows")
+
+    def __init__(self, injection, B, age, seed_photon_fields=("CMB",), Emin=1 * u.GeV,
+                 Emax=510.998 * u.TeV, n_per_decade=100):
+        from .radiative import InverseCompton, _log_grid, _per_walker as _pw
+        from .validator import validate_scalar
+        validate_physical_type("B", B, "magnetic flux density")
+        validate_physical_type("age", age, "time")
+        for name, q in (("B", B), ("age", age)):
+            if not q.on_device and np.ndim(q.value) > 1:
+                raise TypeError("{0} should be a scalar or a 1-D batch over walkers".format(name))
+        fields = seed_photon_fields
+        if isinstance(fields, tuple):
+            fields = list(fields)
+        if type(fields) is list:
+            for s in fields:
+                if type(s) is list and len(s) in (3, 4) and isinstance(s[1], u.Quantity) \
+                        and s[1].unit.physical_type != "temperature":
+                    raise NotImplementedError(
+                        "%s: cooling on monochromatic or tabulated photon fields is not "
+                        "implemented; give thermal fields [name, T, u]" % s[0])
+        seeds = InverseCompton._process_input_seed(fields) if fields else {}
+        if len(seeds) > 8:
+            raise ValueError("at most 8 photon fields, got %d" % len(seeds))
+        for name, seed in seeds.items():
+            if _pw(seed["T"]):
+                raise NotImplementedError(
+                    "%s-T must be the same for every walker of a batch (the loss table is "
+                    "shared); evaluate walkers with different %s-T in separate calls"
+                    % (name, name))
+            if not float(seed["T"].to("K").value) > 0:
+                raise ValueError("{0}-T value should be strictly positive".format(name))
+        d = self.__dict__
+        d["seed_photon_fields"] = seeds
+        d["B"], d["age"] = B, age
+        d["injection"] = injection
+        # -- the injection and the solve grid --
+        if isinstance(injection, (tuple, list)) and len(injection) == 2:
+            e, r = injection
+            e = _validate_ene(e)
+            e_eV = np.atleast_1d(e.to("eV").value).astype(float).ravel()
+            if not isinstance(r, u.Quantity):
+                raise TypeError("injection rates should be given as a Quantity object")
+            amp = u.Quantity(1.0, r.unit) * u.s
+            if not r.on_device and np.shape(r.value)[-1:] != (e_eV.size,) \
+                    or r.on_device and tuple(r.value.shape)[-1:] != (e_eV.size,):
+                raise ValueError("injection rates need one value per energy (%d)" % e_eV.size)
+            if np.any(~np.isfinite(e_eV)) or np.any(e_eV <= 0) or np.any(np.diff(e_eV) <= 0):
+                raise ValueError("injection energies should be positive and ascending")
+            d["_inj"] = "rows"
+        else:
+            lo = validate_scalar("Emin", Emin, domain="strictly-positive", physical_type="energy")
+            hi = validate_scalar("Emax", Emax, domain="strictly-positive", physical_type="energy")
+            e_eV = _log_grid(float(lo.to("eV").value), float(hi.to("eV").value), n_per_decade)
+            if hasattr(injection, "device_rows"):
+                amp = injection.amplitude
+                if not isinstance(amp, u.Quantity):
+                    raise TypeError("the injection amplitude should be given as a Quantity object")
+                amp = amp * u.s
+                d["_inj"] = "analytic"
+            elif getattr(injection, "product", None) == "electron" and hasattr(injection, "flux"):
+                amp = u.Quantity(1.0, "1/eV")
+                d["_inj"] = "secondary"
+            else:
+                raise TypeError("injection should be an analytic particle distribution with an "
+                                "amplitude in 1/(energy time), a SecondaryLeptonsKelner06 with "
+                                "product='electron', or a pair (energies, rates)")
+        validate_physical_type("injection amplitude x time", amp, "differential energy")
+        if not 2 <= e_eV.size <= _COOL_MAX_NODES:
+            raise ValueError("the solve grid has %d nodes; 2 .. %d are possible"
+                             % (e_eV.size, _COOL_MAX_NODES))
+        d["_e"] = e_eV
+        d["amplitude"] = amp
+        d["Emin"], d["Emax"], d["n_per_decade"] = Emin, Emax, n_per_decade
+        inj_names = ["injection." + n for n in getattr(injection, "param_names", ())] \
+            if d["_inj"] != "rows" else ["injection"]
+        d["param_names"] = ["B", "age"] + inj_names + [n + "-u" for n in seeds]
+        self.batch_size  # (raises on inconsistent batch sizes)
+        if seeds:  # the loss table of these temperatures on this grid: built here, once, cached
+            ctx = get_context()
+            self._loss_table(ctx, ctx.const(e_eV))
+
+    def __setattr__(self, name, value):
+        # any parameter change invalidates the cached solves and weights
+        for c in self._cached:
+            self.__dict__.pop(c, None)
+        object.__setattr__(self, name, value)
+
+    # -- what is given per walker ------------------------------------------------------------
+    def _given(self):
+        return [self.B, self.age] + [s["u"] for s in self.seed_photon_fields.values()]
+
+    def _rates(self):
+        return self.injection[1] if self._inj == "rows" else None
+
+    @property
+    def energies(self):
+        """the solve grid"""
+        return u.Quantity(self._e.copy(), "eV")
+
+    @property
+    def on_device(self):
+        if any(q.on_device for q in self._given()):
+            return True
+        if self._inj == "rows":
+            return self._rates().on_device
+        return bool(getattr(self.injection, "on_device", False))
+
+    def _sizes(self):
+        out = []
+        for q in self._given():
+            v = q.value
+            out.append(v.n if q.on_device else (np.shape(v)[0] if np.ndim(v) > 0 else 1))
+        if self._inj == "rows":
+            sh = tuple(self._rates().value.shape)
+            out.append(sh[0] if len(sh) == 2 else 1)
+        else:
+            out.append(self.injection.batch_size)
+        return out
+
+    @property
+    def batch_size(self):
+        n = 1
+        for m in self._sizes():
+            if n != 1 and m != 1 and m != n:
+                raise ValueError("inconsistent walker-batch sizes in CooledElectrons: %d vs %d"
+                                 % (n, m))
+            n = max(n, m)
+        return n
+
+    @property
+    def is_batched(self):
+        if any(q.on_device or np.ndim(q.value) > 0 for q in self._given()):
+            return True
+        if self._inj == "rows":
+            return len(tuple(self._rates().value.shape)) == 2
+        return bool(self.injection.is_batched)
+
+    def _walker(self, k):
+        """this model for walker k alone (host values)"""
+        def one(q):
+            return q[k] if np.ndim(q.value) > 0 else q
+        inj = self.injection
+        if self._inj == "rows":
+            r = self._rates()
+            inj = (inj[0], r[k] if np.ndim(r.value) == 2 else r)
+        elif inj.is_batched:
+            import copy
+            src, inj = inj, copy.copy(inj)
+            inj.__dict__ = {a: b for a, b in src.__dict__.items() if not a.startswith("_")}
+            pd = getattr(inj, "particle_distribution", None)
+            if pd is not None:
+                pd2 = copy.copy(pd)
+                pd2.__dict__ = {a: b for a, b in pd.__dict__.items() if not a.startswith("_")}
+                inj.__dict__["particle_distribution"] = pd = pd2
+            for obj in (inj, pd):
+                for name in getattr(obj, "param_names", ()) if obj is not None else ():
+                    v = getattr(obj, name, None)
+                    if isinstance(v, u.Quantity) and np.ndim(v.value) > 0 or \
+                            not isinstance(v, (u.Quantity, str)) and np.ndim(v) > 0:
+                        obj.__dict__[name] = v[k]
+        fields = [[n, s["T"], one(s["u"])] for n, s in self.seed_photon_fields.items()]
+        return CooledElectrons(inj, one(self.B), one(self.age), fields, self.Emin, self.Emax,
+                               self.n_per_decade)
+
+    # -- the loss table ----------------------------------------------------------------------
+    def _loss_table(self, ctx, ed):
+        """loss[nf][nC] in HBM (eV/s per erg/cm3 of each field at every node of the solve grid),
+        built once per (temperatures, grid) and cached like the emission tables: the project's IC
+        emissivity on a Planck field (the isotropic kernel of nh_table_ic_planck, by
+        nh_cooled_ic_rows on a row of outgoing photon energies per node: two launches per field),
+        reduced with the energy weight (nh_trapz_loglog_comps)"""
+        import ctypes as C
+
+        from . import _lib
+        from .darray import TF_SQUARE, nh_comp, nh_lazy
+        Ts = tuple(float(s["T"].to("K").value) for s in self.seed_photon_fields.values())
+        if not Ts:
+            return None
+        e_eV, nC = self._e, self._e.size
+
+        def build():
+            gam = e_eV / MEC2_EV
+            gd = ctx.const(gam)
+            out = ctx.empty((len(Ts), nC))
+            for f, T in enumerate(Ts):
+                z = _cool_zgrid(4.0 * gam[0] * T * _K_TO_MEC2)
+                nE = z.size
+                zd = ctx.const(z)
+                Kt = ctx.empty((nC, nE))
+                # (a table build, not a step-loop launch: called directly, never recorded)
+                _lib._chk(_lib._lib.nh_cooled_ic_rows(ctx.h, gd.ptr, nC, zd.ptr, nE, T, Kt.ptr, nE))
+                comp = (nh_comp * 1)(nh_comp(Kt.ptr, nE, _cool_loss_scale(T)))
+                g2 = nh_lazy(gd.ptr, 1, 1.0, 1.0, 0.0, TF_SQUARE, 0)  # E_ph = gamma z: gamma^2
+                _lib._chk(_lib._lib.nh_trapz_loglog_comps(
+                    ctx.h, comp, 1, zd.ptr, C.addressof(g2), zd.ptr, nC, nE,
+                    out.ptr + 8 * f * nC, 1))
+                ctx.sync()  # (Kt goes back to the pool when this scope ends)
+                del Kt
+            return out, gd, ed
+
+        return ctx.table(("cool-loss", ed.ptr) + Ts, build)[0]
+
+    # -- the solve ---------------------------------------------------------------------------
+    def _injection_rows(self, ctx, ed):
+        """(owner, pointer, ldq, rows) of Q[rows][nC] in 1/(eV s) on the solve grid"""
+        nC = self._e.size
+        if self._inj == "analytic":
+            inj = self.injection
+            Ni = inj.batch_size
+            rows = inj.device_rows(ctx, Ni, amplitude_to=u.Unit("1/(eV s)"))
+            w, lw, q = ctx.empty((Ni, nC)), ctx.empty((Ni, nC)), ctx.empty((Ni, nC))
+            ctx.call("nh_particle_weights", PD_KIND[inj.kind], rows, Ni, ed, ed, nC, 1.0, w, lw, q)
+            return q, q.ptr, nC if Ni > 1 else 0, Ni
+        if self._inj == "secondary":
+            r = self.injection.flux(u.Quantity(self._e, "eV"), distance=0)
+        else:
+            r = self._rates()
+        v = r.to("1/(eV s)").value
+        if r.on_device:  # (a device matrix: its dense [N][nC] form, one launch unless it is that)
+            own, ptr = v.buffer()
+            return own, ptr, nC if v.shape[0] > 1 else 0, v.shape[0]
+        v = np.ascontiguousarray(np.atleast_2d(np.asarray(v, dtype=float)))
+        own = ctx.array(v)
+        return own, own.ptr, nC if v.shape[0] > 1 else 0, v.shape[0]
+
+    def _solve(self, ctx, N=None):
+        """n[N][nC] (1/eV) in HBM: one nh_cooled_electrons launch per parameter state"""
+        import ctypes as C
+
+        from .darray import DVec, lazy_const, nh_lazy
+        N = self.batch_size if N is None else N
+        cache = self.__dict__.setdefault("_solved", {})
+        hit = cache.get(N)
+        if hit is not None:
+            return hit
+        nC = self._e.size
+        ed = ctx.const(self._e)
+        keep = []
+
+        def lazy_of(q, unit):
+            v = _pa_value(ctx, q, unit)
+            if isinstance(v, DVec):
+                if v.n != N:
+                    raise ValueError("a per-walker value has %d walkers, the batch has %d"
+                                     % (v.n, N))
+                keep.append(v)
+                return v.lazy()
+            return lazy_const(v)
+
+        Bl, agel = lazy_of(self.B, "G"), lazy_of(self.age, "s")
+        seeds = list(self.seed_photon_fields.values())
+        ul = (nh_lazy * max(len(seeds), 1))()
+        for f, s in enumerate(seeds):
+            ul[f] = lazy_of(s["u"], "erg/cm3")
+        loss = self._loss_table(ctx, ed)
+        own, qptr, ldq, nrows = self._injection_rows(ctx, ed)
+        if ldq and nrows != N:
+            raise ValueError("the injection has %d rows, the batch has %d" % (nrows, N))
+        out = ctx.empty((N, nC))
+        ctx.call("nh_cooled_electrons", qptr, ldq, N, ed, nC, C.addressof(Bl),
+                 loss.ptr if loss is not None else None, len(seeds), ul, C.addressof(agel), out,
+                 cool_status(ctx))
+        del own, keep
+        cache[N] = out
+        return out
+
+    def _resample(self, ctx, n, N, e_eV, xg, unit_scale):
+        """(w, dlw) on a target grid: one nh_cooled_weights launch"""
+        nG = e_eV.size
+        w, lw = ctx.empty((N, nG)), ctx.empty((N, nG))
+        ctx.call("nh_cooled_weights", n, ctx.const(self._e), self._e.size, N, ctx.const(e_eV),
+                 ctx.const(xg), nG, float(unit_scale), w, lw)
+        return w, lw
+
+    def __call__(self, e):
+        """dN/dE in 1/eV at energies ``e`` -- (n_e,), (N, n_e), or a device matrix when a
+        parameter lives on the device; zero outside the solve grid"""
+        from .darray import DMat
+        e = _validate_ene(e)
+        e_eV = np.atleast_1d(e.to("eV").value).astype(float).ravel()
+        ctx = get_context()
+        N = self.batch_size
+        w, _ = self._resample(ctx, self._solve(ctx), N, e_eV, np.ones(e_eV.size), 1.0)
+        if self.on_device:
+            return u.Quantity(DMat.from_buffer(ctx, w, N, e_eV.size), "1/eV")
+        out = w.get()
+        if e.isscalar:
+            out = out[:, 0]
+        return u.Quantity(out if self.is_batched else out[0], "1/eV")
+
+    # -- host views: cooling time and break energy -------------------------------------------
+    def _host_b(self):
+        """(b[N][nC] in eV/s on the solve grid, age[N] in s), from downloaded values"""
+        hit = self.__dict__.get("_host_rows")
+        if hit is None:
+            ctx = get_context()
+            N = self.batch_size
+
+            def host(q, unit):
+                return np.broadcast_to(np.asarray(q.to(unit).value, dtype=float), (N,))
+            B = host(self.B, "G")
+            b = _COOL_SYN * (B * B)[:, None] * (self._e * self._e)[None, :]
+            seeds = list(self.seed_photon_fields.values())
+            if seeds:
+                loss = self._loss_table(ctx, ctx.const(self._e)).get()
+                for f, s in enumerate(seeds):
+                    b = b + host(s["u"], "erg/cm3")[:, None] * loss[f][None, :]
+            hit = self.__dict__["_host_rows"] = (b, host(self.age, "s"))
+        return hit
+
+    def cooling_time(self, e):
+        """gamma / |dgamma/dt| in seconds at energies ``e``: (n_e,) or (N, n_e); the loss rate is
+        interpolated log-log between the nodes of the solve grid and NaN outside it"""
+        e = _validate_ene(e)
+        x = np.log(np.atleast_1d(e.to("eV").value).astype(float).ravel())
+        b, _ = self._host_b()
+        lg = np.log(self._e)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out = np.stack([np.exp(x - np.interp(x, lg, np.log(row), left=np.nan, right=np.nan))
+                            for row in b])
+        if e.isscalar:
+            out = out[:, 0]
+        return u.Quantity(out if self.is_batched else out[0], "s")
+
+    def break_energy(self):
+        """the energy at which the cooling time equals the age, per walker (bisection in ln E on
+        the downloaded loss rows); NaN where the two do not meet inside the solve grid"""
+        b, age = self._host_b()
+        lg = np.log(self._e)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            lt = lg[None, :] - np.log(b)  # ln of the cooling time at the nodes
+            la = np.log(age)
+        out = np.full(b.shape[0], np.nan)
+        for k in range(b.shape[0]):
+            f = lambda x: np.interp(x, lg, lt[k]) - la[k]  # noqa: E731
+            lo, hi = lg[0], lg[-1]
+            if not (np.isfinite(la[k]) and f(lo) * f(hi) <= 0):
+                continue
+            flo = f(lo)
+            for _ in range(100):
+                mid = 0.5 * (lo + hi)
+                if f(mid) * flo > 0:
+                    lo = mid
+                else:
+                    hi = mid
+            out[k] = np.exp(0.5 * (lo + hi))
+        return u.Quantity(out if self.is_batched else out[0], "eV")
+
+
+def cool_status_read(ctx, reset=True):
+    """NaN rows that nh_cooled_electrons has given out-of-domain walkers on this context since
+    the last reset (synchronises; not while a graph is captured)"""
+    st = cool_status(ctx)
+    n = int(st.get()[0])
+    if reset and n:
+        st.set(np.zeros(1, dtype=np.int32))
+    return n
+
+
+def cool_status(ctx):
+    """the device int nh_cooled_electrons counts NaN rows in (one per context; it only grows
+    until cool_status_read resets it)"""
+    st = getattr(ctx, "_cool_status", None)
+    if st is None:
+        st = ctx._cool_status = ctx.array(np.zeros(1, dtype=np.int32), dtype=np.int32)
+    return st

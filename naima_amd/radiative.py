@@ -140,13 +140,17 @@ class BaseRadiative:
         for c in ("_cache", "_queue"):
             if c in one.__dict__:
                 one.__dict__[c] = type(one.__dict__[c])()
-        pd = copy.copy(self.particle_distribution)
-        pd.__dict__ = {a: b for a, b in self.particle_distribution.__dict__.items()
-                       if not a.startswith("_")}
-        for name in getattr(pd, "param_names", ()):
-            v = getattr(pd, name)
-            if _is_batched(v):
-                setattr(pd, name, v[k])
+        if getattr(self.particle_distribution, "kind", None) == "cooled":
+            # (B, age, every u and the injection's own parameters, sliced by the model itself)
+            pd = self.particle_distribution._walker(k)
+        else:
+            pd = copy.copy(self.particle_distribution)
+            pd.__dict__ = {a: b for a, b in self.particle_distribution.__dict__.items()
+                           if not a.startswith("_")}
+            for name in getattr(pd, "param_names", ()):
+                v = getattr(pd, name)
+                if _is_batched(v):
+                    setattr(pd, name, v[k])
         one.particle_distribution = pd
         for name in tuple(self._structural) + tuple(self._walker_scalars):
             if hasattr(self, name):
@@ -217,6 +221,8 @@ class BaseRadiative:
         pd = self.particle_distribution
         if getattr(pd, "kind", None) == "table":
             return self._weights_table(pd, xg, e_eV, unit_scale)
+        if getattr(pd, "kind", None) == "cooled":
+            return self._weights_cooled(pd, xg, e_eV, unit_scale)
         if not hasattr(pd, "device_rows"):
             raise TypeError("naima_amd radiative models need a naima_amd.models particle "
                             "distribution (got %r)" % (type(pd).__name__,))
@@ -296,6 +302,22 @@ class BaseRadiative:
             comp[0] = nh_comp(d0d.ptr, 0, 1.0)
             ctx.call("nh_lincomb", comp, 1, None, None, N, nG, lw, nG)
             hit = cache[key] = (w, lw)
+        return ctx, N, hit[0], hit[1], xd, lx
+
+    def _weights_cooled(self, pd, xg, e_eV, unit_scale):
+        """weights of a CooledElectrons distribution: the cooling solve once per parameter
+        state (nh_cooled_electrons, cached on the distribution), then its rows resampled onto
+        this grid (nh_cooled_weights, cached per grid, unit scale and batch size)"""
+        ctx = get_context()
+        N = self.batch_size
+        xd, ed = ctx.const(xg), ctx.const(e_eV)
+        lx = ctx.grid_logratio(xd)
+        n = pd._solve(ctx, N)
+        cache = pd.__dict__.setdefault("_w_dev", {})
+        key = (xd.ptr, ed.ptr, float(unit_scale), N)
+        hit = cache.get(key)
+        if hit is None:
+            hit = cache[key] = pd._resample(ctx, n, N, e_eV, xg, unit_scale)
         return ctx, N, hit[0], hit[1], xd, lx
 
     # -- public ---------------------------------------------------------------
@@ -395,6 +417,11 @@ class BaseElectron(BaseRadiative):
 
     def _general_supported(self):
         return False
+
+    def _pd_analytic(self):
+        """False for a CooledElectrons distribution: it has no parameter rows that
+        nh_general_electron could evaluate on a grid per walker"""
+        return getattr(self.particle_distribution, "kind", None) != "cooled"
 
     def _general_needed(self):
         """True when the spectrum has to come from nh_general_electron (no table to share)"""
@@ -569,6 +596,10 @@ class BaseElectron(BaseRadiative):
     def set_We(self, We, Eemin=None, Eemax=None, amplitude_name=None):
         """Normalize the particle distribution so that the electron energy between
         Eemin and Eemax is We (radiative.py:197-236)"""
+        if getattr(self.particle_distribution, "kind", None) == "cooled":
+            raise NotImplementedError(
+                "set_We does not apply to a CooledElectrons distribution: its amplitude is an "
+                "injection rate; scale the injection, or read the energy with compute_We")
         We = validate_scalar_or_batch("We", We, physical_type="energy")
         oldWe = self.compute_We(Eemin=Eemin, Eemax=Eemax)
         ratio = (We / oldWe).decompose().value
@@ -630,7 +661,7 @@ class Synchrotron(BaseElectron):
             and (rider.a, rider.b, rider.c, rider.tf) == (Bv.a, Bv.b, Bv.c, Bv.tf)
 
     def _general_supported(self):
-        return True
+        return self._pd_analytic()
 
     def _spectrum(self, photon_energy):
         E = _validate_ene(photon_energy)
@@ -680,7 +711,7 @@ class InverseCompton(BaseElectron):
         energy density may all be per walker), monochromatic / tabulated seeds that every walker
         shares, and tabulated seeds with a photon density per walker (SSC:
         nh_general_electron_seed_rows)"""
-        return True
+        return self._pd_analytic()
 
     def _seed_shape_per_walker(self):
         """a thermal seed whose temperature or angle is given per walker: its Khangulyan kernel
@@ -1053,7 +1084,7 @@ class Bremsstrahlung(BaseElectron):
     _walker_scalars = ("n0",)
 
     def _general_supported(self):
-        return True
+        return self._pd_analytic()
 
     def __init__(self, particle_distribution, n0=1 / u.cm ** 3, **kwargs):
         super().__init__(particle_distribution)
