@@ -1235,6 +1235,7 @@ __global__ __launch_bounds__(RT > 0 ? 512 : 1024) void k_half_step_run(const hs_
       }
       const int nz = hi[HI_DEAD] ? 0 : hi[HI_NZ];  // (forbidden by the prior: nothing is integrated)
       int nA = 0, Cd = 1, nS = 0;
+      hs_s2_lanes SL = {1, 0};  // (the log-domain items' chunks per energy; the direct form: Cd for all)
       if (has_syn) {
         const int nEs = H.syn_nE;
         for (int q = 0; q < syn_tiles; ++q) nA += tcnt[q];
@@ -1257,6 +1258,10 @@ __global__ __launch_bounds__(RT > 0 ? 512 : 1024) void k_half_step_run(const hs_
           }
           Cd = min(max(Cd, 1), D.syn_cdmax);
           nS = (nA * Cd + 63) >> 6;
+          // (the log-domain items: no lane of the nS items left empty -- the longest ranges take
+          // one chunk more, nh_syn2.h)
+          SL.cd = Cd;
+          if (S2) SL = hs_s2_spread(nA, Cd, nS, D.syn_cdmax);
         }
         if (syn_zero) {
           for (int k = tid; k < nEs; k += T) spec[H.syn_spec_off + k] = syn_nan ? NAN : 0.0;
@@ -1455,10 +1460,10 @@ __global__ __launch_bounds__(RT > 0 ? 512 : 1024) void k_half_step_run(const hs_
             // (the tile waves' constants were written ahead of barrier 2)
             const int g = H.syn_grid, nEs = H.syn_nE;
             if (S2) {
-              hs_syn2_item(ix, lane, nA, Cd, nEs, R.s2, reinterpret_cast<const int*>(sm + H.o_amap) + nEs,
-                           reinterpret_cast<const int*>(sm + R.o_s2z), sm + R.o_s2q,
-                           hs_lds_addr(sm + R.o_s2lw + HS_S2_GUARD), hs_lds_addr(sm + R.o_s2ig + HS_S2_GUARD),
-                           hs_lds_addr(sm + R.o_s2tab), hs_lds_addr(sm + R.o_s2t), part_s);
+              hs_syn2_item_spread(ix, lane, nA, SL, nEs, R.s2, reinterpret_cast<const int*>(sm + H.o_amap) + nEs,
+                                  reinterpret_cast<const int*>(sm + R.o_s2z), sm + R.o_s2q,
+                                  hs_lds_addr(sm + R.o_s2lw + HS_S2_GUARD), hs_lds_addr(sm + R.o_s2ig + HS_S2_GUARD),
+                                  hs_lds_addr(sm + R.o_s2tab), hs_lds_addr(sm + R.o_s2t), part_s);
             } else {
               const hs_syn_lds L = {reinterpret_cast<const int*>(sm + H.o_amap), sm + H.o_ig2,
                                     sm + H.o_dig2, sm + H.o_ig23, sm + H.o_w[g], sm + H.o_d[g],
@@ -1528,10 +1533,11 @@ __global__ __launch_bounds__(RT > 0 ? 512 : 1024) void k_half_step_run(const hs_
         for (int a = T - 1 - tid; a < nA; a += T) {  // (from the back: the tables took the front)
           const double* pp = sm + H.o_part_s + a;
           double sum = 0.0;
-          for (int c0 = 0; c0 < Cd; c0 += 8) {
+          const int cda = hs_s2_chunks_of(SL, a);  // (this energy's chunks)
+          for (int c0 = 0; c0 < cda; c0 += 8) {
             double v[8];
 #pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = c0 + q < Cd ? pp[(c0 + q) * nEs] : 0.0;
+            for (int q = 0; q < 8; ++q) v[q] = c0 + q < cda ? pp[(c0 + q) * nEs] : 0.0;
             sum += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
           }
           sum *= NH_ERG_PER_EV;  // 1/(s erg) -> 1/(s eV), :340

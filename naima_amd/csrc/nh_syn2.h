@@ -120,27 +120,76 @@ __device__ __forceinline__ int hs_div_small(int x, int d, float rd) {
   return q;
 }
 
-// One work item: 64 (live photon energy, chunk) pairs.  Per live energy a (compacted, as in
-// hs_syn_item): ai0[a] its first live node, Zs[a] the comb index of node 0, and in sq (nEs
-// apart) q | Lambda ln(q) / 3 | f / m | CS1 (signed by the amplitude).
-// a_lw / a_ig: LDS byte addresses of node 0 of the walker's Lambda ln(w) and of the grid's
-// 1/gamma^2 (HS_S2_GUARD entries either side); a_tab: the table, HS_S2_STRIDE doubles per
-// piece, 16-byte aligned; a_t128: 2^(j/128), j < 128.
-__device__ HS_S2_INLINE void hs_syn2_item(int ix, int lane, int nA, int Cd, int nEs,
-                                             const hs_syn2_par& S, const int* ai0, const int* Zs,
-                                             const double* sq, unsigned a_lw, unsigned a_ig,
-                                             unsigned a_tab, unsigned a_t128, double* part_s) {
-  const int vt = ix * 64 + lane;
-  const int ch = hs_div_small(vt, nA, __builtin_amdgcn_rcpf((float)nA));  // (nA, Cd: wave-uniform)
-  const int a = vt - ch * nA;
-  if (ch >= Cd) return;
+// ---- how a slice's live energies share the lanes of its work items --------------------------------
+// The launch plans ONE chunk count Cd for every live energy (from the mean range) and nS = ceil(nA Cd
+// / 64) items; a wave runs as long as its longest lane, so the lanes of the longest range -- the
+// lowest photon energy: the first live node moves up the grid with ln E -- set the pace, and the
+// lanes the last item has left over (cfg3: 12 of 192) carry nothing.  Spread: every energy gets
+// cd = floor(64 nS / nA) >= Cd chunks, and the first nx = 64 nS - nA cd energies of the compacted
+// order -- the longest ranges when the photon energies ascend, as naima's do -- one more, so that no
+// lane of the planned items is left empty (cfg3: 5 chunks, 6 for the first twelve; the longest lane
+// 11 pieces where it had 12).  At most cdmax chunks per energy (the partial sums' room).  Any order
+// of the energies is correct: each is cut into its own chunk count.  Pure, wave-uniform, the same
+// function in the kernel and on the host (tests/test_item_lanes_host.py).
+struct hs_s2_lanes {
+  int cd, nx;  // chunks of every live energy | the first nx of them have cd + 1
+};
+// floor(x / d), 0 <= x < 2^20, 1 <= d < 2^12: in the kernel hs_div_small with d's single-precision
+// reciprocal (every wave forms these quotients in every slice, ahead of its first item: an integer
+// division is ~25 instructions each); on the host the division itself -- the same number
+__host__ __device__ static inline int hs_s2_quot(int x, int d) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return hs_div_small(x, d, __builtin_amdgcn_rcpf((float)d));
+#else
+  return x / d;
+#endif
+}
+// (the quotients' ranges: a plan has at most 512 photon energies and 32 chunks of each, and a grid
+// that fits LDS has fewer than 2^15 nodes)
+__host__ __device__ static inline hs_s2_lanes hs_s2_spread(int nA, int Cd, int nS, int cdmax) {
+  hs_s2_lanes L = {Cd, 0};
+  if (nA < 1 || nS < 1) return L;
+  const int lanes = 64 * nS;
+  int cd = hs_s2_quot(lanes, nA);
+  if (cd < Cd) cd = Cd;  // (never: nS = ceil(nA Cd / 64))
+  if (cd >= cdmax) {
+    L.cd = cdmax > Cd ? cdmax : Cd;
+    return L;
+  }
+  L.cd = cd;
+  L.nx = lanes - nA * cd;  // (< nA)
+  return L;
+}
+// lane vt of the items (ix 64 + lane) -> energy a of the compacted order, its chunk ch of cda; false: idle
+// (the energies run fastest, as with one chunk count: neighbouring lanes hold the SAME chunk of
+// neighbouring energies, whose nodes and table pieces lie beside each other in LDS.  The chunks of one
+// energy on neighbouring lanes read it a chunk length apart -- 128 bytes for cfg2's 16-node chunks:
+// two banks for the whole wave; cfg2 / 256 measured 9.24 -> 7.99 M walker-steps/s that way.  The
+// extra chunk of the first nx energies: the lanes behind everybody's cd chunks.)
+__host__ __device__ static inline bool hs_s2_lane_of(const hs_s2_lanes& L, int nA, int vt, int& a, int& ch, int& cda) {
+  const int body = nA * L.cd;  // (wave-uniform)
+  const bool extra = vt >= body;
+  const int q = hs_s2_quot(extra ? 0 : vt, nA);
+  ch = extra ? L.cd : q;
+  a = extra ? vt - body : vt - q * nA;
+  cda = L.cd + (a < L.nx ? 1 : 0);
+  return a < (extra ? L.nx : nA);
+}
+// the chunks of energy a (the sum phase)
+__host__ __device__ static inline int hs_s2_chunks_of(const hs_s2_lanes& L, int a) { return L.cd + (a < L.nx ? 1 : 0); }
+// nodes per chunk of a range of nodes k0 .. kend cut into cda chunks of whole pieces (m = 1 << lm nodes)
+__host__ __device__ static inline int hs_s2_chunk_nodes(int k0, int kend, int cda, int lm) {
+  const int per = hs_s2_quot(kend - k0 + cda, cda);
+  return ((per + (1 << lm) - 1) >> lm) << lm;
+}
+
+// One lane of a work item: chunk ch -- `per` nodes, whole pieces -- of live energy a, whose range
+// starts at comb index k0 (a piece boundary) and ends at kend, the grid's last node; node 0 of the
+// grid sits at comb index Z.  Returns the chunk's part of the integral (CS1 and 1 / ilx applied).
+__device__ HS_S2_INLINE double hs_syn2_chunk(int a, int Z, int kb, int per, int kend, int nEs,
+                                              const hs_syn2_par& S, const double* sq, unsigned a_lw,
+                                              unsigned a_ig, unsigned a_tab, unsigned a_t128) {
   const int lm = S.lm, m = 1 << lm;
-  const int Z = Zs[a];
-  const int k0 = ((Z + ai0[a]) >> lm) << lm;  // the range starts on a piece boundary
-  const int kend = Z + S.nG - 1;              // the grid's last node
-  int per = hs_div_small(kend - k0 + Cd, Cd, __builtin_amdgcn_rcpf((float)Cd));  // nodes k0 .. kend over Cd chunks ...
-  per = ((per + m - 1) >> lm) << lm;          // ... of whole pieces
-  const int kb = k0 + ch * per;
   // The segments' log-ratios stay in the exponents' own unit (1/128 octave): dl' = dE ilx has the
   // same ilx for every segment of a log-uniform grid, so the sum is taken over (u2 - u1) / dE and
   // multiplied by 1 / ilx once (one multiplication per node less); |dl'| < th = 2^-10 / lx  <=>
@@ -151,7 +200,11 @@ __device__ HS_S2_INLINE void hs_syn2_item(int ix, int lane, int nA, int Cd, int 
   if (kb <= kend) {
     const int n = min(per, kend - kb + 1);
     const int groups = (n + m - 1) >> lm;     // (the last chunk's last piece runs on into the guards)
-    const double qx = sq[a], Kc = sq[nEs + a], lam0 = sq[2 * nEs + a];
+    const double Kc = sq[nEs + a], lam0 = sq[2 * nEs + a];
+    // (-Lambda x = (-Lambda q) / gamma^2: the constant folded into the lane's q once, so that a node's
+    // exponent is one FMA on the grid's 1 / gamma^2 -- it was a product and an FMA; E moves by a
+    // rounding of Lambda x, 1e-14 relative on u)
+    const double qxl = -HS_S2_LAMBDA * sq[a];
     double c0, c1, c2, c3, c4, c5;
     auto coefs = [&](int p, int kfirst, double& lam) {  // piece p, whose first node is kfirst
       const int pe = min(p, S.P);
@@ -163,13 +216,12 @@ __device__ HS_S2_INLINE void hs_syn2_item(int ix, int lane, int nA, int Cd, int 
       lam = fma((double)(kfirst - (pe << lm)), S.im, lam0);  // (= f / m inside the table)
     };
     auto node = [&](unsigned pl, unsigned pg, double lam, double& E, double& u) {
-      const double x = qx * hs_s2_ld(pg);  // (q / gamma^2: one product -- it was the cube of cbrt(q) cbrt(1/gamma^2), three)
       double g = fma(c5, lam, c4);
       g = fma(g, lam, c3);
       g = fma(g, lam, c2);
       g = fma(g, lam, c1);
       g = fma(g, lam, c0);
-      E = fma(x, -HS_S2_LAMBDA, g) + hs_s2_ld(pl);
+      E = fma(qxl, hs_s2_ld(pg), g) + hs_s2_ld(pl);  // (g - Lambda q / gamma^2 + Lambda ln w)
       u = hs_exp128(E, a_t128);
     };
     // the start node kb - 1: the last node of the piece before
@@ -201,7 +253,45 @@ __device__ HS_S2_INLINE void hs_syn2_item(int ix, int lane, int nA, int Cd, int 
   // instructions per item)
   double ilx_here = S.ilx;
   asm volatile("" : "+v"(ilx_here));
-  part_s[ch * nEs + a] = acc * (sq[3 * nEs + a] * nh_rcp(ilx_here));
+  return acc * (sq[3 * nEs + a] * nh_rcp(ilx_here));
+}
+
+// One work item: 64 (live photon energy, chunk) pairs.  Per live energy a (compacted, as in
+// hs_syn_item): ai0[a] its first live node, Zs[a] the comb index of node 0, and in sq (nEs
+// apart) q | Lambda ln(q) / 3 | f / m | CS1 (signed by the amplitude).
+// a_lw / a_ig: LDS byte addresses of node 0 of the walker's Lambda ln(w) and of the grid's
+// 1/gamma^2 (HS_S2_GUARD entries either side); a_tab: the table, HS_S2_STRIDE doubles per
+// piece, 16-byte aligned; a_t128: 2^(j/128), j < 128.
+// (one chunk count for every energy: the kernel of one launch per half-step)
+__device__ HS_S2_INLINE void hs_syn2_item(int ix, int lane, int nA, int Cd, int nEs,
+                                             const hs_syn2_par& S, const int* ai0, const int* Zs,
+                                             const double* sq, unsigned a_lw, unsigned a_ig,
+                                             unsigned a_tab, unsigned a_t128, double* part_s) {
+  const int vt = ix * 64 + lane;
+  const int ch = hs_div_small(vt, nA, __builtin_amdgcn_rcpf((float)nA));  // (nA, Cd: wave-uniform)
+  const int a = vt - ch * nA;
+  if (ch >= Cd) return;
+  const int lm = S.lm, m = 1 << lm;
+  const int Z = Zs[a];
+  const int k0 = ((Z + ai0[a]) >> lm) << lm;  // the range starts on a piece boundary
+  const int kend = Z + S.nG - 1;              // the grid's last node
+  int per = hs_div_small(kend - k0 + Cd, Cd, __builtin_amdgcn_rcpf((float)Cd));  // nodes k0 .. kend over Cd chunks ...
+  per = ((per + m - 1) >> lm) << lm;          // ... of whole pieces
+  part_s[ch * nEs + a] = hs_syn2_chunk(a, Z, k0 + ch * per, per, kend, nEs, S, sq, a_lw, a_ig, a_tab, a_t128);
+}
+// (a chunk count per energy, every lane of the planned items used: the resident loop -- hs_s2_spread)
+__device__ HS_S2_INLINE void hs_syn2_item_spread(int ix, int lane, int nA, hs_s2_lanes L, int nEs,
+                                                    const hs_syn2_par& S, const int* ai0, const int* Zs,
+                                                    const double* sq, unsigned a_lw, unsigned a_ig,
+                                                    unsigned a_tab, unsigned a_t128, double* part_s) {
+  int a, ch, cda;
+  if (!hs_s2_lane_of(L, nA, ix * 64 + lane, a, ch, cda)) return;
+  const int lm = S.lm;
+  const int Z = Zs[a];
+  const int k0 = ((Z + ai0[a]) >> lm) << lm;  // the range starts on a piece boundary
+  const int kend = Z + S.nG - 1;              // the grid's last node
+  const int per = hs_s2_chunk_nodes(k0, kend, cda, lm);  // nodes k0 .. kend over the energy's chunks of whole pieces
+  part_s[ch * nEs + a] = hs_syn2_chunk(a, Z, k0 + ch * per, per, kend, nEs, S, sq, a_lw, a_ig, a_tab, a_t128);
 }
 
 // ---- the faint head of a live range (resident loop) ----------------------------------------------
