@@ -106,8 +106,24 @@ class nh_hs_desc(C.Structure):
                 ("blobs", nh_hs_blob * 4), ("nblobs", C.c_int), ("send_width", C.c_int)]
 
 
+# __array_priority__ of every device-resident class (above Quantity's and Unit's, so that
+# ndarray, Quantity and Unit operators defer to them); is_device() is the one test for it
+DEVICE_PRIORITY = 30000
+
+
+def is_device(x):
+    """True for a device-resident lazy value (DVec, DMat, DFactor, LazyPrior) and for the
+    parameter block they come from (DPars)"""
+    return getattr(x, "__array_priority__", 0) == DEVICE_PRIORITY or isinstance(x, DPars)
+
+
 def lazy_const(v):
     return nh_lazy(None, 0, float(v), 0.0, 0.0, TF_ID, 0)
+
+
+def as_lazy(v):
+    """the kernel argument of a number or a DVec"""
+    return v.lazy() if isinstance(v, DVec) else lazy_const(v)
 
 
 def _defer(x):
@@ -123,7 +139,7 @@ def _is_number(x):
 
 class DVec:
     """lazy per-walker scalar on the device (see module docstring)"""
-    __array_priority__ = 30000
+    __array_priority__ = DEVICE_PRIORITY
     ndim = 1
 
     def __init__(self, ctx, owner, ptr, n, stride=1, a=1.0, b=1.0, c=0.0, tf=TF_ID):
@@ -343,7 +359,7 @@ class DPars:
 
 class DMat:
     """lazy (N, m) device matrix: colfac[k] * sum_j scale_j * buf_j[w*ld_j + k]"""
-    __array_priority__ = 30000
+    __array_priority__ = DEVICE_PRIORITY
     __array_ufunc__ = None
     ndim = 2
 
@@ -496,7 +512,7 @@ class DFactor:
     """a lazy (N, nE) per-walker, per-energy factor of a device flux (an absorption): a subclass
     gives ``apply(m)`` -- the ``DMat`` of factor * m, or of the factor itself without m, in one
     launch that also forms m's linear combination -- and ``shape``"""
-    __array_priority__ = 30000
+    __array_priority__ = DEVICE_PRIORITY
     __array_ufunc__ = None
     ndim = 2
 
@@ -575,10 +591,6 @@ class DPairAbs(DFactor):
         self.ctx, self.fields, self.tau = ctx, list(fields), bool(tau)
         self.shape = (int(N), int(nE))
 
-    @staticmethod
-    def _lazy(v):
-        return v.lazy() if isinstance(v, DVec) else lazy_const(v)
-
     def apply(self, m=None):
         N, nE = self.shape
         if self.tau and m is not None:
@@ -586,8 +598,8 @@ class DPairAbs(DFactor):
         comps, ncomp, cf = self._terms_of(m)
         arr = (nh_pair_field * max(len(self.fields), 1))()
         for j, (kappa, per_walker, L, dens, T) in enumerate(self.fields):
-            arr[j] = nh_pair_field(kappa.ptr, nE if per_walker else 0, self._lazy(L),
-                                   self._lazy(dens), self._lazy(T if T is not None else 0.0),
+            arr[j] = nh_pair_field(kappa.ptr, nE if per_walker else 0, as_lazy(L),
+                                   as_lazy(dens), as_lazy(T if T is not None else 0.0),
                                    int(T is not None), 0)
         out = self.ctx.empty((N, nE))
         self.ctx.call("nh_pairabs_apply", arr, len(self.fields), comps, ncomp, cf,
@@ -597,7 +609,7 @@ class DPairAbs(DFactor):
 
 class LazyPrior:
     """sum of prior terms on device scalars, evaluated by nh_priors"""
-    __array_priority__ = 30000
+    __array_priority__ = DEVICE_PRIORITY
     __array_ufunc__ = None
 
     def __init__(self, ctx, n, terms=(), const=0.0):
@@ -651,7 +663,3 @@ class LazyPrior:
             self.ctx.call("nh_priors", arr, len(chunk), self.n, nxt)
             out = nxt
         return DVec(self.ctx, out, out.ptr, self.n)
-
-
-def is_device(x):
-    return isinstance(x, (DVec, DMat, DPars, LazyPrior, DFactor))

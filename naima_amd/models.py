@@ -10,7 +10,9 @@ classes evaluate all of them in one batched HIP launch.  Evaluation itself
 import numpy as np
 
 from . import units as u
+from . import walker_value as wv
 from ._lib import NH_PD_NPAR, PD_KIND, get_context
+from .darray import DVec, lazy_const, nh_lazy
 from .constants import AR_CGS, C_CGS, ERG_TO_EV, HBAR_CGS, MEC2_ERG, MEC2_EV, R0_CM
 from .validator import validate_physical_type, validate_scalar_or_batch
 
@@ -45,38 +47,30 @@ class _ParticleDistribution:
         self.__dict__.pop("_slot7_packed", None)
         object.__setattr__(self, name, value)
 
+    def _own_values(self):
+        """every value that may be given per walker (walker_value)"""
+        return [getattr(self, name) for name in self.param_names]
+
     @property
     def batch_size(self):
         """number of walkers this distribution describes (1 if all parameters are scalars)"""
-        n = 1
-        for name in self.param_names:
-            v = getattr(self, name)
-            v = v.value if isinstance(v, u.Quantity) else v
-            if np.ndim(v) > 0:
-                m = np.shape(v)[0]
-                if n != 1 and m != 1 and m != n:
-                    raise ValueError("inconsistent walker-batch sizes in %s: %d vs %d"
-                                     % (type(self).__name__, n, m))
-                n = max(n, m)
-        return n
+        return wv.merge(wv.counts(self._own_values()), type(self).__name__)
 
     @property
     def is_batched(self):
-        for name in self.param_names:
-            v = getattr(self, name)
-            v = v.value if isinstance(v, u.Quantity) else v
-            if np.ndim(v) > 0:
-                return True
-        return False
+        return wv.is_batched(self._own_values())
+
+    @property
+    def on_device(self):
+        return wv.on_device(self._own_values())
 
     def _amplitude_unit(self):
         a = self.amplitude
         return a.unit if isinstance(a, u.Quantity) else u.dimensionless_unscaled
 
-    def param_rows(self, N, amplitude_to=None):
-        """[N, NH_PD_NPAR] float64 rows (include/naima_hip.h); amplitude converted to
-        ``amplitude_to`` (e.g. 1/eV) when given, energies in eV."""
-        rows = np.zeros((N, NH_PD_NPAR))
+    def _slot_values(self, amplitude_to):
+        """(name, slot, bare value in the row's units) of every parameter: the amplitude in
+        ``amplitude_to`` when that is given, energies in eV, the rest dimensionless"""
         for name, slot, is_energy in self._slots:
             v = getattr(self, name)
             if name == "amplitude":
@@ -86,6 +80,13 @@ class _ParticleDistribution:
                 v = v.to("eV").value
             elif isinstance(v, u.Quantity):
                 v = v.to(u.dimensionless_unscaled).value
+            yield name, slot, v
+
+    def param_rows(self, N, amplitude_to=None):
+        """[N, NH_PD_NPAR] float64 rows (include/naima_hip.h); amplitude converted to
+        ``amplitude_to`` (e.g. 1/eV) when given, energies in eV."""
+        rows = np.zeros((N, NH_PD_NPAR))
+        for name, slot, v in self._slot_values(amplitude_to):
             rows[:, slot] = np.asarray(v, dtype=float)
         if not any(s[0] == "beta" for s in self._slots):
             rows[:, 4] = 1.0
@@ -94,7 +95,6 @@ class _ParticleDistribution:
     def device_rows(self, ctx, N, amplitude_to=None):
         """the [N][NH_PD_NPAR] parameter rows in HBM, packed by ``nh_pack_rows`` from
         host scalars, host vectors or lazy device scalars (no host round trip)"""
-        from .darray import DVec, lazy_const, nh_lazy
         cache = self.__dict__.setdefault("_rows_dev", {})
         key = (N, None if amplitude_to is None else amplitude_to.name)
         hit = cache.get(key)
@@ -111,38 +111,14 @@ class _ParticleDistribution:
             cols[7] = rider.lazy()
             keep.append(rider)
             self.__dict__["_slot7_packed"] = rider
-        for name, slot, is_energy in self._slots:
-            v = getattr(self, name)
-            if name == "amplitude":
-                if isinstance(v, u.Quantity):
-                    v = v.to(amplitude_to).value if amplitude_to is not None else v.value
-            elif is_energy:
-                v = v.to("eV").value
-            elif isinstance(v, u.Quantity):
-                v = v.to(u.dimensionless_unscaled).value
-            if isinstance(v, DVec):
-                if v.n != N:
-                    raise ValueError("parameter %s has %d walkers, batch has %d" % (name, v.n, N))
-                cols[slot] = v.lazy()
-                keep.append(v)
-            elif np.ndim(v) == 0:
-                cols[slot] = lazy_const(v)
-            else:
-                dev = ctx.array(np.broadcast_to(np.asarray(v, dtype=float), (N,)))
-                cols[slot] = nh_lazy(dev.ptr, 1, 1.0, 1.0, 0.0, 0, 0)
-                keep.append(dev)
+        for name, slot, v in self._slot_values(amplitude_to):
+            cols[slot], k = wv.lazy(ctx, v, N=N, mismatch="parameter " + name
+                                    + " has %d walkers, batch has %d")
+            if k is not None:
+                keep.append(k)
         out = ctx.pack_rows(cols, NH_PD_NPAR, N)
         cache[key] = out
         return out
-
-    @property
-    def on_device(self):
-        for name in self.param_names:
-            v = getattr(self, name)
-            v = v.value if isinstance(v, u.Quantity) else v
-            if getattr(v, "__array_priority__", 0) == 30000:
-                return True
-        return False
 
     def __call__(self, e):
         """dN/dE at energies ``e`` -- shape (n_e,) or (N, n_e) for a walker batch.
@@ -292,16 +268,15 @@ class TableModel:
 
     @property
     def on_device(self):
-        return getattr(self._amp, "__array_priority__", 0) == 30000
+        return wv.classify(self._amp)[0] is wv.DEVICE
 
     @property
     def batch_size(self):
-        a = self._amp
-        return int(np.shape(a)[0]) if np.ndim(a) > 0 else 1
+        return int(wv.classify(self._amp)[1])
 
     @property
     def is_batched(self):
-        return np.ndim(self._amp) > 0
+        return wv.per_walker(self._amp)
 
     def __call__(self, e):
         e = _validate_ene(e)
@@ -378,13 +353,6 @@ def _ebl_table(ctx, x, code, kind):
     return ctx.table(("ebl", kind, xd.ptr, cd.ptr), build)
 
 
-def _per_walker(redshift):
-    from .darray import DVec
-    v = redshift.value if isinstance(redshift, u.Quantity) else redshift
-    return isinstance(v, DVec) or (getattr(v, "__array_priority__", 0) != 30000
-                                   and np.ndim(v) == 1)
-
-
 class EblAbsorptionModel(TableModel):
     """Opacity of the extragalactic background light (Dominguez et al. 2011) at a given
     redshift as a TableModel; ``transmission(e)`` is the factor to multiply a flux with
@@ -406,7 +374,7 @@ class EblAbsorptionModel(TableModel):
         import os
 
         from .validator import validate_scalar
-        if _per_walker(redshift):
+        if wv.is_vector(redshift):  # one redshift per walker: 1-D host array or DVec
             self._init_batch(redshift, ebl_absorption_model)
             return
         if not isinstance(redshift, u.Quantity):
@@ -491,24 +459,6 @@ class EblAbsorptionModel(TableModel):
 
 # k_B / (m_e c^2) per kelvin, from the radiation constant a = pi^2 k_B^4 / (15 (hbar c)^3)
 _K_TO_MEC2 = (15.0 * AR_CGS * (HBAR_CGS * C_CGS) ** 3 / np.pi ** 2) ** 0.25 / MEC2_ERG
-
-
-def _pa_value(ctx, q, unit):
-    """the value of a Quantity in ``unit``: a float, or a DVec.  A 1-D host array is uploaded
-    as it was given and converted as a device value is, lazily, so that a host batch and the
-    same numbers held on the device give the same bits."""
-    from .darray import DVec
-    v = q.value
-    if not isinstance(v, DVec):
-        v = np.asarray(v, dtype=float)
-        if v.ndim > 1 or (v.ndim == 1 and v.size == 0):
-            raise TypeError("a per-walker value must be a non-empty 1-D array, got shape %r"
-                            % (v.shape,))
-        if v.size == 1:  # (a scalar, or a batch of one walker)
-            return float(np.ravel(q.to(unit).value)[0])
-        d = ctx.array(v)
-        v = DVec(ctx, d, d.ptr, v.shape[0])
-    return u.Quantity(v, q.unit).to(unit).value
 
 
 _pa_rows = {}  # the (n_e,) rows of scalar models, by content (PairAbsorptionModel._result)
@@ -598,7 +548,7 @@ class PairAbsorptionModel:
                     % (s[0], s[0]))
 
     # -- what is given per walker ----------------------------------------------------------
-    def _given(self):
+    def _own_values(self):
         """every Quantity that may be given per walker"""
         qs = list(self.path_length)
         for seed in self.seed_photon_fields.values():
@@ -612,20 +562,16 @@ class PairAbsorptionModel:
 
     @property
     def on_device(self):
-        return any(q.on_device for q in self._given())
+        return wv.on_device(self._own_values())
 
     @property
     def batch_size(self):
-        """walkers of the batch (None: scalars everywhere)"""
-        n = None
-        for q in self._given():
-            k = np.shape(q.value)[0] if np.ndim(q.value) == 1 and np.size(q.value) > 1 else (
-                q.value.n if q.on_device else None)
-            if k is not None:
-                if n is not None and k != n:
-                    raise ValueError("inconsistent walker-batch sizes: %d vs %d" % (n, k))
-                n = k
-        return n
+        """walkers of the batch (None: scalars everywhere).  A host array of one element is a
+        scalar here, and every other count has to agree, a device value of one walker too"""
+        def count(q):
+            form, n = wv.classify(q)
+            return n if form is wv.DEVICE or (wv.is_vector(q) and n > 1) else None
+        return wv.merge([count(q) for q in self._own_values()], broadcast_one=False)
 
     def _values(self, ctx):
         """per field: (seed, L [cm], dens, T [K] or None, theta [rad] or None) as floats or
@@ -633,16 +579,16 @@ class PairAbsorptionModel:
         1 for a tabulated one"""
         out = []
         for (name, seed), L in zip(self.seed_photon_fields.items(), self.path_length):
-            Lv = _pa_value(ctx, L, "cm")
-            th = None if seed["isotropic"] else _pa_value(ctx, seed["theta"], "rad")
+            Lv = wv.resolve(ctx, L, "cm", fold=True)
+            th = None if seed["isotropic"] else wv.resolve(ctx, seed["theta"], "rad", fold=True)
             if seed["type"] == "thermal":
-                out.append((seed, Lv, _pa_value(ctx, seed["u"], "erg/cm3"),
-                            _pa_value(ctx, seed["T"], "K"), th))
+                out.append((seed, Lv, wv.resolve(ctx, seed["u"], "erg/cm3", fold=True),
+                            wv.resolve(ctx, seed["T"], "K", fold=True), th))
             elif seed["energy"].size == 1:
                 d = seed["photon_density"]
                 if not d.on_device and np.size(d.value) == 1:
                     d = u.Quantity(float(np.ravel(d.value)[0]), d.unit)
-                out.append((seed, Lv, _pa_value(ctx, d, "eV/cm3")
+                out.append((seed, Lv, wv.resolve(ctx, d, "eV/cm3", fold=True)
                             / float(seed["energy"].to("eV").value[0]), None, th))
             else:
                 out.append((seed, Lv, 1.0, None, th))
@@ -656,9 +602,9 @@ class PairAbsorptionModel:
         import ctypes as C
 
         from . import _lib
-        from .darray import DPairAbs
-        lT = DPairAbs._lazy(T if T is not None else 0.0)
-        lth = DPairAbs._lazy(theta) if theta is not None else None
+        from .darray import as_lazy
+        lT = as_lazy(T if T is not None else 0.0)
+        lth = as_lazy(theta) if theta is not None else None
         args = (kind, _K_TO_MEC2, C.byref(lT), C.byref(lth) if lth is not None else None,
                 se.ptr if se is not None else None, sn.ptr if sn is not None else None, ns,
                 xd.ptr, nE, nrows, out.ptr, nE)
@@ -816,7 +762,7 @@ class CooledElectrons:
 
     def __init__(self, injection, B, age, seed_photon_fields=("CMB",), Emin=1 * u.GeV,
                  Emax=510.998 * u.TeV, n_per_decade=100):
-        from .radiative import InverseCompton, _log_grid, _per_walker as _pw
+        from .radiative import InverseCompton, _log_grid
         from .validator import validate_scalar
         validate_physical_type("B", B, "magnetic flux density")
         validate_physical_type("age", age, "time")
@@ -837,7 +783,7 @@ class CooledElectrons:
         if len(seeds) > 8:
             raise ValueError("at most 8 photon fields, got %d" % len(seeds))
         for name, seed in seeds.items():
-            if _pw(seed["T"]):
+            if wv.per_walker(seed["T"]):
                 raise NotImplementedError(
                     "%s-T must be the same for every walker of a batch (the loss table is "
                     "shared); evaluate walkers with different %s-T in separate calls"
@@ -901,7 +847,7 @@ class CooledElectrons:
         object.__setattr__(self, name, value)
 
     # -- what is given per walker ------------------------------------------------------------
-    def _given(self):
+    def _own_values(self):
         return [self.B, self.age] + [s["u"] for s in self.seed_photon_fields.values()]
 
     def _rates(self):
@@ -914,37 +860,24 @@ class CooledElectrons:
 
     @property
     def on_device(self):
-        if any(q.on_device for q in self._given()):
+        if wv.on_device(self._own_values()):
             return True
         if self._inj == "rows":
             return self._rates().on_device
         return bool(getattr(self.injection, "on_device", False))
 
-    def _sizes(self):
-        out = []
-        for q in self._given():
-            v = q.value
-            out.append(v.n if q.on_device else (np.shape(v)[0] if np.ndim(v) > 0 else 1))
-        if self._inj == "rows":
-            sh = tuple(self._rates().value.shape)
-            out.append(sh[0] if len(sh) == 2 else 1)
-        else:
-            out.append(self.injection.batch_size)
-        return out
-
     @property
     def batch_size(self):
-        n = 1
-        for m in self._sizes():
-            if n != 1 and m != 1 and m != n:
-                raise ValueError("inconsistent walker-batch sizes in CooledElectrons: %d vs %d"
-                                 % (n, m))
-            n = max(n, m)
-        return n
+        if self._inj == "rows":  # (rates of shape (N, nC): the walkers on the leading axis)
+            sh = tuple(self._rates().value.shape)
+            inj = sh[0] if len(sh) == 2 else 1
+        else:
+            inj = self.injection.batch_size
+        return wv.merge(wv.counts(self._own_values()) + [inj], "CooledElectrons")
 
     @property
     def is_batched(self):
-        if any(q.on_device or np.ndim(q.value) > 0 for q in self._given()):
+        if wv.is_batched(self._own_values()):
             return True
         if self._inj == "rows":
             return len(tuple(self._rates().value.shape)) == 2
@@ -953,7 +886,7 @@ class CooledElectrons:
     def _walker(self, k):
         """this model for walker k alone (host values)"""
         def one(q):
-            return q[k] if np.ndim(q.value) > 0 else q
+            return q[k] if wv.per_walker(q) else q
         inj = self.injection
         if self._inj == "rows":
             r = self._rates()
@@ -1042,7 +975,7 @@ class CooledElectrons:
         """n[N][nC] (1/eV) in HBM: one nh_cooled_electrons launch per parameter state"""
         import ctypes as C
 
-        from .darray import DVec, lazy_const, nh_lazy
+        from .darray import nh_lazy
         N = self.batch_size if N is None else N
         cache = self.__dict__.setdefault("_solved", {})
         hit = cache.get(N)
@@ -1050,23 +983,15 @@ class CooledElectrons:
             return hit
         nC = self._e.size
         ed = ctx.const(self._e)
-        keep = []
-
-        def lazy_of(q, unit):
-            v = _pa_value(ctx, q, unit)
-            if isinstance(v, DVec):
-                if v.n != N:
-                    raise ValueError("a per-walker value has %d walkers, the batch has %d"
-                                     % (v.n, N))
-                keep.append(v)
-                return v.lazy()
-            return lazy_const(v)
-
-        Bl, agel = lazy_of(self.B, "G"), lazy_of(self.age, "s")
         seeds = list(self.seed_photon_fields.values())
-        ul = (nh_lazy * max(len(seeds), 1))()
+        # (uploaded as given, the unit folded in: a host batch gives a device batch's bits)
+        args = dict(N=N, fold=True, mismatch="a per-walker value has %d walkers, the batch has %d")
+        Bl, keep_B = wv.lazy(ctx, self.B, "G", **args)
+        agel, keep_age = wv.lazy(ctx, self.age, "s", **args)
+        ul, keep_u = (nh_lazy * max(len(seeds), 1))(), []
         for f, s in enumerate(seeds):
-            ul[f] = lazy_of(s["u"], "erg/cm3")
+            ul[f], k = wv.lazy(ctx, s["u"], "erg/cm3", **args)
+            keep_u.append(k)
         loss = self._loss_table(ctx, ed)
         own, qptr, ldq, nrows = self._injection_rows(ctx, ed)
         if ldq and nrows != N:
@@ -1075,7 +1000,7 @@ class CooledElectrons:
         ctx.call("nh_cooled_electrons", qptr, ldq, N, ed, nC, C.addressof(Bl),
                  loss.ptr if loss is not None else None, len(seeds), ul, C.addressof(agel), out,
                  cool_status(ctx))
-        del own, keep
+        del own, keep_B, keep_age, keep_u
         cache[N] = out
         return out
 

@@ -15,6 +15,7 @@ Grids are generated on the host with the reference's exact expressions
 (radiative.py:147-154, 1002-1009); everything else is in libnaima_hip.so.
 There is no NumPy evaluation path.
 """
+import ctypes as C
 import logging
 import os
 from collections import OrderedDict
@@ -22,14 +23,15 @@ from collections import OrderedDict
 import numpy as np
 
 from . import units as u
+from . import walker_value as wv
 from . import _lib as _lib_mod
 from ._lib import PD_KIND, PP_MODEL, get_context
-from .darray import DMat, DVec
+from .darray import DMat, DVec, lazy_const, nh_lazy
 from .constants import (AR_CGS, ASTROPY_TO_ERG, ASTROPY_TO_GEV, C_CGS, ERG_TO_EV, MEC2_ERG,
                         MEC2_EV, M_P_GEV, T_TH_GEV, energy_ratio_to, mec2, mec2_unit)
 from .models import _validate_ene
 from .validator import (validate_array, validate_physical_type, validate_scalar,
-                        validate_scalar_or_batch)
+                        validate_scalar_or_batch, validate_scalar_or_per_walker)
 
 __all__ = ["Synchrotron", "InverseCompton", "PionDecay", "Bremsstrahlung"]
 
@@ -37,43 +39,6 @@ log = logging.getLogger("naima_amd.radiative")
 
 _PER_EV = u.Unit("1/eV")
 _SPEC_UNIT = u.Unit("1/(s eV)")
-
-
-def _batch_of(x):
-    v = x.value if isinstance(x, u.Quantity) else x
-    return np.shape(v)[0] if np.ndim(v) > 0 else 1
-
-
-def _is_batched(x):
-    v = x.value if isinstance(x, u.Quantity) else x
-    return np.ndim(v) > 0
-
-
-def _is_dev(x):
-    v = x.value if isinstance(x, u.Quantity) else x
-    return getattr(v, "__array_priority__", 0) == 30000
-
-
-def _per_walker(x):
-    """True for a parameter given per walker: host vector or device value"""
-    return _is_batched(x) or _is_dev(x)
-
-
-def _as_dvec(ctx, rows, N):
-    if isinstance(rows, DVec):
-        return rows
-    buf = ctx.array(np.broadcast_to(np.asarray(rows, dtype=float), (N,)))
-    return DVec(ctx, buf, buf.ptr, N)
-
-
-def _merge_batch(*sizes):
-    n = 1
-    for s in sizes:
-        if s != 1:
-            if n != 1 and s != n:
-                raise ValueError("inconsistent walker-batch sizes: %d vs %d" % (n, s))
-            n = s
-    return n
 
 
 class BaseRadiative:
@@ -91,19 +56,23 @@ class BaseRadiative:
                                    physical_type="differential energy")
 
     # -- batching -------------------------------------------------------------
-    def _own_batch_sizes(self):
+    def _own_values(self):
+        """the class's own quantities that may be given per walker (walker_value); the
+        particle distribution and the structural values are counted beside them"""
         return ()
+
+    def _walker_values(self):
+        return list(self._own_values()) + [v for _, v in self._structural_values()]
 
     @property
     def batch_size(self):
-        return _merge_batch(getattr(self.particle_distribution, "batch_size", 1),
-                            *(self._own_batch_sizes() + self._structural_batch()))
+        return wv.merge([getattr(self.particle_distribution, "batch_size", 1)]
+                        + wv.counts(self._walker_values()))
 
     @property
     def is_batched(self):
         return bool(getattr(self.particle_distribution, "is_batched", False)) or any(
-            s != 1 for s in self._own_batch_sizes() + self._structural_batch()) \
-            or self._own_batched()
+            c != 1 for c in wv.counts(self._walker_values())) or self._own_batched()
 
     def _own_batched(self):
         return False
@@ -120,17 +89,15 @@ class BaseRadiative:
 
     def _needs_walker_loop(self):
         for n, v in self._structural_values():
-            if _is_dev(v):
+            form = wv.classify(v)[0]
+            if form is wv.DEVICE:
                 raise NotImplementedError(
                     "%s is a device-resident per-walker value: the particle grid / emission "
                     "tables would differ per walker.  Run the sampler with device=False (host "
                     "loop), which evaluates such walkers one by one" % n)
-            if _is_batched(v):
+            if form is wv.HOST:
                 return True
         return False
-
-    def _structural_batch(self):
-        return tuple(_batch_of(v) for _, v in self._structural_values())
 
     def _walker(self, k):
         """this model for walker k alone (scalars everywhere)"""
@@ -149,13 +116,13 @@ class BaseRadiative:
                            if not a.startswith("_")}
             for name in getattr(pd, "param_names", ()):
                 v = getattr(pd, name)
-                if _is_batched(v):
+                if wv.per_walker(v):
                     setattr(pd, name, v[k])
         one.particle_distribution = pd
         for name in tuple(self._structural) + tuple(self._walker_scalars):
             if hasattr(self, name):
                 v = getattr(self, name)
-                if _is_batched(v):
+                if wv.per_walker(v):
                     one.__dict__[name] = v[k]
         return one
 
@@ -178,37 +145,36 @@ class BaseRadiative:
             host = host[0]
         return host
 
-    def _own_device_values(self):
-        return ()
-
     @property
     def on_device(self):
         """True when a parameter is a device-resident value: results then stay in HBM
         as lazy ``DMat``/``DVec`` (no synchronising download)"""
-        if getattr(self.particle_distribution, "on_device", False):
-            return True
-        for v in self._own_device_values():
-            v = v.value if isinstance(v, u.Quantity) else v
-            if getattr(v, "__array_priority__", 0) == 30000:
-                return True
-        return False
+        return bool(getattr(self.particle_distribution, "on_device", False)) \
+            or wv.on_device(self._own_values())
 
-    def _result(self, ctx, out, N, nE, E, scale=1.0, rows=None):
+    def _result(self, ctx, out, N, nE, E, factor=1.0):
         """spectra [N][nE] in a device buffer -> Quantity 1/(s eV) (lazy on device, or
-        downloaded with the reference's shape).  ``rows``: per-walker factor (host
-        vector or device scalar per walker) for physical parameters that the reference
-        applies as one scalar and that may be fit parameters here (n0, nh, seed u)."""
+        downloaded with the reference's shape), times ``factor``"""
+        spec = DMat.from_buffer(ctx, out, N, nE) if self.on_device else out.get()
+        return self._times(ctx, spec, N, E, factor)
+
+    def _times(self, ctx, spec, N, E, factor):
+        """spectra (a lazy DMat on the device, an (N, nE) ndarray on the host) times
+        ``factor`` -> Quantity 1/(s eV).  The factor is one scale, or one value per walker
+        (host vector or device value) for physical parameters that the reference applies as
+        one scalar and that may be fit parameters here (n0, nh, seed u)."""
+        rows = wv.per_walker(factor)
         if self.on_device:
-            m = DMat.from_buffer(ctx, out, N, nE, scale=scale)
-            if rows is not None:
-                m = m * _as_dvec(ctx, rows, N)
-            return u.Quantity(m, _SPEC_UNIT)
-        host = out.get()
-        if scale != 1.0:
-            host = host * scale
-        if rows is not None:
-            host = host * np.broadcast_to(np.asarray(rows, dtype=float), (N,))[:, None]
-        return u.Quantity(self._finish(host, E), _SPEC_UNIT)
+            if rows:
+                spec = spec * wv.resolve(ctx, factor, N=N)
+            elif factor != 1.0:
+                spec = spec * float(factor)
+            return u.Quantity(spec, _SPEC_UNIT)
+        if rows:
+            spec = spec * np.broadcast_to(np.asarray(factor, dtype=float), (N,))[:, None]
+        elif factor != 1.0:
+            spec = spec * factor
+        return u.Quantity(self._finish(spec, E), _SPEC_UNIT)
 
     def _weights(self, xg, e_eV, unit_scale):
         """device weights w = xg*n and log-ratios lw[i] = ln|w[i+1]/w[i]| of every walker.
@@ -267,9 +233,7 @@ class BaseRadiative:
     def _weights_table(self, pd, xg, e_eV, unit_scale):
         """weights of a TableModel distribution: amplitude[w] times a walker-independent
         shape on the grid (host spline once, cached in HBM); rows by nh_lincomb"""
-        import ctypes as C
-
-        from .darray import lazy_const, nh_comp
+        from .darray import nh_comp
         ctx = get_context()
         N = pd.batch_size
         nG = xg.size
@@ -376,7 +340,7 @@ def _to_GeV(q):
 
 
 def _scalar_energy(name, q):
-    if _is_batched(q):
+    if wv.per_walker(q):
         raise NotImplementedError(
             "%s must be the same for every walker of a batch (the particle grid is shared); "
             "evaluate walkers with different %s in separate calls" % (name, name))
@@ -413,7 +377,7 @@ class BaseElectron(BaseRadiative):
         """True when Eemin, Eemax or nEed is given per walker (host vector or device value):
         every walker then has its own grid (limits AND node count, radiative.py:147-154) and
         the spectrum comes from nh_general_electron"""
-        return _per_walker(self.Eemin) or _per_walker(self.Eemax) or _per_walker(self.nEed)
+        return wv.per_walker(self.Eemin) or wv.per_walker(self.Eemax) or wv.per_walker(self.nEed)
 
     def _general_supported(self):
         return False
@@ -434,7 +398,7 @@ class BaseElectron(BaseRadiative):
             others = [(n, v) for n, v in self._structural_values()
                       if n not in self._general_names and not n.endswith(("-T", "-theta"))]
             for n, v in others:
-                if _per_walker(v):
+                if wv.per_walker(v):
                     return super()._needs_walker_loop()
             return False
         return super()._needs_walker_loop()
@@ -445,58 +409,37 @@ class BaseElectron(BaseRadiative):
         each walker's grid between Eemin and Eemax (default: the object's own limits), [N][1];
         what = 4: InverseCompton on the shared monochromatic / tabulated seed
         ``seed_arrays = (energies [eV], densities)`` (nh_general_electron_seed)"""
-        import ctypes as C
-
-        from .darray import lazy_const
         ctx = get_context()
         pd = self.particle_distribution
         if not hasattr(pd, "device_rows"):
             raise NotImplementedError("per-walker Eemin / Eemax need a naima_amd.models "
                                       "particle distribution with analytic parameters")
         N = self.batch_size
-
-        def lazy_of(q, unit):
-            v = q.to(unit).value
-            if isinstance(v, DVec):
-                return v.lazy(), v
-            if np.ndim(v) > 0:
-                d = _as_dvec(ctx, v, N)
-                return d.lazy(), d
-            return lazy_const(float(v)), None
-
         # the limits travel in their own unit, with that unit in erg beside them: the kernel forms
         # (value / mec2[erg]) * unit_erg exactly as _gam_between does
         qmin = self.Eemin if Eemin is None else Eemin
         qmax = self.Eemax if Eemax is None else Eemax
-        emin, k1 = lazy_of(qmin, qmin.unit)
-        emax, k2 = lazy_of(qmax, qmax.unit)
-        nv = self.nEed.value if isinstance(self.nEed, u.Quantity) else self.nEed
-        if isinstance(nv, DVec):
-            ned, k4 = nv.lazy(), nv
-        elif np.ndim(nv) > 0:
-            k4 = _as_dvec(ctx, np.asarray(nv, dtype=float), N)
-            ned = k4.lazy()
-        else:
-            ned, k4 = lazy_const(float(nv)), None
+        emin, k1 = wv.lazy(ctx, qmin, N=N)
+        emax, k2 = wv.lazy(ctx, qmax, N=N)
+        ned, k4 = wv.lazy(ctx, self.nEed, N=N)
         rows = pd.device_rows(ctx, N, amplitude_to=_PER_EV)
         nE = 1 if what == 2 else E_eV.size
         ncomp = len(seeds) if what == 1 else (2 if what == 3 else 1)
         out = ctx.empty((N, ncomp * nE))
         status = ctx.general_status()
-        Bl, k3 = (lazy_of(B, "G") if what == 0 else (None, None))
-        from .darray import nh_lazy
+        Bl, k3 = (wv.lazy(ctx, B, "G", N) if what == 0 else (None, None))
         T = (nh_lazy * max(ncomp, 1))()
         th = (nh_lazy * max(ncomp, 1))()
         keep = []
         iso_mask = 0  # (isotropy is a flag: an angle may have any sign, radiative.py:597)
         for j, (Tq, thq) in enumerate(seeds):
-            T[j], k = lazy_of(Tq, "K")
+            T[j], k = wv.lazy(ctx, Tq, "K", N)
             keep.append(k)
             if thq is None:
                 th[j] = lazy_const(0.0)
                 iso_mask |= 1 << j
             else:
-                th[j], k = lazy_of(thq, "rad")
+                th[j], k = wv.lazy(ctx, thq, "rad", N)
                 keep.append(k)
         if what == 4 and seed_rows:
             se, sd = seed_arrays
@@ -563,14 +506,14 @@ class BaseElectron(BaseRadiative):
         if not hasattr(self.particle_distribution, "device_rows"):
             return False
         for q in (lo, hi, self.nEed):  # (a per-walker value has to match the object's own batch)
-            v = q.value if isinstance(q, u.Quantity) else q
+            v = wv.raw(q)
             if not isinstance(v, DVec) and np.ndim(v) > 0 and \
                     not (self.is_batched and len(v) == self.batch_size):
                 return False
         return True
 
     def _We_between(self, lo, hi, what, **kw):
-        if _per_walker(lo) or _per_walker(hi) or _per_walker(self.nEed):
+        if wv.per_walker(lo) or wv.per_walker(hi) or wv.per_walker(self.nEed):
             if self._We_general_ok(lo, hi):
                 return self._We_general(lo, hi)
             return self._loop_walkers(what, **kw)  # (one walker at a time: host values only)
@@ -641,10 +584,7 @@ class Synchrotron(BaseElectron):
                 and not pd.__dict__.get("_rows_dev"):
             pd.__dict__["_slot7"] = Bv
 
-    def _own_batch_sizes(self):
-        return (_batch_of(self.B),)
-
-    def _own_device_values(self):
+    def _own_values(self):
         return (self.B,)
 
     def _launch_shared_inputs(self, ctx):
@@ -717,13 +657,13 @@ class InverseCompton(BaseElectron):
         """a thermal seed whose temperature or angle is given per walker: its Khangulyan kernel
         differs from walker to walker, no table can be shared (radiative.py:547-607)"""
         for seed in self.seed_photon_fields.values():
-            if seed["type"] == "thermal" and (_per_walker(seed["T"]) or (
-                    not seed["isotropic"] and _per_walker(seed["theta"]))):
+            if seed["type"] == "thermal" and (wv.per_walker(seed["T"]) or (
+                    not seed["isotropic"] and wv.per_walker(seed["theta"]))):
                 return True
         return False
 
     def _general_needed(self):
-        if _per_walker(self.nEed):
+        if wv.per_walker(self.nEed):
             return False
         return self._general_limits() or (self._seed_shape_per_walker()
                                           and self._general_supported())
@@ -772,7 +712,7 @@ class InverseCompton(BaseElectron):
             colfac = Eph / E_eV
             if dev:
                 m = DMat(ctx, [(out, out.ptr + 8 * j * nE, len(names) * nE, 1.0)], (N, nE)) * colfac
-                m = m * _as_dvec(ctx, uf, N) if (_per_walker(sd["u"]) or _per_walker(sd["T"])) \
+                m = m * wv.resolve(ctx, uf, N=N) if (wv.per_walker(sd["u"]) or wv.per_walker(sd["T"])) \
                     else m * float(uf)
                 specs.append(m)
             else:
@@ -806,7 +746,7 @@ class InverseCompton(BaseElectron):
         for name, seed in self.seed_photon_fields.items():
             sd = dict(seed)
             for key in ("T", "u", "theta"):
-                if key in sd and _is_batched(sd[key]):
+                if key in sd and wv.per_walker(sd[key]):
                     sd[key] = sd[key][k]
             if sd["type"] == "array" and np.ndim(sd["photon_density"].value) == 2:
                 sd["photon_density"] = sd["photon_density"][k]
@@ -814,19 +754,20 @@ class InverseCompton(BaseElectron):
         one.__dict__["seed_photon_fields"] = seeds
         return one
 
-    def _own_batch_sizes(self):
-        sizes = []
-        for seed in self.seed_photon_fields.values():
-            if seed["type"] == "array" and np.ndim(seed["photon_density"].value) == 2:
-                sizes.append(seed["photon_density"].shape[0])
-            if seed["type"] == "thermal":
-                sizes.append(_batch_of(seed["u"]))
-        return tuple(sizes)
+    def _own_values(self):
+        """per seed: the energy density of a thermal one, the photon density of an array one
+        where it is (N, n_s) -- the one value that is 2-D, the walkers on its leading axis; a
+        1-D density is shared by every walker"""
+        return [s["u"] if s["type"] == "thermal" else s["photon_density"]
+                for s in self.seed_photon_fields.values()
+                if s["type"] == "thermal" or self._seed_per_walker(s)]
 
-    def _own_device_values(self):
-        return tuple(s["photon_density"] for s in self.seed_photon_fields.values()
-                     if s["type"] == "array") + tuple(
-            s["u"] for s in self.seed_photon_fields.values() if s["type"] == "thermal")
+    @property
+    def on_device(self):
+        # (a shared 1-D density may live on the device too: no walkers of its own to count)
+        return super().on_device or any(
+            s["photon_density"].on_device for s in self.seed_photon_fields.values()
+            if s["type"] == "array")
 
     @staticmethod
     def _process_input_seed(seed_photon_fields):
@@ -863,7 +804,7 @@ class InverseCompton(BaseElectron):
                 else:
                     name, T, uu, theta = inseed
                     seed["isotropic"] = False
-                    if _is_batched(theta):
+                    if wv.per_walker(theta):
                         validate_physical_type("{0}-theta".format(name), theta, "angle")
                         seed["theta"] = theta
                     else:
@@ -872,7 +813,7 @@ class InverseCompton(BaseElectron):
                 thermal = T.unit.physical_type == "temperature"
                 if thermal:
                     seed["type"] = "thermal"
-                    if _is_batched(T):  # one temperature per walker: the general path
+                    if wv.per_walker(T):  # one temperature per walker: the general path
                         validate_physical_type("{0}-T".format(name), T, "temperature")
                     else:
                         validate_scalar("{0}-T".format(name), T, domain="positive",
@@ -880,7 +821,7 @@ class InverseCompton(BaseElectron):
                     seed["T"] = T
                     if not isinstance(uu, u.Quantity) and uu == 0:
                         seed["u"] = ar * T ** 4
-                    elif _per_walker(uu):  # one energy density per walker (fit parameter)
+                    elif wv.per_walker(uu):  # one energy density per walker (fit parameter)
                         validate_physical_type("{0}-u".format(name), uu, "pressure")
                         seed["u"] = uu
                     else:
@@ -973,7 +914,7 @@ class InverseCompton(BaseElectron):
                 if seed["type"] == "thermal":
                     T = seed["T"].to("K").value
                     uf = (seed["u"].to("erg/cm3").value / (AR_CGS * T ** 4))
-                    if _per_walker(seed["u"]):  # energy density as a fit parameter
+                    if wv.per_walker(seed["u"]):  # energy density as a fit parameter
                         rowfac[name], uf = uf, 1.0
                 else:
                     uf = 1.0
@@ -987,7 +928,7 @@ class InverseCompton(BaseElectron):
                     specs[name] = DMat(ctx, [(out, out.ptr + 8 * (h * N * nK + j * nE), nK, 1.0)
                                              for h in range(ns)], (N, nE))
                     if name in rowfac:
-                        specs[name] = specs[name] * _as_dvec(ctx, rowfac[name], N)
+                        specs[name] = specs[name] * wv.resolve(ctx, rowfac[name], N=N)
             else:
                 host = out.get().reshape(ns, N, nK).sum(axis=0)
                 for j, name in enumerate(static):
@@ -1104,28 +1045,16 @@ class Bremsstrahlung(BaseElectron):
         E = _validate_ene(photon_energy)
         E_eV = np.atleast_1d(E.to("eV").value).astype(float)
         nE = E_eV.size
-        rows = None
-        if _per_walker(self.n0):  # the target density is a fit parameter: one factor per walker
-            validate_physical_type("n0", self.n0, "number density")
-            rows, n0 = self.n0.to("1/cm3").value, 1.0
-        else:
-            n0 = validate_scalar("n0", self.n0, physical_type="number density").to("1/cm3").value
+        n0 = validate_scalar_or_per_walker("n0", self.n0, "number density").to("1/cm3").value
+        rows = 1.0
+        if wv.per_walker(n0):  # the target density is a fit parameter: one factor per walker
+            rows, n0 = n0, 1.0
+        fee, fep = n0 * self.weight_ee * C_CGS, n0 * self.weight_ep * C_CGS
         if self._general_limits():
             # Eemin / Eemax / nEed per walker: every walker's own grid, the cross sections
             # evaluated at its nodes (nh_general_electron, what = 3: e-e | e-ion side by side)
             ctx, N, out = self._general_launch(3, E_eV)
-            fee, fep = n0 * self.weight_ee * C_CGS, n0 * self.weight_ep * C_CGS
-            if self.on_device:
-                tot = DMat.from_buffer(ctx, out, N, nE, ld=2 * nE, scale=fee) + \
-                    DMat.from_buffer(ctx, out, N, nE, ld=2 * nE, col0=nE, scale=fep)
-                if rows is not None:
-                    tot = tot * _as_dvec(ctx, rows, N)
-                return u.Quantity(tot, _SPEC_UNIT)
-            host = out.get()
-            host = fee * host[:, :nE] + fep * host[:, nE:]
-            if rows is not None:
-                host = host * np.broadcast_to(np.asarray(rows, dtype=float), (N,))[:, None]
-            return u.Quantity(self._finish(host, E), _SPEC_UNIT)
+            return self._times(ctx, self._halves(ctx, out, N, nE, fee, fep), N, E, rows)
         ctx, N, w, lw, gd, lx, gam = self._electron_weights()
         nG = gam.size
         Ed = ctx.const(E_eV)
@@ -1139,27 +1068,22 @@ class Bremsstrahlung(BaseElectron):
 
         Kt, dKt = ctx.table(("brems", gd.ptr, Ed.ptr), build)
         # spec = n0 (w_ee c int(n sigma_ee) + w_ep c int(n sigma_1)), radiative.py:949-987
-        scale = np.concatenate([np.full(nE, n0 * self.weight_ee * C_CGS),
-                                np.full(nE, n0 * self.weight_ep * C_CGS)])
+        scale = np.concatenate([np.full(nE, fee), np.full(nE, fep)])
         # (the Baring+99 fits go negative near their edges: signed reduction)
         out, _ = ctx.emit_tables(w, lw, N, nG, lx, Kt, dKt, 2 * nE, ctx.const(scale), 0,
                                  may_split=False)
+        return self._times(ctx, self._halves(ctx, out, N, nE), N, E, rows)
+
+    def _halves(self, ctx, out, N, nE, fee=1.0, fep=1.0):
+        """fee * e-e + fep * e-ion of the two spectra side by side in out[N][2 nE]; a local
+        helper: the base class's _result takes one buffer of one term"""
         if self.on_device:
-            tot = DMat.from_buffer(ctx, out, N, nE, ld=2 * nE) + \
-                DMat.from_buffer(ctx, out, N, nE, ld=2 * nE, col0=nE)
-            if rows is not None:
-                tot = tot * _as_dvec(ctx, rows, N)
-            return u.Quantity(tot, _SPEC_UNIT)
+            return DMat.from_buffer(ctx, out, N, nE, ld=2 * nE, scale=fee) + \
+                DMat.from_buffer(ctx, out, N, nE, ld=2 * nE, col0=nE, scale=fep)
         host = out.get()
-        host = host[:, :nE] + host[:, nE:]
-        if rows is not None:
-            host = host * np.broadcast_to(np.asarray(rows, dtype=float), (N,))[:, None]
-        return u.Quantity(self._finish(host, E), _SPEC_UNIT)
+        return fee * host[:, :nE] + fep * host[:, nE:]
 
-    def _own_batch_sizes(self):
-        return (_batch_of(self.n0),)
-
-    def _own_device_values(self):
+    def _own_values(self):
         return (self.n0,)
 
 
@@ -1186,13 +1110,13 @@ class BaseProton(BaseRadiative):
     def _general_limits(self):
         """True when Epmin, Epmax or nEpd is given per walker: every walker then has its own
         proton grid (radiative.py:1002-1009) and nh_general_proton integrates over it"""
-        return _per_walker(self.Epmin) or _per_walker(self.Epmax) or _per_walker(self.nEpd)
+        return wv.per_walker(self.Epmin) or wv.per_walker(self.Epmax) or wv.per_walker(self.nEpd)
 
     def _general_ok(self, *values):
         if not hasattr(self.particle_distribution, "device_rows"):
             return False
         for q in values:  # (a per-walker value has to match the object's own batch)
-            v = q.value if isinstance(q, u.Quantity) else q
+            v = wv.raw(q)
             if not isinstance(v, DVec) and np.ndim(v) > 0 and \
                     not (self.is_batched and len(v) == self.batch_size):
                 return False
@@ -1202,36 +1126,25 @@ class BaseProton(BaseRadiative):
         if self._general_limits() and self._general_ok(self.Epmin, self.Epmax, self.nEpd):
             others = [v for n, v in self._structural_values()
                       if n not in ("Epmin", "Epmax", "nEpd")]
-            if not any(_per_walker(v) for v in others):
+            if not any(wv.per_walker(v) for v in others):
                 return False
         return super()._needs_walker_loop()
 
     def _general_proton(self, what, E_eV, lo, hi, count_mode, hiE=0, nuc=0, lut=None):
         """nh_general_proton over every walker's own grid between lo and hi: spectra [N][nE]
         (what 0: analytic cross section, 1: look-up table) or Wp [N][1] in GeV (what 2)"""
-        import ctypes as C
-
-        from .darray import lazy_const
         ctx = get_context()
         pd = self.particle_distribution
         N = self.batch_size
-
-        def lazy_of(v):
-            v = v.value if isinstance(v, u.Quantity) else v
-            if isinstance(v, DVec):
-                return v.lazy(), v
-            if np.ndim(v) > 0:
-                d = _as_dvec(ctx, np.asarray(v, dtype=float), N)
-                return d.lazy(), d
-            return lazy_const(float(v)), None
 
         def gev_factor(q):
             f = ASTROPY_TO_GEV.get(q.unit.name)
             return float(q.unit.to("GeV") if f is None else f)
 
-        emin, k1 = lazy_of(lo)
-        emax, k2 = lazy_of(hi)
-        ned, k3 = lazy_of(self.nEpd)
+        # (the limits travel in their own unit, with that unit in GeV beside them)
+        emin, k1 = wv.lazy(ctx, lo, N=N)
+        emax, k2 = wv.lazy(ctx, hi, N=N)
+        ned, k3 = wv.lazy(ctx, self.nEpd, N=N)
         rows = pd.device_rows(ctx, N, amplitude_to=_PER_EV)
         nE = 1 if what == 2 else E_eV.size
         out = ctx.empty((N, nE))
@@ -1294,7 +1207,7 @@ class BaseProton(BaseRadiative):
             "Epmin", Epmin, physical_type="energy")
         hi = self.Epmax if Epmax is None else validate_scalar_or_batch(
             "Epmax", Epmax, physical_type="energy")
-        if _per_walker(lo) or _per_walker(hi) or _per_walker(self.nEpd):
+        if wv.per_walker(lo) or wv.per_walker(hi) or wv.per_walker(self.nEpd):
             if self._general_ok(lo, hi, self.nEpd):
                 return self._Wp_general(lo, hi, 1)
             return self._loop_walkers("compute_Wp", Epmin=Epmin, Epmax=Epmax)
@@ -1351,11 +1264,7 @@ class PionDecay(BaseProton):
     def __init__(self, particle_distribution, nh=1.0 / u.cm ** 3, nuclear_enhancement=True,
                  **kwargs):
         super().__init__(particle_distribution)
-        if _per_walker(nh):  # a fit parameter: one value per walker
-            validate_physical_type("nh", nh, "number density")
-            self.nh = nh
-        else:
-            self.nh = validate_scalar("nh", nh, physical_type="number density")
+        self.nh = validate_scalar_or_per_walker("nh", nh, "number density")
         self.nuclear_enhancement = nuclear_enhancement
         self.useLUT = True
         self.hiEmodel = "Pythia8"
@@ -1407,10 +1316,7 @@ class PionDecay(BaseProton):
                                  may_split=False)
         nh = self.nh.to("1/cm3").value
         fac = (nh * C_CGS) * 1e-9  # 1/(s GeV) -> 1/(s eV), radiative.py:1534-1536
-        if _per_walker(self.nh):
-            self.specpp = self._result(ctx, out, N, nE, E, rows=fac)
-        else:
-            self.specpp = self._result(ctx, out, N, nE, E, scale=fac)
+        self.specpp = self._result(ctx, out, N, nE, E, factor=fac)
         return self.specpp
 
     def _spectrum_general(self, E, E_eV):
@@ -1429,16 +1335,10 @@ class PionDecay(BaseProton):
             lut=_lut_spline(self._lut_file()) if use_lut else None)
         nh = self.nh.to("1/cm3").value
         fac = (nh * C_CGS) * 1e-9  # 1/(s GeV) -> 1/(s eV), radiative.py:1534-1536
-        if _per_walker(self.nh):
-            self.specpp = self._result(ctx, out, N, E_eV.size, E, rows=fac)
-        else:
-            self.specpp = self._result(ctx, out, N, E_eV.size, E, scale=fac)
+        self.specpp = self._result(ctx, out, N, E_eV.size, E, factor=fac)
         return self.specpp
 
-    def _own_batch_sizes(self):
-        return (_batch_of(self.nh),)
-
-    def _own_device_values(self):
+    def _own_values(self):
         return (self.nh,)
 
 
@@ -1457,18 +1357,11 @@ class PionDecayKelner06(BaseRadiative):
 
     def __init__(self, particle_distribution, nh=1.0 / u.cm ** 3, Etrans=0.1 * u.TeV, **kwargs):
         self.particle_distribution = particle_distribution
-        if _per_walker(nh):
-            validate_physical_type("nh", nh, "number density")
-            self.nh = nh
-        else:
-            self.nh = validate_scalar("nh", nh, physical_type="number density")
+        self.nh = validate_scalar_or_per_walker("nh", nh, "number density")
         self.Etrans = validate_scalar("Etrans", Etrans, domain="positive", physical_type="energy")
         self.__dict__.update(**kwargs)
 
-    def _own_batch_sizes(self):
-        return (_batch_of(self.nh),)
-
-    def _own_device_values(self):
+    def _own_values(self):
         return (self.nh,)
 
     def _launch(self, E_eV, want_wp=False):
@@ -1497,10 +1390,7 @@ class PionDecayKelner06(BaseRadiative):
             self.nhat = nh_ if self.is_batched else float(nh_[0])
         # density_factor = nh / (1 cm^-3), radiative.py:1765
         dens = self.nh.to("1/cm3").value
-        if _per_walker(self.nh):
-            self.specpp = self._result(ctx, out, N, E_eV.size, E, rows=dens)
-        else:
-            self.specpp = self._result(ctx, out, N, E_eV.size, E, scale=float(dens))
+        self.specpp = self._result(ctx, out, N, E_eV.size, E, factor=dens)
         return self.specpp
 
     @property
@@ -1563,11 +1453,7 @@ class SecondaryLeptonsKelner06(BaseRadiative):
     def __init__(self, particle_distribution, nh=1.0 / u.cm ** 3, Etrans=0.1 * u.TeV,
                  product="nu_mu", **kwargs):
         self.particle_distribution = particle_distribution
-        if _per_walker(nh):
-            validate_physical_type("nh", nh, "number density")
-            self.nh = nh
-        else:
-            self.nh = validate_scalar("nh", nh, physical_type="number density")
+        self.nh = validate_scalar_or_per_walker("nh", nh, "number density")
         self.Etrans = validate_scalar("Etrans", Etrans, domain="positive", physical_type="energy")
         if product not in self.products:
             raise ValueError("product must be one of %s (got %r)"
@@ -1575,10 +1461,7 @@ class SecondaryLeptonsKelner06(BaseRadiative):
         self.product = product
         self.__dict__.update(**kwargs)
 
-    def _own_batch_sizes(self):
-        return (_batch_of(self.nh),)
-
-    def _own_device_values(self):
+    def _own_values(self):
         return (self.nh,)
 
     def _spectrum(self, energy):
@@ -1601,8 +1484,5 @@ class SecondaryLeptonsKelner06(BaseRadiative):
             nh_ = nhat.get()
             self.nhat = nh_ if self.is_batched else nh_[0]
         dens = self.nh.to("1/cm3").value
-        if _per_walker(self.nh):
-            self.specpp = self._result(ctx, out, N, nE, E, rows=dens)
-        else:
-            self.specpp = self._result(ctx, out, N, nE, E, scale=float(dens))
+        self.specpp = self._result(ctx, out, N, nE, E, factor=dens)
         return self.specpp

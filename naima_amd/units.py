@@ -20,6 +20,8 @@ import re
 
 import numpy as np
 
+from .darray import is_device as _is_device
+
 __all__ = ["Unit", "Quantity", "UnitsError", "UnitConversionError", "dimensionless_unscaled"]
 
 _NB = 6  # cm g s K rad G
@@ -104,7 +106,7 @@ class Unit:
             return self._combine(other, -1)
         if isinstance(other, _QuantityBase):
             return Quantity(1.0 / other.value, self / other.unit)
-        if getattr(other, "__array_priority__", 0) == 30000:
+        if _is_device(other):
             return Quantity(1.0 / other, self)
         return Quantity(1.0 / np.asarray(other, dtype=float), self)
 
@@ -323,7 +325,7 @@ class Quantity(_QuantityBase):
             value, unit = float(m.group(1)), Unit(m.group(2))
         if unit is None:
             unit = dimensionless_unscaled
-        if getattr(value, "__array_priority__", 0) == 30000:
+        if _is_device(value):
             self.value = value  # device-resident lazy value (naima_amd.darray)
         else:
             v = np.asarray(value, dtype=dtype)
@@ -370,7 +372,7 @@ class Quantity(_QuantityBase):
 
     @property
     def on_device(self):
-        return getattr(self.value, "__array_priority__", 0) == 30000
+        return _is_device(self.value)
 
     @property
     def T(self):
@@ -420,7 +422,7 @@ class Quantity(_QuantityBase):
             return other.value, other.unit
         if isinstance(other, Unit):
             return 1.0, other
-        if getattr(other, "__array_priority__", 0) == 30000:
+        if _is_device(other):
             return other, dimensionless_unscaled
         if getattr(other, "_make", None) is not None:  # (darray.FactorRow: keeps its device form)
             return other, dimensionless_unscaled

@@ -4,6 +4,8 @@ extended to accept a 1-D batch over walkers where the reference takes a scalar."
 import numpy as np
 
 from . import units as u
+from .darray import is_device
+from .walker_value import per_walker
 
 
 def validate_physical_type(name, value, physical_type):
@@ -17,7 +19,7 @@ def validate_physical_type(name, value, physical_type):
 
 def _check_domain(name, value, domain):
     v = value.value if isinstance(value, u.Quantity) else value
-    if getattr(v, "__array_priority__", 0) == 30000:
+    if is_device(v):
         return  # device-resident: checking would force a synchronising download
     v = np.asarray(v, dtype=float)
     if np.any(~np.isfinite(v)):
@@ -53,6 +55,15 @@ def validate_scalar_or_batch(name, value, domain=None, physical_type=None):
         raise TypeError("{0} should be a scalar or a 1-D batch over walkers".format(name))
     _check_domain(name, value, domain)
     return value
+
+
+def validate_scalar_or_per_walker(name, value, physical_type):
+    """a scalar, checked as the reference checks it, or one value per walker (host array or
+    device value: a fit parameter), of which only the physical type is checked"""
+    if per_walker(value):
+        validate_physical_type(name, value, physical_type)
+        return value
+    return validate_scalar(name, value, physical_type=physical_type)
 
 
 def validate_array(name, value, domain=None, ndim=1, shape=None, physical_type=None):
