@@ -215,6 +215,9 @@ __device__ __forceinline__ void nh_clk_close(long long* clk) {
   clk[2] += 1;
 }
 
+// the quiet NaN an entry point writes where a result does not exist
+__device__ __forceinline__ double nh_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
+
 __device__ __forceinline__ double nh_rcp(double x) {
   double r = __builtin_amdgcn_rcp(x);
   double e = fma(-x, r, 1.0);

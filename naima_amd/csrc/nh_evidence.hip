@@ -44,8 +44,6 @@ constexpr int EV_LP_THREADS = 128;  // nh_mvn_logpdf: d * 128 * 8 bytes of LDS h
 static_assert(EV_D * (EV_D + 1) / 2 <= EV_PPT * PO_THREADS, "pairs per thread");
 static_assert(EV_D <= 64, "k_cov_mean is one wave");
 
-__device__ __forceinline__ double ev_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
 __device__ __forceinline__ long long ev_src(long long e, long long row0, long long ld,
                                             long long cstride, int npool) {
   const long long t = e / npool, j = e - t * npool;
@@ -96,7 +94,7 @@ __global__ void k_cov_mean(const double* __restrict__ part, const int* __restric
     s += part[k * d + c];
     nb |= bad[k * d + c];
   }
-  mean[c] = nb ? ev_nan() : s / (double)S;
+  mean[c] = nb ? nh_nan() : s / (double)S;
 }
 
 // part[k * np + p] = the sum over the rows of chunk k of the centred product of pair p = (a, b),
@@ -228,7 +226,7 @@ __global__ __launch_bounds__(EV_LP_THREADS) void k_mvn_logpdf(
       q = fma(yi, yi, q);
     }
     const double lg = *lognorm - 0.5 * q;
-    out[e] = bad ? ev_nan() : (lp ? lp[e] - lg : lg);
+    out[e] = bad ? nh_nan() : (lp ? lp[e] - lg : lg);
   }
 }
 

@@ -15,8 +15,6 @@ constexpr int CRIT_TAIL_MAX = NH_PSIS_MAX_TAIL;      // tail entries a workgroup
 constexpr int CRIT_MAX_CAND = 96;                    // 30 + floor(sqrt(4096)) = 94 candidates b_j
 constexpr double CRIT_LOG_TINY = -708.3964185322641; // log(DBL_MIN)
 
-__device__ __forceinline__ double crit_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
 __device__ __forceinline__ double crit_wave_allsum(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);

@@ -10,8 +10,7 @@
 //                        the terms; optionally the row totals; the number of non-finite terms in
 //                        a device int64 (an integer atomic per wave that met one).
 //   nh_lnl_column_stats  per column of L: max, mean, unbiased variance, lse = max + log sum
-//                        exp(L - max), min.  Two passes over L in the tiling of nh_colred.h, the
-//                        per-chunk partials summed in chunk order.
+//                        exp(L - max), min.  Two chunk passes over L (nh_colred.h).
 //   nh_psis_columns      Pareto-smoothed importance sampling per column (Vehtari, Simpson, Gelman,
 //                        Yao, Gabry; the generalised-Pareto fit of Zhang & Stephens 2009 with the
 //                        weak priors of the loo package).  With x = min(L) - L (the negated column,
@@ -92,94 +91,68 @@ __global__ __launch_bounds__(PO_THREADS) void k_crit_pointwise(
 }
 
 // ---------------------------------------------------------------- column statistics
-// per (row chunk k, column c): pd[(k*3 + 0|1|2)*ncol + c] = sum, min, max
-__global__ __launch_bounds__(PO_THREADS) void k_crit_sum(const double* __restrict__ x, long long M,
-                                                       int ncol, long long ld, int cw,
-                                                       long long rows, double* __restrict__ pd) {
-  __shared__ double rs[PO_THREADS], rlo[PO_THREADS], rhi[PO_THREADS];
-  int tid = threadIdx.x, tx = tid % cw, ty = tid / cw, R = PO_THREADS / cw;
-  int c = blockIdx.x * cw + tx;
-  long long k = blockIdx.y;
-  long long t0 = k * rows, t1 = min(M, t0 + rows);
-  double s = 0.0, lo = INFINITY, hi = -INFINITY;
-  if (c < ncol) {
-    for (long long t = t0 + ty; t < t1; t += R) {
+// (the chunk pass, its partials and the fold in chunk order: nh_colred.h)
+// sum, min, max
+struct k_crit_sum {
+  using F = colred_fields<0, '+', '<', '>'>;
+  const double* __restrict__ x;
+  long long ld;
+  template <class W>
+  __device__ __forceinline__ void column(int c, W walk, F::acc& a) const {
+    double s = 0.0, lo = INFINITY, hi = -INFINITY;
+    walk([&](long long t) {
       double v = x[t * ld + c];
       s += v;
       lo = fmin(lo, v);
       hi = fmax(hi, v);
-    }
+    });
+    a = {{s, lo, hi}};
   }
-  rs[tid] = s; rlo[tid] = lo; rhi[tid] = hi;
-  po_tree(rs, tid, ty, cw, [](double a, double b) { return a + b; });
-  po_tree(rlo, tid, ty, cw, [](double a, double b) { return fmin(a, b); });
-  po_tree(rhi, tid, ty, cw, [](double a, double b) { return fmax(a, b); });
-  if (ty == 0 && c < ncol) {
-    pd[(k * 3 + 0) * ncol + c] = rs[tid];
-    pd[(k * 3 + 1) * ncol + c] = rlo[tid];
-    pd[(k * 3 + 2) * ncol + c] = rhi[tid];
-  }
-}
+};
 
 // stats[0|1|4][c] = max, mean (the value itself for a column of equal values), min
-__global__ void k_crit_mean(const double* __restrict__ pd, long long nch, int ncol, long long M,
-                          double* __restrict__ stats) {
+__global__ void k_crit_mean(long long nch, int ncol, long long M, double* __restrict__ stats,
+                            colred_out part) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncol) return;
-  double s = 0.0, lo = INFINITY, hi = -INFINITY;
-  for (long long k = 0; k < nch; ++k) {
-    s += pd[(k * 3 + 0) * ncol + c];
-    lo = fmin(lo, pd[(k * 3 + 1) * ncol + c]);
-    hi = fmax(hi, pd[(k * 3 + 2) * ncol + c]);
-  }
+  const auto a = colred_fold<k_crit_sum>(part, nch, ncol, c);
+  const double s = a.d[0], lo = a.d[1], hi = a.d[2];
   stats[c] = hi;
   stats[ncol + c] = lo == hi ? lo : s / (double)M;
   stats[4 * ncol + c] = lo;
 }
 
-// pq[(k*2 + 0|1)*ncol + c] = the chunk's sums of (x - mean)^2 and of exp(x - max)
-__global__ __launch_bounds__(PO_THREADS) void k_crit_sq(const double* __restrict__ x, long long M,
-                                                      int ncol, long long ld, int cw,
-                                                      long long rows,
-                                                      const double* __restrict__ stats,
-                                                      double* __restrict__ pq) {
-  __shared__ double rq[PO_THREADS], re[PO_THREADS];
-  int tid = threadIdx.x, tx = tid % cw, ty = tid / cw, R = PO_THREADS / cw;
-  int c = blockIdx.x * cw + tx;
-  long long k = blockIdx.y;
-  long long t0 = k * rows, t1 = min(M, t0 + rows);
-  double q = 0.0, e = 0.0;
-  if (c < ncol) {
+// the sums of (x - mean)^2 and of exp(x - max)
+struct k_crit_sq {
+  using F = colred_fields<0, '+', '+'>;
+  const double* __restrict__ x;
+  long long ld;
+  const double* __restrict__ stats;
+  int ncol;
+  template <class W>
+  __device__ __forceinline__ void column(int c, W walk, F::acc& a) const {
     const double hi = stats[c], mean = stats[ncol + c];
-    for (long long t = t0 + ty; t < t1; t += R) {
+    double q = 0.0, e = 0.0;
+    walk([&](long long t) {
       double v = x[t * ld + c];
       double d = v - mean;
       q = fma(d, d, q);
       e += exp(v - hi);
-    }
+    });
+    a = {{q, e}};
   }
-  rq[tid] = q; re[tid] = e;
-  po_tree(rq, tid, ty, cw, [](double a, double b) { return a + b; });
-  po_tree(re, tid, ty, cw, [](double a, double b) { return a + b; });
-  if (ty == 0 && c < ncol) {
-    pq[(k * 2 + 0) * ncol + c] = rq[tid];
-    pq[(k * 2 + 1) * ncol + c] = re[tid];
-  }
-}
+};
 
 // stats[2][c] = sum / (M - 1): exactly 0 for equal values, NaN for M == 1;
 // stats[3][c] = max + log(sum of exp(x - max))
-__global__ void k_crit_fin(const double* __restrict__ pq, long long nch, int ncol, long long M,
-                         double* __restrict__ stats) {
+__global__ void k_crit_fin(long long nch, int ncol, long long M, double* __restrict__ stats,
+                           colred_out part) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncol) return;
-  double q = 0.0, e = 0.0;
-  for (long long k = 0; k < nch; ++k) {
-    q += pq[(k * 2 + 0) * ncol + c];
-    e += pq[(k * 2 + 1) * ncol + c];
-  }
+  const auto a = colred_fold<k_crit_sq>(part, nch, ncol, c);
+  const double q = a.d[0], e = a.d[1];
   const double hi = stats[c], lo = stats[4 * ncol + c];
-  stats[2 * ncol + c] = M > 1 ? (lo == hi ? 0.0 : q / (double)(M - 1)) : crit_nan();
+  stats[2 * ncol + c] = M > 1 ? (lo == hi ? 0.0 : q / (double)(M - 1)) : nh_nan();
   stats[3 * ncol + c] = hi + log(e);
 }
 
@@ -190,24 +163,24 @@ __device__ __forceinline__ double crit_cut(double lmin, double lsel) {
   return fmax(lmin - lsel, CRIT_LOG_TINY);
 }
 
-// per (row chunk k, column c) over the rows with x <= cut: part[(k*2 + 0|1)*ncol + c] = the sums
-// of exp(x) and of exp((x + L) - min); the rows with x > cut go to the column's list
-// tx / trow [c*cap ..], their number to cnt[c] (zeroed before the launch)
-__global__ __launch_bounds__(PO_THREADS) void k_crit_split(
-    const double* __restrict__ L, long long M, int ncol, long long ld, int cw, long long rows,
-    const double* __restrict__ stats, const double* __restrict__ lsel, int cap,
-    double* __restrict__ part, double* __restrict__ tx, int* __restrict__ trow,
-    unsigned* __restrict__ cnt) {
-  __shared__ double ra[PO_THREADS], rb[PO_THREADS];
-  int tid = threadIdx.x, txc = tid % cw, ty = tid / cw, R = PO_THREADS / cw;
-  int c = blockIdx.x * cw + txc;
-  long long k = blockIdx.y;
-  long long t0 = k * rows, t1 = min(M, t0 + rows);
-  double a = 0.0, b = 0.0;
-  if (c < ncol) {
+// over the rows with x <= cut: the sums of exp(x) and of exp((x + L) - min); the rows with x > cut
+// go to the column's list tx / trow [c*cap ..], their number to cnt[c] (zeroed before the launch)
+struct k_crit_split {
+  using F = colred_fields<0, '+', '+'>;
+  const double* __restrict__ L;
+  long long ld;
+  const double* __restrict__ stats;
+  const double* __restrict__ lsel;
+  int ncol, cap;
+  double* __restrict__ tx;
+  int* __restrict__ trow;
+  unsigned* __restrict__ cnt;
+  template <class W>
+  __device__ __forceinline__ void column(int c, W walk, F::acc& a) const {
     const double lmin = stats[4 * ncol + c];
     const double cut = crit_cut(lmin, lsel[c]);
-    for (long long t = t0 + ty; t < t1; t += R) {
+    double sa = 0.0, sb = 0.0;
+    walk([&](long long t) {
       const double v = L[t * ld + c];
       const double xv = lmin - v;
       if (xv > cut) {
@@ -218,25 +191,19 @@ __global__ __launch_bounds__(PO_THREADS) void k_crit_split(
           trow[(long long)c * cap + slot] = (int)t;
         }
       } else {
-        a += exp(xv);
-        b += exp((xv + v) - lmin);
+        sa += exp(xv);
+        sb += exp((xv + v) - lmin);
       }
-    }
+    });
+    a = {{sa, sb}};
   }
-  ra[tid] = a; rb[tid] = b;
-  po_tree(ra, tid, ty, cw, [](double p, double q) { return p + q; });
-  po_tree(rb, tid, ty, cw, [](double p, double q) { return p + q; });
-  if (ty == 0 && c < ncol) {
-    part[(k * 2 + 0) * ncol + c] = ra[tid];
-    part[(k * 2 + 1) * ncol + c] = rb[tid];
-  }
-}
+};
 
 // one workgroup per column: sort the tail, fit, smooth, finish the two log-sum-exps
 __global__ __launch_bounds__(PO_THREADS) void k_crit_tail(
     const double* __restrict__ L, int ncol, long long ld, long long nch, int cap,
     const double* __restrict__ stats, const double* __restrict__ lsel,
-    const double* __restrict__ part, const double* __restrict__ tx, const int* __restrict__ trow,
+    colred_out part, const double* __restrict__ tx, const int* __restrict__ trow,
     const unsigned* __restrict__ cnt, double* __restrict__ pareto_k, long long* __restrict__ n_tail,
     double* __restrict__ elpd) {
   CRIT_TAIL_LDS(s);
@@ -270,11 +237,8 @@ __global__ __launch_bounds__(PO_THREADS) void k_crit_tail(
   for (int i = tid; i < n; i += PO_THREADS) b += exp(tt[i] - emax);
   b = crit_block_reduce(b, red, tid, [](double p, double q) { return p + q; });
   if (tid == 0) {
-    double an = 0.0, bn = 0.0;
-    for (long long k = 0; k < nch; ++k) {
-      an += part[(k * 2 + 0) * ncol + c];
-      bn += part[(k * 2 + 1) * ncol + c];
-    }
+    const auto below = colred_fold<k_crit_split>(part, nch, ncol, c);
+    const double an = below.d[0], bn = below.d[1];
     pareto_k[c] = kpar;
     n_tail[c] = n;
     elpd[c] = (lmin + emax) + (log(bn * exp(-emax) + b) - log(an + a));
@@ -283,18 +247,12 @@ __global__ __launch_bounds__(PO_THREADS) void k_crit_tail(
 
 }  // namespace
 
-#define CRIT_REQUIRE_MATRIX(M, ncol, ld)                             \
-  NH_REQUIRE(M > 0, "M == 0: no samples");                         \
-  NH_REQUIRE(M < (1ll << 31), "M >= 2^31 rows");                   \
-  NH_REQUIRE(ncol > 0, "ncol must be positive");                   \
-  NH_REQUIRE(ld >= ncol, "ncol > ld")
-
 extern "C" int nh_pointwise_lnl(nh_ctx* ctx, const double* x, long long M, int nE, long long ld,
                                 const double* conv, const double* flux, const double* elo,
                                 const double* ehi, const int* ul, const double* cl, double* L,
                                 long long ldL, double* total, long long* nbad) {
   NH_REQUIRE(ctx && x && conv && flux && elo && ehi && ul && cl && L && nbad, "null argument");
-  CRIT_REQUIRE_MATRIX(M, nE, ld);
+  NH_REQUIRE_MATRIX(M, nE, ld, NH_ROWS_INT);
   NH_REQUIRE(ldL >= nE, "nE > ldL");
   hipStream_t s = ctx->stream;
   NH_CHECK_HIP(hipMemsetAsync(nbad, 0, 8, s));
@@ -308,27 +266,24 @@ extern "C" int nh_pointwise_lnl(nh_ctx* ctx, const double* x, long long M, int n
 extern "C" int nh_lnl_column_stats(nh_ctx* ctx, const double* L, long long M, int ncol,
                                    long long ld, double* stats) {
   NH_REQUIRE(ctx && L && stats, "null argument");
-  CRIT_REQUIRE_MATRIX(M, ncol, ld);
-  int cw = po_pow2_at_least(ncol, 64);
-  long long ntile = cdiv(ncol, cw), rows, nch;
-  po_chunks(M, ntile, PO_THREADS / cw, &rows, &nch);
-  NH_REQUIRE(nch <= 65535 && ntile < (1ll << 31), "too many columns");
+  NH_REQUIRE_MATRIX(M, ncol, ld, NH_ROWS_INT);
+  const colred_grid g = colred_plan(M, ncol);
+  NH_REQUIRE_PLAN(g);
+  const long long nch = g.nch;
   // scratch: pd [nch][3][ncol] | pq [nch][2][ncol]
   void* base = nullptr;
   int rc = nh_scratch(ctx, (size_t)nch * ncol * 5 * 8, &base);
   if (rc) return rc;
   double* pd = (double*)base;
   double* pq = pd + (size_t)nch * 3 * ncol;
+  const colred_out sums = colred_dense<k_crit_sum>(pd), sq = colred_dense<k_crit_sq>(pq);
   hipStream_t s = ctx->stream;
-  dim3 grid((unsigned)ntile, (unsigned)nch);
-  unsigned cb = (unsigned)cdiv(ncol, PO_THREADS);
-  hipLaunchKernelGGL(k_crit_sum, grid, dim3(PO_THREADS), 0, s, L, M, ncol, ld, cw, rows, pd);
+  if ((rc = colred_launch<k_crit_sum>(s, g, sums, L, ld))) return rc;
+  hipLaunchKernelGGL(k_crit_mean, dim3(g.col_blocks()), dim3(PO_THREADS), 0, s, nch, ncol, M, stats,
+                     sums);
   NH_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_crit_mean, dim3(cb), dim3(PO_THREADS), 0, s, pd, nch, ncol, M, stats);
-  NH_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_crit_sq, grid, dim3(PO_THREADS), 0, s, L, M, ncol, ld, cw, rows, stats, pq);
-  NH_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_crit_fin, dim3(cb), dim3(PO_THREADS), 0, s, pq, nch, ncol, M, stats);
+  if ((rc = colred_launch<k_crit_sq>(s, g, sq, L, ld, stats, ncol))) return rc;
+  hipLaunchKernelGGL(k_crit_fin, dim3(g.col_blocks()), dim3(PO_THREADS), 0, s, nch, ncol, M, stats, sq);
   NH_CHECK_HIP(hipGetLastError());
   return NH_OK;
 }
@@ -337,14 +292,13 @@ extern "C" int nh_psis_columns(nh_ctx* ctx, const double* L, long long M, int nc
                                int Mt, const double* stats, const double* lsel, double* pareto_k,
                                long long* n_tail, double* elpd) {
   NH_REQUIRE(ctx && L && stats && lsel && pareto_k && n_tail && elpd, "null argument");
-  CRIT_REQUIRE_MATRIX(M, ncol, ld);
+  NH_REQUIRE_MATRIX(M, ncol, ld, NH_ROWS_INT);
   NH_REQUIRE(Mt >= 0 && Mt < M, "Mt outside [0, M)");
   NH_REQUIRE(Mt <= NH_PSIS_MAX_TAIL, "Mt > NH_PSIS_MAX_TAIL: thin the chain");
   const int cap = std::max(Mt, 1);
-  int cw = po_pow2_at_least(ncol, 64);
-  long long ntile = cdiv(ncol, cw), rows, nch;
-  po_chunks(M, ntile, PO_THREADS / cw, &rows, &nch);
-  NH_REQUIRE(nch <= 65535, "too many columns");
+  const colred_grid g = colred_plan(M, ncol);
+  NH_REQUIRE_PLAN(g);
+  const long long nch = g.nch;
   // scratch: part [nch][2][ncol] | tx [ncol][cap] | trow [ncol][cap] | cnt [ncol]
   const size_t npart = (size_t)nch * 2 * ncol, nlist = (size_t)ncol * cap;
   void* base = nullptr;
@@ -356,11 +310,11 @@ extern "C" int nh_psis_columns(nh_ctx* ctx, const double* L, long long M, int nc
   unsigned* cnt = (unsigned*)(trow + nlist);
   hipStream_t s = ctx->stream;
   NH_CHECK_HIP(hipMemsetAsync(cnt, 0, (size_t)ncol * 4, s));
-  hipLaunchKernelGGL(k_crit_split, dim3((unsigned)ntile, (unsigned)nch), dim3(PO_THREADS), 0, s, L, M,
-                     ncol, ld, cw, rows, stats, lsel, cap, part, tx, trow, cnt);
-  NH_CHECK_HIP(hipGetLastError());
+  const colred_out below = colred_dense<k_crit_split>(part);
+  if ((rc = colred_launch<k_crit_split>(s, g, below, L, ld, stats, lsel, ncol, cap, tx, trow, cnt)))
+    return rc;
   hipLaunchKernelGGL(k_crit_tail, dim3((unsigned)ncol), dim3(PO_THREADS), 0, s, L, ncol, ld, nch, cap,
-                     stats, lsel, part, tx, trow, cnt, pareto_k, n_tail, elpd);
+                     stats, lsel, below, tx, trow, cnt, pareto_k, n_tail, elpd);
   NH_CHECK_HIP(hipGetLastError());
   return NH_OK;
 }

@@ -5,10 +5,8 @@
 // layout of get_chain(flat=True) and of stored scalar blobs).
 //
 //   nh_column_moments  per column: the counts of finite values and of NaNs, min, max, mean and the
-//                      unbiased variance of the finite values.  Two passes (the mean, then the sum
-//                      of (x - mean)^2); workgroups take (column tile, row chunk), a lane per
-//                      column, and reduce their row lanes through an LDS tree; the per-chunk
-//                      partials are summed by one thread per column in chunk order.
+//                      unbiased variance of the finite values.  Two chunk passes of nh_colred.h
+//                      (the mean, then the sum of (x - mean)^2), each folded in chunk order.
 //   nh_hist_columns    1-D counts of every column and 2-D counts of a list of column pairs on
 //                      per-column edges.  A thread reads a row, bins every column once (an
 //                      arithmetic estimate corrected against the edges, as NumPy does), keeps the
@@ -42,109 +40,76 @@ constexpr int PO_KDE_STAGE = 1024;     // values of a column per LDS stage of th
 constexpr unsigned short PO_DROPPED = 0xffffu;
 
 // ---------------------------------------------------------------- moments
-// (the tiling, the chunks and the LDS tree down the row lanes: nh_colred.h)
-// per (row chunk k, column c): pd[(k*3 + 0|1|2)*ncol + c] = sum, min, max of the finite values,
-// pc[(k*2 + 0|1)*ncol + c] = the number of finite values, of NaNs
-__global__ __launch_bounds__(PO_THREADS) void k_po_sum(const double* __restrict__ x, long long M,
-                                                       int ncol, long long ld, int cw,
-                                                       long long rows, double* __restrict__ pd,
-                                                       long long* __restrict__ pc) {
-  __shared__ double rs[PO_THREADS], rlo[PO_THREADS], rhi[PO_THREADS];
-  __shared__ long long rn[PO_THREADS], rnan[PO_THREADS];
-  int tid = threadIdx.x, tx = tid % cw, ty = tid / cw, R = PO_THREADS / cw;
-  int c = blockIdx.x * cw + tx;
-  long long k = blockIdx.y;
-  long long t0 = k * rows, t1 = min(M, t0 + rows);
-  double s = 0.0, lo = INFINITY, hi = -INFINITY;
-  long long n = 0, nn = 0;
-  if (c < ncol) {
-    for (long long t = t0 + ty; t < t1; t += R) {
+// (the chunk pass, its partials and the fold in chunk order: nh_colred.h)
+// sum, min, max of the finite values | their number, that of the NaNs
+struct k_po_sum {
+  using F = colred_fields<2, '+', '<', '>'>;
+  const double* __restrict__ x;
+  long long ld;
+  template <class W>
+  __device__ __forceinline__ void column(int c, W walk, F::acc& a) const {
+    double s = 0.0, lo = INFINITY, hi = -INFINITY;
+    long long n = 0, nn = 0;
+    walk([&](long long t) {
       double v = x[t * ld + c];
       if (po_finite(v)) {
         s += v;
         lo = fmin(lo, v);
         hi = fmax(hi, v);
         ++n;
-      } else if (v != v) {
-        ++nn;
       }
-    }
+      nn += v != v ? 1 : 0;  // (beside the branch: a counter moves in every row, nh_colred.h)
+    });
+    a = {{s, lo, hi}, {n, nn}};
   }
-  rs[tid] = s; rlo[tid] = lo; rhi[tid] = hi; rn[tid] = n; rnan[tid] = nn;
-  po_tree(rs, tid, ty, cw, [](double a, double b) { return a + b; });
-  po_tree(rlo, tid, ty, cw, [](double a, double b) { return fmin(a, b); });
-  po_tree(rhi, tid, ty, cw, [](double a, double b) { return fmax(a, b); });
-  po_tree(rn, tid, ty, cw, [](long long a, long long b) { return a + b; });
-  po_tree(rnan, tid, ty, cw, [](long long a, long long b) { return a + b; });
-  if (ty == 0 && c < ncol) {
-    pd[(k * 3 + 0) * ncol + c] = rs[tid];
-    pd[(k * 3 + 1) * ncol + c] = rlo[tid];
-    pd[(k * 3 + 2) * ncol + c] = rhi[tid];
-    pc[(k * 2 + 0) * ncol + c] = rn[tid];
-    pc[(k * 2 + 1) * ncol + c] = rnan[tid];
-  }
-}
+};
 
 // counts[0|1][c] = n, NaNs; stats[0|1|2][c] = min, max, mean (NaN without a finite value; the
 // value itself for a column whose finite values are all equal)
-__global__ void k_po_mean(const double* __restrict__ pd, const long long* __restrict__ pc,
-                          long long nch, int ncol, long long* __restrict__ counts,
-                          double* __restrict__ stats) {
+__global__ void k_po_mean(long long nch, int ncol, long long* __restrict__ counts,
+                          double* __restrict__ stats, colred_out part) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncol) return;
-  double s = 0.0, lo = INFINITY, hi = -INFINITY;
-  long long n = 0, nn = 0;
-  for (long long k = 0; k < nch; ++k) {
-    s += pd[(k * 3 + 0) * ncol + c];
-    lo = fmin(lo, pd[(k * 3 + 1) * ncol + c]);
-    hi = fmax(hi, pd[(k * 3 + 2) * ncol + c]);
-    n += pc[(k * 2 + 0) * ncol + c];
-    nn += pc[(k * 2 + 1) * ncol + c];
-  }
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const auto a = colred_fold<k_po_sum>(part, nch, ncol, c);
+  const double s = a.d[0], lo = a.d[1], hi = a.d[2];
+  const long long n = a.n[0];
   counts[c] = n;
-  counts[ncol + c] = nn;
-  stats[c] = n ? lo : nan;
-  stats[ncol + c] = n ? hi : nan;
-  stats[2 * ncol + c] = n ? (lo == hi ? lo : s / (double)n) : nan;
+  counts[ncol + c] = a.n[1];
+  stats[c] = n ? lo : nh_nan();
+  stats[ncol + c] = n ? hi : nh_nan();
+  stats[2 * ncol + c] = n ? (lo == hi ? lo : s / (double)n) : nh_nan();
 }
 
-// pq[k*ncol + c] = the chunk's sum of (x - mean)^2 over the finite values
-__global__ __launch_bounds__(PO_THREADS) void k_po_sq(const double* __restrict__ x, long long M,
-                                                      int ncol, long long ld, int cw,
-                                                      long long rows,
-                                                      const double* __restrict__ stats,
-                                                      double* __restrict__ pq) {
-  __shared__ double rq[PO_THREADS];
-  int tid = threadIdx.x, tx = tid % cw, ty = tid / cw, R = PO_THREADS / cw;
-  int c = blockIdx.x * cw + tx;
-  long long k = blockIdx.y;
-  long long t0 = k * rows, t1 = min(M, t0 + rows);
-  double q = 0.0;
-  if (c < ncol) {
+// the sum of (x - mean)^2 over the finite values
+struct k_po_sq {
+  using F = colred_fields<0, '+'>;
+  const double* __restrict__ x;
+  long long ld;
+  const double* __restrict__ stats;
+  int ncol;
+  template <class W>
+  __device__ __forceinline__ void column(int c, W walk, F::acc& a) const {
     const double mean = stats[2 * ncol + c];
-    for (long long t = t0 + ty; t < t1; t += R) {
+    double q = 0.0;
+    walk([&](long long t) {
       double v = x[t * ld + c];
       if (po_finite(v)) {
         double d = v - mean;
         q = fma(d, d, q);
       }
-    }
+    });
+    a = {{q}};
   }
-  rq[tid] = q;
-  po_tree(rq, tid, ty, cw, [](double a, double b) { return a + b; });
-  if (ty == 0 && c < ncol) pq[k * ncol + c] = rq[tid];
-}
+};
 
 // stats[3][c] = sum / (n - 1): exactly 0 for equal values, NaN for fewer than two
-__global__ void k_po_var(const double* __restrict__ pq, long long nch, int ncol,
-                         const long long* __restrict__ counts, double* __restrict__ stats) {
+__global__ void k_po_var(long long nch, int ncol, const long long* __restrict__ counts,
+                         double* __restrict__ stats, colred_out part) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncol) return;
-  double q = 0.0;
-  for (long long k = 0; k < nch; ++k) q += pq[k * ncol + c];
+  const double q = colred_fold<k_po_sq>(part, nch, ncol, c).d[0];
   long long n = counts[c];
-  double var = __longlong_as_double(0x7ff8000000000000ll);
+  double var = nh_nan();
   if (n > 1) var = stats[c] == stats[ncol + c] ? 0.0 : q / (double)(n - 1);
   stats[3 * ncol + c] = var;
 }
@@ -228,7 +193,7 @@ __global__ void k_po_gmean(const double* __restrict__ pd, const long long* __res
     n += pc[i];
   }
   counts[q] = n;
-  stats[q] = n ? (lo == hi ? lo : s / (double)n) : __longlong_as_double(0x7ff8000000000000ll);
+  stats[q] = n ? (lo == hi ? lo : s / (double)n) : nh_nan();
   lohi[2 * q] = lo;
   lohi[2 * q + 1] = hi;
 }
@@ -268,7 +233,7 @@ __global__ void k_po_gvar(const double* __restrict__ pq, long long nch, int ndim
   double sq = 0.0;
   for (long long c = 0; c < nch; ++c) sq += pq[i0 + c * ndim];
   long long n = counts[q];
-  double var = __longlong_as_double(0x7ff8000000000000ll);
+  double var = nh_nan();
   if (n > 1) var = lohi[2 * q] == lohi[2 * q + 1] ? 0.0 : sq / (double)(n - 1);
   stats[nq + q] = var;
 }
@@ -405,19 +370,13 @@ __global__ void k_po_kde_reduce(const double* __restrict__ part, const long long
 
 }  // namespace
 
-#define PO_REQUIRE_MATRIX()                                        \
-  NH_REQUIRE(M > 0, "M == 0: no samples");                         \
-  NH_REQUIRE(ncol > 0, "ncol must be positive");                   \
-  NH_REQUIRE(ld >= ncol, "ncol > ld")
-
 extern "C" int nh_column_moments(nh_ctx* ctx, const double* x, long long M, int ncol, long long ld,
                                  long long* counts, double* stats) {
   NH_REQUIRE(ctx && x && counts && stats, "null argument");
-  PO_REQUIRE_MATRIX();
-  int cw = po_pow2_at_least(ncol, 64);
-  long long ntile = cdiv(ncol, cw), rows, nch;
-  po_chunks(M, ntile, PO_THREADS / cw, &rows, &nch);
-  NH_REQUIRE(nch <= 65535 && ntile < (1ll << 31), "too many columns");
+  NH_REQUIRE_MATRIX(M, ncol, ld, NH_ROWS_ANY);
+  const colred_grid g = colred_plan(M, ncol);
+  NH_REQUIRE_PLAN(g);
+  const long long nch = g.nch;
   // scratch: pd [nch][3][ncol] | pq [nch][ncol] | pc [nch][2][ncol]
   void* base = nullptr;
   int rc = nh_scratch(ctx, (size_t)nch * ncol * 6 * 8, &base);
@@ -425,16 +384,15 @@ extern "C" int nh_column_moments(nh_ctx* ctx, const double* x, long long M, int 
   double* pd = (double*)base;
   double* pq = pd + (size_t)nch * 3 * ncol;
   long long* pc = (long long*)(pq + (size_t)nch * ncol);
+  const colred_out sums = colred_dense<k_po_sum>(pd, pc), sq = colred_dense<k_po_sq>(pq);
   hipStream_t s = ctx->stream;
-  dim3 grid((unsigned)ntile, (unsigned)nch);
-  unsigned cb = (unsigned)cdiv(ncol, PO_THREADS);
-  hipLaunchKernelGGL(k_po_sum, grid, dim3(PO_THREADS), 0, s, x, M, ncol, ld, cw, rows, pd, pc);
+  if ((rc = colred_launch<k_po_sum>(s, g, sums, x, ld))) return rc;
+  hipLaunchKernelGGL(k_po_mean, dim3(g.col_blocks()), dim3(PO_THREADS), 0, s, nch, ncol, counts, stats,
+                     sums);
   NH_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_po_mean, dim3(cb), dim3(PO_THREADS), 0, s, pd, pc, nch, ncol, counts, stats);
-  NH_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_po_sq, grid, dim3(PO_THREADS), 0, s, x, M, ncol, ld, cw, rows, stats, pq);
-  NH_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_po_var, dim3(cb), dim3(PO_THREADS), 0, s, pq, nch, ncol, counts, stats);
+  if ((rc = colred_launch<k_po_sq>(s, g, sq, x, ld, stats, ncol))) return rc;
+  hipLaunchKernelGGL(k_po_var, dim3(g.col_blocks()), dim3(PO_THREADS), 0, s, nch, ncol, counts, stats,
+                     sq);
   NH_CHECK_HIP(hipGetLastError());
   return NH_OK;
 }
@@ -443,7 +401,7 @@ extern "C" int nh_hist_columns(nh_ctx* ctx, const double* x, long long M, int nc
                                const double* edges, int nb, const int* pairs, int npairs,
                                long long* h1, long long* h2) {
   NH_REQUIRE(ctx && x && edges && h1, "null argument");
-  PO_REQUIRE_MATRIX();
+  NH_REQUIRE_MATRIX(M, ncol, ld, NH_ROWS_ANY);
   NH_REQUIRE(ncol <= NH_HIST_MAX_COLS, "ncol > NH_HIST_MAX_COLS");
   NH_REQUIRE(nb >= 1, "nb must be positive");
   NH_REQUIRE(nb <= NH_HIST_MAX_BINS_1D, "nb > NH_HIST_MAX_BINS_1D");
@@ -484,7 +442,7 @@ extern "C" int nh_hist_columns(nh_ctx* ctx, const double* x, long long M, int nc
 extern "C" int nh_kde_columns(nh_ctx* ctx, const double* x, long long M, int ncol, long long ld,
                               const double* points, int G, const double* bw, double* out) {
   NH_REQUIRE(ctx && x && points && bw && out, "null argument");
-  PO_REQUIRE_MATRIX();
+  NH_REQUIRE_MATRIX(M, ncol, ld, NH_ROWS_ANY);
   NH_REQUIRE(ncol <= 65535, "ncol > 65535");
   NH_REQUIRE(G > 0, "G must be positive");
   int gp = po_pow2_at_least(G, PO_THREADS);

@@ -24,8 +24,8 @@
 //                    chi2_obs, maxabs_rep >= maxabs_obs, runs_rep <= runs_obs; and the number of
 //                    the other rows.  An integer atomic per wave.
 //   nh_pit_columns   per column: the mean over the rows of the split-normal CDF of the datum
-//                    given the row's model (an upper limit: the fraction of rows above it), in
-//                    the tiling of nh_colred.h, the per-chunk partials added in chunk order.
+//                    given the row's model (an upper limit: the fraction of rows above it): one
+//                    chunk pass (nh_colred.h).
 //
 // No floating-point atomics: every floating-point sum has an order fixed by the shapes alone, so
 // repeated calls give bit-identical results.  Row indices are 64-bit, M < 2^31.  Every launch is
@@ -34,8 +34,6 @@
 #include "nh_philox.h"
 
 namespace {
-
-__device__ __forceinline__ double ppc_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 // ---------------------------------------------------------------- the random stream
 // (Philox4x32-10: nh_philox.h; counter word 3 = 0 is this stream's)
@@ -175,52 +173,41 @@ __device__ __forceinline__ double ppc_cdf(double y, double m, double el, double 
   return eh / w + (2.0 * el / w) * (0.5 * erf((z / el) * 0.7071067811865476));
 }
 
-// per (row chunk k, column c): part[k*ncol + c] = the chunk's sum of the CDF (of the rows above
-// the limit, for an upper limit)
-__global__ __launch_bounds__(PO_THREADS) void k_pit_sum(
-    const double* __restrict__ x, long long M, int ncol, long long ld, int cw, long long rows,
-    const double* __restrict__ conv, const double* __restrict__ flux,
-    const double* __restrict__ elo, const double* __restrict__ ehi, const int* __restrict__ ul,
-    double* __restrict__ part) {
-  __shared__ double rs[PO_THREADS];
-  int tid = threadIdx.x, tx = tid % cw, ty = tid / cw, R = PO_THREADS / cw;
-  int c = blockIdx.x * cw + tx;
-  long long k = blockIdx.y;
-  long long t0 = k * rows, t1 = min(M, t0 + rows);
-  double s = 0.0;
-  if (c < ncol) {
+// the sum of the CDF (of the rows above the limit, for an upper limit)
+struct k_pit_sum {
+  using F = colred_fields<0, '+'>;
+  const double* __restrict__ x;
+  long long ld;
+  const double* __restrict__ conv;
+  const double* __restrict__ flux;
+  const double* __restrict__ elo;
+  const double* __restrict__ ehi;
+  const int* __restrict__ ul;
+  template <class W>
+  __device__ __forceinline__ void column(int c, W walk, F::acc& a) const {
     const double cv = conv[c], f = flux[c], el = elo[c], eh = ehi[c];
     const bool lim = ul[c] != 0;
-    for (long long t = t0 + ty; t < t1; t += R) {
+    double s = 0.0;
+    walk([&](long long t) {
       const double mc = x[t * ld + c] * cv;
       s += lim ? (mc > f ? 1.0 : 0.0) : ppc_cdf(f, mc, el, eh);
-    }
+    });
+    a = {{s}};
   }
-  rs[tid] = s;
-  po_tree(rs, tid, ty, cw, [](double a, double b) { return a + b; });
-  if (ty == 0 && c < ncol) part[k * ncol + c] = rs[tid];
-}
+};
 
 // out[0][c] = pit, out[1][c] = ul_violation: the chunks in order, NaN where the other applies
-__global__ void k_pit_fin(const double* __restrict__ part, long long nch, int ncol, long long M,
-                          const int* __restrict__ ul, double* __restrict__ out) {
+__global__ void k_pit_fin(long long nch, int ncol, long long M, const int* __restrict__ ul,
+                          double* __restrict__ out, colred_out part) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncol) return;
-  double s = 0.0;
-  for (long long k = 0; k < nch; ++k) s += part[k * ncol + c];
-  const double v = s / (double)M;
+  const double v = colred_fold<k_pit_sum>(part, nch, ncol, c).d[0] / (double)M;
   const bool lim = ul[c] != 0;
-  out[c] = lim ? ppc_nan() : v;
-  out[ncol + c] = lim ? v : ppc_nan();
+  out[c] = lim ? nh_nan() : v;
+  out[ncol + c] = lim ? v : nh_nan();
 }
 
 }  // namespace
-
-#define PPC_REQUIRE_MATRIX(M, ncol, ld)                              \
-  NH_REQUIRE(M > 0, "M == 0: no samples");                         \
-  NH_REQUIRE(M < (1ll << 31), "M >= 2^31 rows");                   \
-  NH_REQUIRE(ncol > 0, "ncol must be positive");                   \
-  NH_REQUIRE(ld >= ncol, "ncol > ld")
 
 extern "C" int nh_ppc_rows(nh_ctx* ctx, const double* x, long long M, int nE, long long ld,
                            const double* conv, const double* flux, const double* elo,
@@ -228,7 +215,7 @@ extern "C" int nh_ppc_rows(nh_ctx* ctx, const double* x, long long M, int nE, lo
                            long long row0, double* Y, long long ldY, double* T) {
   NH_REQUIRE(ctx && x && conv && flux && elo && ehi && ul, "null argument");
   NH_REQUIRE(Y || T, "Y and T both NULL: nothing to write");
-  PPC_REQUIRE_MATRIX(M, nE, ld);
+  NH_REQUIRE_MATRIX(M, nE, ld, NH_ROWS_INT);
   NH_REQUIRE(!Y || ldY >= nE, "nE > ldY");
   NH_REQUIRE(row0 >= 0, "row0 < 0");
   unsigned nb = (unsigned)std::min<long long>(cdiv(M, PO_THREADS / 64), 8192);
@@ -255,21 +242,17 @@ extern "C" int nh_pit_columns(nh_ctx* ctx, const double* x, long long M, int nE,
                               const double* conv, const double* flux, const double* elo,
                               const double* ehi, const int* ul, double* out) {
   NH_REQUIRE(ctx && x && conv && flux && elo && ehi && ul && out, "null argument");
-  PPC_REQUIRE_MATRIX(M, nE, ld);
-  int cw = po_pow2_at_least(nE, 64);
-  long long ntile = cdiv(nE, cw), rows, nch;
-  po_chunks(M, ntile, PO_THREADS / cw, &rows, &nch);
-  NH_REQUIRE(nch <= 65535 && ntile < (1ll << 31), "too many columns");
+  NH_REQUIRE_MATRIX(M, nE, ld, NH_ROWS_INT);
+  const colred_grid g = colred_plan(M, nE);
+  NH_REQUIRE_PLAN(g);
   void* base = nullptr;  // scratch: part [nch][nE]
-  int rc = nh_scratch(ctx, (size_t)nch * nE * 8, &base);
+  int rc = nh_scratch(ctx, (size_t)g.nch * nE * 8, &base);
   if (rc) return rc;
-  double* part = (double*)base;
+  const colred_out part = colred_dense<k_pit_sum>((double*)base);
   hipStream_t s = ctx->stream;
-  hipLaunchKernelGGL(k_pit_sum, dim3((unsigned)ntile, (unsigned)nch), dim3(PO_THREADS), 0, s, x, M,
-                     nE, ld, cw, rows, conv, flux, elo, ehi, ul, part);
-  NH_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_pit_fin, dim3((unsigned)cdiv(nE, PO_THREADS)), dim3(PO_THREADS), 0, s, part,
-                     nch, nE, M, ul, out);
+  if ((rc = colred_launch<k_pit_sum>(s, g, part, x, ld, conv, flux, elo, ehi, ul))) return rc;
+  hipLaunchKernelGGL(k_pit_fin, dim3(g.col_blocks()), dim3(PO_THREADS), 0, s, g.nch, nE, M, ul, out,
+                     part);
   NH_CHECK_HIP(hipGetLastError());
   return NH_OK;
 }

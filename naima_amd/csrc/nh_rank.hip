@@ -26,8 +26,6 @@ namespace {
 
 constexpr int RK_NEAR = 4;                        // neighbours looked at before the binary search
 
-__device__ __forceinline__ double rk_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
 __device__ __forceinline__ long long rk_src(long long e, long long row0, long long ld,
                                             long long cstride, int npool, int p) {
   long long t = e / npool, j = e - t * npool;
@@ -65,7 +63,7 @@ __global__ __launch_bounds__(RK_THREADS) void k_rank_ties(const unsigned long lo
   int p = c0 + blockIdx.y;
   unsigned me = ic[i];
   double* dst = r + (long long)me * ncolp + p;
-  if (status[p] != 0) { *dst = rk_nan(); return; }
+  if (status[p] != 0) { *dst = nh_nan(); return; }
   unsigned long long k = kc[me];
   long long first = i, last = i;
   for (int n = 0; n < RK_NEAR && first > 0 && kc[ic[first - 1]] == k; ++n) --first;
@@ -115,7 +113,7 @@ __device__ double rk_ppnd16(double p) {
     return q * num / den;
   }
   double r = q < 0.0 ? p : 1.0 - p;  // (1 - p is exact for p >= 1/2)
-  if (!(r > 0.0)) return r == 0.0 ? (q < 0.0 ? -INFINITY : INFINITY) : rk_nan();
+  if (!(r > 0.0)) return r == 0.0 ? (q < 0.0 ? -INFINITY : INFINITY) : nh_nan();
   r = sqrt(-log(r));
   double num, den;
   if (r <= 5.0) {
@@ -177,7 +175,7 @@ __global__ __launch_bounds__(RK_THREADS) void k_rank_scores(const double* __rest
     long long e = i / ncolp;
     int p = (int)(i - e * ncolp);
     double v = r[i];
-    double s = v != v ? rk_nan() : rk_ppnd16((v - 0.375) / denom);
+    double s = v != v ? nh_nan() : rk_ppnd16((v - 0.375) / denom);
     z[layout == NH_RANK_CHAIN ? rk_chain_at(e, p, npool, ldz, cstride) : i] = s;
   }
 }
@@ -196,7 +194,7 @@ __global__ __launch_bounds__(RK_THREADS) void k_rank_transform(const double* __r
     double v = x[rk_src(e, row0, ld, cstride, npool, p)], q = thr[p];
     double o;
     if (mode == NH_RANK_FOLD) o = fabs(v - q);
-    else o = (v != v || q != q) ? rk_nan() : (v <= q ? 1.0 : 0.0);
+    else o = (v != v || q != q) ? nh_nan() : (v <= q ? 1.0 : 0.0);
     out[rk_chain_at(e, p, npool, ldo, cstride)] = o;
   }
 }

@@ -12,8 +12,8 @@
 //                           the tail rows (an integer atomic counter); one workgroup per column
 //                           sorts, fits and smooths the tail (nh_gpd.h) and writes the tail's
 //                           log-weights; a last pass writes the others and sums exp(2 lw).
-//   nh_weighted_moments     count, weighted mean and weighted variance per column: two passes in
-//                           the tiling of nh_colred.h, per-chunk partials added in chunk order.
+//   nh_weighted_moments     count, weighted mean and weighted variance per column: two chunk
+//                           passes (nh_colred.h).
 //   nh_weighted_select      weighted order statistics: the radix sort of (key, row index) of
 //                           nh_radix.h per column, zero-weight rows keyed behind everything; then
 //                           the running sum of the weights in sorted order (below) picks the rows.
@@ -61,54 +61,36 @@ __global__ __launch_bounds__(PO_THREADS) void k_rw_row_sums(const double* __rest
 }
 
 // ---------------------------------------------------------------- PSIS weights
-// per (row chunk k, column c): pm[k*ncol + c] = the maximum (NaNs passed over), pc[(k*2 + 0|1)*ncol
-// + c] = the number of NaN or +inf entries, of finite ones
-__global__ __launch_bounds__(PO_THREADS) void k_rw_max(const double* __restrict__ x, long long M,
-                                                      int ncol, long long ld, int cw, long long rows,
-                                                      double* __restrict__ pm,
-                                                      long long* __restrict__ pc) {
-  __shared__ double rhi[PO_THREADS];
-  __shared__ long long rbad[PO_THREADS], rfin[PO_THREADS];
-  int tid = threadIdx.x, tx = tid % cw, ty = tid / cw, R = PO_THREADS / cw;
-  int c = blockIdx.x * cw + tx;
-  long long k = blockIdx.y;
-  long long t0 = k * rows, t1 = min(M, t0 + rows);
-  double hi = -INFINITY;
-  long long bad = 0, fin = 0;
-  if (c < ncol) {
-    for (long long t = t0 + ty; t < t1; t += R) {
+// (the chunk passes, their partials and the fold in chunk order: nh_colred.h)
+// the maximum (NaNs passed over) | the number of NaN or +inf entries, of finite ones
+struct k_rw_max {
+  using F = colred_fields<2, '>'>;
+  const double* __restrict__ x;
+  long long ld;
+  template <class W>
+  __device__ __forceinline__ void column(int c, W walk, F::acc& a) const {
+    double hi = -INFINITY;
+    long long bad = 0, fin = 0;
+    walk([&](long long t) {
       double v = x[t * ld + c];
       hi = fmax(hi, v);
-      if (po_finite(v)) ++fin;
-      else if (!(v == -INFINITY)) ++bad;
-    }
+      const bool f = po_finite(v);  // (each counter moves in every row: nh_colred.h)
+      fin += f ? 1 : 0;
+      bad += (f || v == -INFINITY) ? 0 : 1;
+    });
+    a = {{hi}, {bad, fin}};
   }
-  rhi[tid] = hi; rbad[tid] = bad; rfin[tid] = fin;
-  po_tree(rhi, tid, ty, cw, [](double a, double b) { return fmax(a, b); });
-  po_tree(rbad, tid, ty, cw, [](long long a, long long b) { return a + b; });
-  po_tree(rfin, tid, ty, cw, [](long long a, long long b) { return a + b; });
-  if (ty == 0 && c < ncol) {
-    pm[k * ncol + c] = rhi[tid];
-    pc[(k * 2 + 0) * ncol + c] = rbad[tid];
-    pc[(k * 2 + 1) * ncol + c] = rfin[tid];
-  }
-}
+};
 
 // cst[0][c] = the column's maximum; status[c] = its NaN and +inf entries, M for a column without
 // a finite entry (every one of its -inf entries offends), 0 for a column that gets weights
-__global__ void k_rw_max_fin(const double* __restrict__ pm, const long long* __restrict__ pc,
-                             long long nch, int ncol, long long M, double* __restrict__ cst,
-                             int* __restrict__ status) {
+__global__ void k_rw_max_fin(long long nch, int ncol, long long M, double* __restrict__ cst,
+                             int* __restrict__ status, colred_out part) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncol) return;
-  double hi = -INFINITY;
-  long long bad = 0, fin = 0;
-  for (long long k = 0; k < nch; ++k) {
-    hi = fmax(hi, pm[k * ncol + c]);
-    bad += pc[(k * 2 + 0) * ncol + c];
-    fin += pc[(k * 2 + 1) * ncol + c];
-  }
-  cst[c] = hi;
+  const auto a = colred_fold<k_rw_max>(part, nch, ncol, c);
+  const long long bad = a.n[0], fin = a.n[1];
+  cst[c] = a.d[0];
   status[c] = (int)(bad ? bad : (fin ? 0 : M));
 }
 
@@ -118,24 +100,27 @@ __device__ __forceinline__ double rw_cut(double hi, double lsel) {
   return fmax(lsel - hi, CRIT_LOG_TINY);
 }
 
-// per (row chunk k, column c): part[(k*3 + 0|2)*ncol + c] = the sums of exp(x) over the rows with
-// x <= cut and over all rows (slot 1 is k_rw_write's); the rows with x > cut go to the column's
-// list tx / trow [c*cap ..], their number to cnt[c] (zeroed before the launch)
-__global__ __launch_bounds__(PO_THREADS) void k_rw_split(
-    const double* __restrict__ lr, long long M, int ncol, long long ld, int cw, long long rows,
-    const double* __restrict__ cst, const int* __restrict__ status, const double* __restrict__ lsel,
-    int cap, double* __restrict__ part, double* __restrict__ tx, int* __restrict__ trow,
-    unsigned* __restrict__ cnt) {
-  __shared__ double ra[PO_THREADS], rr[PO_THREADS];
-  int tid = threadIdx.x, txc = tid % cw, ty = tid / cw, R = PO_THREADS / cw;
-  int c = blockIdx.x * cw + txc;
-  long long k = blockIdx.y;
-  long long t0 = k * rows, t1 = min(M, t0 + rows);
-  double a = 0.0, r = 0.0;
-  if (c < ncol && status[c] == 0) {
+// the sums of exp(x) over the rows with x <= cut and over all rows (slots 0 and 2 of part
+// [nch][3][ncol]; slot 1 is k_rw_write's); the rows with x > cut go to the column's list
+// tx / trow [c*cap ..], their number to cnt[c] (zeroed before the launch)
+struct k_rw_split {
+  using F = colred_fields<0, '+', '+'>;
+  const double* __restrict__ lr;
+  long long ld;
+  const double* __restrict__ cst;
+  const int* __restrict__ status;
+  const double* __restrict__ lsel;
+  int cap;
+  double* __restrict__ tx;
+  int* __restrict__ trow;
+  unsigned* __restrict__ cnt;
+  template <class W>
+  __device__ __forceinline__ void column(int c, W walk, F::acc& a) const {
+    if (status[c] != 0) return;
     const double hi = cst[c];
     const double cut = rw_cut(hi, lsel[c]);
-    for (long long t = t0 + ty; t < t1; t += R) {
+    double sa = 0.0, r = 0.0;
+    walk([&](long long t) {
       const double xv = lr[t * ld + c] - hi;
       const double e = exp(xv);
       r += e;
@@ -147,18 +132,12 @@ __global__ __launch_bounds__(PO_THREADS) void k_rw_split(
           trow[(long long)c * cap + slot] = (int)t;
         }
       } else {
-        a += e;
+        sa += e;
       }
-    }
+    });
+    a = {{sa, r}};
   }
-  ra[tid] = a; rr[tid] = r;
-  po_tree(ra, tid, ty, cw, [](double p, double q) { return p + q; });
-  po_tree(rr, tid, ty, cw, [](double p, double q) { return p + q; });
-  if (ty == 0 && c < ncol) {
-    part[(k * 3 + 0) * ncol + c] = ra[tid];
-    part[(k * 3 + 2) * ncol + c] = rr[tid];
-  }
-}
+};
 
 // one workgroup per column: sort the tail, fit, smooth; the normaliser and the mean ratio; the
 // tail rows' log-weights.  cst[1][c] = logsumexp(x) for k_rw_write, cst[2][c] = the tail's sum of
@@ -166,7 +145,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_rw_split(
 // where one ratio towers over the rest).
 __global__ __launch_bounds__(PO_THREADS) void k_rw_tail(
     int ncol, long long M, long long nch, int cap, double* __restrict__ cst,
-    const int* __restrict__ status, const double* __restrict__ lsel, const double* __restrict__ part,
+    const int* __restrict__ status, const double* __restrict__ lsel, colred_out part,
     const double* __restrict__ tx, const int* __restrict__ trow, const unsigned* __restrict__ cnt,
     double* __restrict__ lw, long long ldw, double* __restrict__ pareto_k,
     long long* __restrict__ n_tail, double* __restrict__ lmean) {
@@ -175,7 +154,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_rw_tail(
   const int c = blockIdx.x;
   if (status[c] != 0) {  // (the workgroup's: no barrier is skipped by a part of it)
     if (tid == 0) {
-      pareto_k[c] = lmean[c] = cst[ncol + c] = cst[2 * ncol + c] = crit_nan();
+      pareto_k[c] = lmean[c] = cst[ncol + c] = cst[2 * ncol + c] = nh_nan();
       n_tail[c] = 0;
     }
     return;
@@ -191,11 +170,8 @@ __global__ __launch_bounds__(PO_THREADS) void k_rw_tail(
   for (int i = tid; i < n; i += PO_THREADS) a += exp(xs[i]);
   a = crit_block_reduce(a, s.red, tid, [](double p, double q) { return p + q; });
   if (tid == 0) {
-    double an = 0.0, rn = 0.0;
-    for (long long k = 0; k < nch; ++k) {
-      an += part[(k * 3 + 0) * ncol + c];
-      rn += part[(k * 3 + 2) * ncol + c];
-    }
+    const auto sums = colred_fold<k_rw_split>(part, nch, ncol, c);
+    const double an = sums.d[0], rn = sums.d[1];
     const double lz = log(an + a);
     pareto_k[c] = kpar;
     n_tail[c] = n;
@@ -215,70 +191,64 @@ __global__ __launch_bounds__(PO_THREADS) void k_rw_tail(
   if (tid == 0) cst[2 * ncol + c] = b;
 }
 
-// lw = x - logsumexp(x) of the rows below the cutoff, and part[(k*3 + 1)*ncol + c] = the chunk's
-// sum of exp(2 lw) over them; NaN in every row of a column without weights
-__global__ __launch_bounds__(PO_THREADS) void k_rw_write(
-    const double* __restrict__ lr, long long M, int ncol, long long ld, int cw, long long rows,
-    const double* __restrict__ cst, const int* __restrict__ status, const double* __restrict__ lsel,
-    double* __restrict__ lw, long long ldw, double* __restrict__ part) {
-  __shared__ double rb[PO_THREADS];
-  int tid = threadIdx.x, txc = tid % cw, ty = tid / cw, R = PO_THREADS / cw;
-  int c = blockIdx.x * cw + txc;
-  long long k = blockIdx.y;
-  long long t0 = k * rows, t1 = min(M, t0 + rows);
-  double b = 0.0;
-  if (c < ncol) {
+// lw = x - logsumexp(x) of the rows below the cutoff, and the sum of exp(2 lw) over them (slot 1
+// of part); NaN in every row of a column without weights
+struct k_rw_write {
+  using F = colred_fields<0, '+'>;
+  const double* __restrict__ lr;
+  long long ld;
+  const double* __restrict__ cst;
+  const int* __restrict__ status;
+  const double* __restrict__ lsel;
+  int ncol;
+  double* __restrict__ lw;
+  long long ldw;
+  template <class W>
+  __device__ __forceinline__ void column(int c, W walk, F::acc& a) const {
     if (status[c] != 0) {
-      for (long long t = t0 + ty; t < t1; t += R) lw[t * ldw + c] = crit_nan();
-    } else {
-      const double hi = cst[c], lz = cst[ncol + c];
-      const double cut = rw_cut(hi, lsel[c]);
-      for (long long t = t0 + ty; t < t1; t += R) {
-        const double xv = lr[t * ld + c] - hi;
-        if (!(xv > cut)) {
-          const double l = xv - lz;
-          lw[t * ldw + c] = l;
-          b += exp(2.0 * l);
-        }
-      }
+      walk([&](long long t) { lw[t * ldw + c] = nh_nan(); });
+      return;
     }
+    const double hi = cst[c], lz = cst[ncol + c];
+    const double cut = rw_cut(hi, lsel[c]);
+    double b = 0.0;
+    walk([&](long long t) {
+      const double xv = lr[t * ld + c] - hi;
+      if (!(xv > cut)) {
+        const double l = xv - lz;
+        lw[t * ldw + c] = l;
+        b += exp(2.0 * l);
+      }
+    });
+    a = {{b}};
   }
-  rb[tid] = b;
-  po_tree(rb, tid, ty, cw, [](double p, double q) { return p + q; });
-  if (ty == 0 && c < ncol) part[(k * 3 + 1) * ncol + c] = rb[tid];
-}
+};
 
 // ess[c] = 1 / sum_s exp(2 lw): the chunks in chunk order, then the tail; NaN without weights
-__global__ void k_rw_ess(const double* __restrict__ part, long long nch, int ncol,
-                         const double* __restrict__ cst, const int* __restrict__ status,
-                         double* __restrict__ ess) {
+__global__ void k_rw_ess(long long nch, int ncol, const double* __restrict__ cst,
+                         const int* __restrict__ status, double* __restrict__ ess, colred_out part) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncol) return;
-  double b = 0.0;
-  for (long long k = 0; k < nch; ++k) b += part[(k * 3 + 1) * ncol + c];
-  ess[c] = status[c] != 0 ? crit_nan() : 1.0 / (b + cst[2 * ncol + c]);
+  const double b = colred_fold<k_rw_write>(part, nch, ncol, c).d[0];
+  ess[c] = status[c] != 0 ? nh_nan() : 1.0 / (b + cst[2 * ncol + c]);
 }
 
 // ---------------------------------------------------------------- weighted moments
-// per (row chunk k, column c) over the rows with lw > -inf: pd[(k*4 + 0..3)*ncol + c] = the sums
-// of w and of w x, min and max of x; pc[(k*2 + 0|1)*ncol + c] = their number, that of non-finite x
-__global__ __launch_bounds__(PO_THREADS) void k_rw_wsum(const double* __restrict__ x, long long M,
-                                                       int ncol, long long ld,
-                                                       const double* __restrict__ lw, long long ldw,
-                                                       int cw, long long rows, double* __restrict__ pd,
-                                                       long long* __restrict__ pc) {
-  __shared__ double rw[PO_THREADS], rs[PO_THREADS], rlo[PO_THREADS], rhi[PO_THREADS];
-  __shared__ long long rn[PO_THREADS], rbad[PO_THREADS];
-  int tid = threadIdx.x, tx = tid % cw, ty = tid / cw, R = PO_THREADS / cw;
-  int c = blockIdx.x * cw + tx;
-  long long k = blockIdx.y;
-  long long t0 = k * rows, t1 = min(M, t0 + rows);
-  double sw = 0.0, s = 0.0, lo = INFINITY, hi = -INFINITY;
-  long long n = 0, bad = 0;
-  if (c < ncol) {
-    for (long long t = t0 + ty; t < t1; t += R) {
+// over the rows with lw > -inf: the sums of w and of w x, min and max of x | their number, that
+// of non-finite x
+struct k_rw_wsum {
+  using F = colred_fields<2, '+', '+', '<', '>'>;
+  const double* __restrict__ x;
+  long long ld;
+  const double* __restrict__ lw;
+  long long ldw;
+  template <class W>
+  __device__ __forceinline__ void column(int c, W walk, F::acc& a) const {
+    double sw = 0.0, s = 0.0, lo = INFINITY, hi = -INFINITY;
+    long long n = 0, bad = 0;
+    walk([&](long long t) {
       const double l = lw[t * ldw];
-      if (l == -INFINITY) continue;
+      if (l == -INFINITY) return;
       const double w = exp(l), v = x[t * ld + c];
       sw += w;
       s += w * v;
@@ -286,85 +256,58 @@ __global__ __launch_bounds__(PO_THREADS) void k_rw_wsum(const double* __restrict
       hi = fmax(hi, v);
       ++n;
       bad += po_finite(v) ? 0 : 1;
-    }
+    });
+    a = {{sw, s, lo, hi}, {n, bad}};
   }
-  rw[tid] = sw; rs[tid] = s; rlo[tid] = lo; rhi[tid] = hi; rn[tid] = n; rbad[tid] = bad;
-  po_tree(rw, tid, ty, cw, [](double a, double b) { return a + b; });
-  po_tree(rs, tid, ty, cw, [](double a, double b) { return a + b; });
-  po_tree(rlo, tid, ty, cw, [](double a, double b) { return fmin(a, b); });
-  po_tree(rhi, tid, ty, cw, [](double a, double b) { return fmax(a, b); });
-  po_tree(rn, tid, ty, cw, [](long long a, long long b) { return a + b; });
-  po_tree(rbad, tid, ty, cw, [](long long a, long long b) { return a + b; });
-  if (ty == 0 && c < ncol) {
-    pd[(k * 4 + 0) * ncol + c] = rw[tid];
-    pd[(k * 4 + 1) * ncol + c] = rs[tid];
-    pd[(k * 4 + 2) * ncol + c] = rlo[tid];
-    pd[(k * 4 + 3) * ncol + c] = rhi[tid];
-    pc[(k * 2 + 0) * ncol + c] = rn[tid];
-    pc[(k * 2 + 1) * ncol + c] = rbad[tid];
-  }
-}
+};
 
 // out[0|1][c] = the number of rows with positive weight, the weighted mean (the value itself
 // where all are equal; NaN with a non-finite value or without a row); mst[0|1][c] = the sum of
 // the weights, 1 where the variance is exactly 0 / 0 where it is a quotient / -1 where it is NaN
-__global__ void k_rw_wmean(const double* __restrict__ pd, const long long* __restrict__ pc,
-                           long long nch, int ncol, double* __restrict__ out,
-                           double* __restrict__ mst) {
+__global__ void k_rw_wmean(long long nch, int ncol, double* __restrict__ out,
+                           double* __restrict__ mst, colred_out part) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncol) return;
-  double sw = 0.0, s = 0.0, lo = INFINITY, hi = -INFINITY;
-  long long n = 0, bad = 0;
-  for (long long k = 0; k < nch; ++k) {
-    sw += pd[(k * 4 + 0) * ncol + c];
-    s += pd[(k * 4 + 1) * ncol + c];
-    lo = fmin(lo, pd[(k * 4 + 2) * ncol + c]);
-    hi = fmax(hi, pd[(k * 4 + 3) * ncol + c]);
-    n += pc[(k * 2 + 0) * ncol + c];
-    bad += pc[(k * 2 + 1) * ncol + c];
-  }
+  const auto a = colred_fold<k_rw_wsum>(part, nch, ncol, c);
+  const double sw = a.d[0], s = a.d[1], lo = a.d[2], hi = a.d[3];
+  const long long n = a.n[0], bad = a.n[1];
   const bool none = bad || n == 0;
   out[c] = (double)n;
-  out[ncol + c] = none ? crit_nan() : (lo == hi ? lo : s / sw);
+  out[ncol + c] = none ? nh_nan() : (lo == hi ? lo : s / sw);
   mst[c] = sw;
   mst[ncol + c] = none ? -1.0 : (lo == hi ? 1.0 : 0.0);
 }
 
-// pq[k*ncol + c] = the chunk's sum of w (x - mean)^2 over the rows with lw > -inf
-__global__ __launch_bounds__(PO_THREADS) void k_rw_wsq(const double* __restrict__ x, long long M,
-                                                      int ncol, long long ld,
-                                                      const double* __restrict__ lw, long long ldw,
-                                                      int cw, long long rows,
-                                                      const double* __restrict__ out,
-                                                      double* __restrict__ pq) {
-  __shared__ double rq[PO_THREADS];
-  int tid = threadIdx.x, tx = tid % cw, ty = tid / cw, R = PO_THREADS / cw;
-  int c = blockIdx.x * cw + tx;
-  long long k = blockIdx.y;
-  long long t0 = k * rows, t1 = min(M, t0 + rows);
-  double q = 0.0;
-  if (c < ncol) {
+// the sum of w (x - mean)^2 over the rows with lw > -inf
+struct k_rw_wsq {
+  using F = colred_fields<0, '+'>;
+  const double* __restrict__ x;
+  long long ld;
+  const double* __restrict__ lw;
+  long long ldw;
+  const double* __restrict__ out;
+  int ncol;
+  template <class W>
+  __device__ __forceinline__ void column(int c, W walk, F::acc& a) const {
     const double mean = out[ncol + c];
-    for (long long t = t0 + ty; t < t1; t += R) {
+    double q = 0.0;
+    walk([&](long long t) {
       const double l = lw[t * ldw];
-      if (l == -INFINITY) continue;
+      if (l == -INFINITY) return;
       const double d = x[t * ld + c] - mean;
       q += exp(l) * (d * d);
-    }
+    });
+    a = {{q}};
   }
-  rq[tid] = q;
-  po_tree(rq, tid, ty, cw, [](double a, double b) { return a + b; });
-  if (ty == 0 && c < ncol) pq[k * ncol + c] = rq[tid];
-}
+};
 
-__global__ void k_rw_wvar(const double* __restrict__ pq, long long nch, int ncol,
-                          const double* __restrict__ mst, double* __restrict__ out) {
+__global__ void k_rw_wvar(long long nch, int ncol, const double* __restrict__ mst,
+                          double* __restrict__ out, colred_out part) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncol) return;
-  double q = 0.0;
-  for (long long k = 0; k < nch; ++k) q += pq[k * ncol + c];
+  const double q = colred_fold<k_rw_wsq>(part, nch, ncol, c).d[0];
   const double kind = mst[ncol + c];
-  out[2 * ncol + c] = kind < 0.0 ? crit_nan() : (kind > 0.0 ? 0.0 : q / mst[c]);
+  out[2 * ncol + c] = kind < 0.0 ? nh_nan() : (kind > 0.0 ? 0.0 : q / mst[c]);
 }
 
 // ---------------------------------------------------------------- the running sum of weights
@@ -425,8 +368,8 @@ __global__ void k_rw_tile_scan(const double* __restrict__ bsum, unsigned nblk, i
     run = run + bsum[(long long)j * nblk + b];
   }
   if (out && (nanflag[j] != 0 || !(run > 0.0))) {
-    for (int r = 0; r < nq; ++r) out[(long long)r * ncol + c0 + j] = crit_nan();
-    run = crit_nan();
+    for (int r = 0; r < nq; ++r) out[(long long)r * ncol + c0 + j] = nh_nan();
+    run = nh_nan();
   }
   total[j] = run;
 }
@@ -541,16 +484,10 @@ unsigned rw_grid(long long n) {
 
 }  // namespace
 
-#define RW_REQUIRE_MATRIX(M, ncol, ld)                             \
-  NH_REQUIRE(M > 0, "M == 0: no samples");                         \
-  NH_REQUIRE(M < (1ll << 31), "M >= 2^31 rows");                   \
-  NH_REQUIRE(ncol > 0, "ncol must be positive");                   \
-  NH_REQUIRE(ld >= ncol, "ncol > ld")
-
 extern "C" int nh_row_sums_select(nh_ctx* ctx, const double* L, long long M, int ncol, long long ld,
                                   const int* cols, int n, int sign, double* out, long long ldo) {
   NH_REQUIRE(ctx && L && out && (cols || n == 0), "null argument");
-  RW_REQUIRE_MATRIX(M, ncol, ld);
+  NH_REQUIRE_MATRIX(M, ncol, ld, NH_ROWS_INT);
   NH_REQUIRE(n >= 0, "n must not be negative");
   NH_REQUIRE(sign == 1 || sign == -1, "sign must be +1 or -1");
   NH_REQUIRE(ldo >= 1, "ldo must be positive");
@@ -576,15 +513,14 @@ extern "C" int nh_psis_weights(nh_ctx* ctx, const double* lr, long long M, int n
                                int* status) {
   NH_REQUIRE(ctx && lr && lsel && lw && pareto_k && n_tail && ess && lmean && status,
              "null argument");
-  RW_REQUIRE_MATRIX(M, ncol, ld);
+  NH_REQUIRE_MATRIX(M, ncol, ld, NH_ROWS_INT);
   NH_REQUIRE(ldw >= ncol, "ncol > ldw");
   NH_REQUIRE(Mt >= 0 && Mt < M, "Mt outside [0, M)");
   NH_REQUIRE(Mt <= NH_PSIS_MAX_TAIL, "Mt > NH_PSIS_MAX_TAIL: thin the chain");
   const int cap = std::max(Mt, 1);
-  int cw = po_pow2_at_least(ncol, 64);
-  long long ntile = cdiv(ncol, cw), rows, nch;
-  po_chunks(M, ntile, PO_THREADS / cw, &rows, &nch);
-  NH_REQUIRE(nch <= 65535 && ntile < (1ll << 31), "too many columns");
+  const colred_grid g = colred_plan(M, ncol);
+  NH_REQUIRE_PLAN(g);
+  const long long nch = g.nch;
   // scratch: part [nch][3][ncol] (its first third is k_rw_max's pm before) | pc [nch][2][ncol] |
   // cst [3][ncol] | tx [ncol][cap] | trow [ncol][cap] | cnt [ncol]
   const size_t npart = (size_t)nch * 3 * ncol, npc = (size_t)nch * 2 * ncol;
@@ -600,24 +536,20 @@ extern "C" int nh_psis_weights(nh_ctx* ctx, const double* lr, long long M, int n
   int* trow = (int*)(tx + nlist);
   unsigned* cnt = (unsigned*)(trow + nlist);
   hipStream_t s = ctx->stream;
-  const dim3 grid((unsigned)ntile, (unsigned)nch);
-  const unsigned cb = (unsigned)cdiv(ncol, PO_THREADS);
+  const unsigned cb = g.col_blocks();
+  const colred_out maxes = colred_dense<k_rw_max>(part, pc);
+  const colred_out sums = {part, nullptr, 3, 2}, sq = {part + ncol, nullptr, 3, 1};  // slots 0, 2 | 1
   NH_CHECK_HIP(hipMemsetAsync(cnt, 0, (size_t)ncol * 4, s));
-  hipLaunchKernelGGL(k_rw_max, grid, dim3(PO_THREADS), 0, s, lr, M, ncol, ld, cw, rows, part, pc);
+  if ((rc = colred_launch<k_rw_max>(s, g, maxes, lr, ld))) return rc;
+  hipLaunchKernelGGL(k_rw_max_fin, dim3(cb), dim3(PO_THREADS), 0, s, nch, ncol, M, cst, status, maxes);
   NH_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_rw_max_fin, dim3(cb), dim3(PO_THREADS), 0, s, part, pc, nch, ncol, M, cst,
-                     status);
-  NH_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_rw_split, grid, dim3(PO_THREADS), 0, s, lr, M, ncol, ld, cw, rows, cst, status,
-                     lsel, cap, part, tx, trow, cnt);
-  NH_CHECK_HIP(hipGetLastError());
+  if ((rc = colred_launch<k_rw_split>(s, g, sums, lr, ld, cst, status, lsel, cap, tx, trow, cnt)))
+    return rc;
   hipLaunchKernelGGL(k_rw_tail, dim3((unsigned)ncol), dim3(PO_THREADS), 0, s, ncol, M, nch, cap, cst,
-                     status, lsel, part, tx, trow, cnt, lw, ldw, pareto_k, n_tail, lmean);
+                     status, lsel, sums, tx, trow, cnt, lw, ldw, pareto_k, n_tail, lmean);
   NH_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_rw_write, grid, dim3(PO_THREADS), 0, s, lr, M, ncol, ld, cw, rows, cst, status,
-                     lsel, lw, ldw, part);
-  NH_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_rw_ess, dim3(cb), dim3(PO_THREADS), 0, s, part, nch, ncol, cst, status, ess);
+  if ((rc = colred_launch<k_rw_write>(s, g, sq, lr, ld, cst, status, lsel, ncol, lw, ldw))) return rc;
+  hipLaunchKernelGGL(k_rw_ess, dim3(cb), dim3(PO_THREADS), 0, s, nch, ncol, cst, status, ess, sq);
   NH_CHECK_HIP(hipGetLastError());
   return NH_OK;
 }
@@ -625,12 +557,11 @@ extern "C" int nh_psis_weights(nh_ctx* ctx, const double* lr, long long M, int n
 extern "C" int nh_weighted_moments(nh_ctx* ctx, const double* x, long long M, int ncol, long long ld,
                                    const double* lw, long long ldw, double* out) {
   NH_REQUIRE(ctx && x && lw && out, "null argument");
-  RW_REQUIRE_MATRIX(M, ncol, ld);
+  NH_REQUIRE_MATRIX(M, ncol, ld, NH_ROWS_INT);
   NH_REQUIRE(ldw >= 1, "ldw must be positive");
-  int cw = po_pow2_at_least(ncol, 64);
-  long long ntile = cdiv(ncol, cw), rows, nch;
-  po_chunks(M, ntile, PO_THREADS / cw, &rows, &nch);
-  NH_REQUIRE(nch <= 65535 && ntile < (1ll << 31), "too many columns");
+  const colred_grid g = colred_plan(M, ncol);
+  NH_REQUIRE_PLAN(g);
+  const long long nch = g.nch;
   // scratch: pd [nch][4][ncol] | pc [nch][2][ncol] | pq [nch][ncol] | mst [2][ncol]
   const size_t nc = (size_t)nch * ncol;
   void* base = nullptr;
@@ -641,15 +572,13 @@ extern "C" int nh_weighted_moments(nh_ctx* ctx, const double* x, long long M, in
   double* pq = (double*)(pc + nc * 2);
   double* mst = pq + nc;
   hipStream_t s = ctx->stream;
-  const dim3 grid((unsigned)ntile, (unsigned)nch);
-  const unsigned cb = (unsigned)cdiv(ncol, PO_THREADS);
-  hipLaunchKernelGGL(k_rw_wsum, grid, dim3(PO_THREADS), 0, s, x, M, ncol, ld, lw, ldw, cw, rows, pd, pc);
+  const unsigned cb = g.col_blocks();
+  const colred_out sums = colred_dense<k_rw_wsum>(pd, pc), sq = colred_dense<k_rw_wsq>(pq);
+  if ((rc = colred_launch<k_rw_wsum>(s, g, sums, x, ld, lw, ldw))) return rc;
+  hipLaunchKernelGGL(k_rw_wmean, dim3(cb), dim3(PO_THREADS), 0, s, nch, ncol, out, mst, sums);
   NH_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_rw_wmean, dim3(cb), dim3(PO_THREADS), 0, s, pd, pc, nch, ncol, out, mst);
-  NH_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_rw_wsq, grid, dim3(PO_THREADS), 0, s, x, M, ncol, ld, lw, ldw, cw, rows, out, pq);
-  NH_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_rw_wvar, dim3(cb), dim3(PO_THREADS), 0, s, pq, nch, ncol, mst, out);
+  if ((rc = colred_launch<k_rw_wsq>(s, g, sq, x, ld, lw, ldw, out, ncol))) return rc;
+  hipLaunchKernelGGL(k_rw_wvar, dim3(cb), dim3(PO_THREADS), 0, s, nch, ncol, mst, out, sq);
   NH_CHECK_HIP(hipGetLastError());
   return NH_OK;
 }
@@ -658,7 +587,7 @@ extern "C" int nh_weighted_select(nh_ctx* ctx, const double* x, long long M, int
                                   const double* lw, long long ldw, const double* q, int nq,
                                   double* out) {
   NH_REQUIRE(ctx && x && lw && q && out, "null argument");
-  RW_REQUIRE_MATRIX(M, ncol, ld);
+  NH_REQUIRE_MATRIX(M, ncol, ld, NH_ROWS_INT);
   NH_REQUIRE(ldw >= 1, "ldw must be positive");
   NH_REQUIRE(nq >= 1 && nq <= RW_MAX_Q, "nq must be in [1, 16]");
   rw_q qs = {};

@@ -34,7 +34,7 @@ __device__ __forceinline__ unsigned long long sel_key(double v) {
 }
 
 __device__ __forceinline__ double sel_value(unsigned long long k) {
-  if (k == ~0ull) return __longlong_as_double(0x7ff8000000000000ll);
+  if (k == ~0ull) return nh_nan();
   unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
   return __longlong_as_double((long long)b);
 }
