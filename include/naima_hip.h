@@ -948,6 +948,34 @@ int nh_pairabs_apply(nh_ctx* ctx, const nh_pair_field* fields /*host*/, int nfie
                      const nh_comp* comps /*host*/, int ncomp, const double* colfac, int write_tau,
                      int N, int m, double* out, int ldo);
 
+/* ---- synchrotron self-absorption of a homogeneous one-zone source, per walker ----------------
+ * (new: the reference has none.)  For N(gamma) particles per unit Lorentz factor in a volume V,
+ *   alpha(E) V = kappa(E) = pi^2 hbar^3 CS1(E) / (m_e E) trapz_loglog((N/gamma) H(x), gamma)
+ *   H = 2 Gtilde(x) (1 - dln Gtilde / dln x),  x = E / Ec(gamma, B)
+ * (the form integrated by parts: no derivative of N, non-negative node by node) with CS1, Ec and
+ * Gtilde those of nh_synchrotron.  FP64, deterministic, no atomics, no scratch.
+ * nh_syn_absorption: out[w*ldo+k] = kappa_w(E_eV[k]) in cm^2.  The arguments, the refusals and
+ *   the rules of nh_synchrotron: a zero node kills its segments, a NaN weight in an energy's live
+ *   range makes it NaN, a node with x > 746 is dead, B <= 0, NaN or +-inf gives a NaN row.  A
+ *   kernel of its own at the launch shape nh_synchrotron_plan gives without the epilogue, which
+ *   nh_syn_absorption_plan reports.
+ * nh_ssa_apply: out[w*ldo+k] = f(tau_w[k]) * colfac[k] * sum_j comps[j] (ncomp 0..8; no terms:
+ *   the escape fraction itself; write_tau: tau itself, which takes no terms and no colfac) from
+ *   kappa[w*ldk + k] (ldk = 0: one shared row) and the lazy radius R_cm(w):
+ *   NH_SSA_SPHERE  tau = 3 kappa / (2 pi R^2) along a diameter, f = 3 u / tau,
+ *                  u = 1/2 + exp(-tau)/tau - (1 - exp(-tau))/tau^2 (Gould 1979); below tau = 1 the
+ *                  series 1 - 3 tau/8 + tau^2/10 - ... (20 terms)
+ *   NH_SSA_SLAB    a face-on cylinder of face radius R: tau = kappa / (pi R^2), f = -expm1(-tau)/tau
+ *   kappa = 0 gives exactly 1, a NaN kappa NaN; a walker with R <= 0, NaN or +-inf a NaN row. */
+enum { NH_SSA_SPHERE = 0, NH_SSA_SLAB = 1 };
+int nh_syn_absorption(nh_ctx* ctx, const double* w, const double* dlw, const double* B_G, int ldB,
+                      int N, const double* gam, const double* lx, int nG,
+                      const double* E_eV, int nE, double* out, int ldo);
+int nh_syn_absorption_plan(int N, int nG, int nE, int* C, int* tw, int* ktiles, int* lds_bytes);
+int nh_ssa_apply(nh_ctx* ctx, const double* kappa, long long ldk, const nh_lazy* R_cm /*host*/,
+                 int geometry, const nh_comp* comps /*host*/, int ncomp, const double* colfac,
+                 int write_tau, int N, int m, double* out, int ldo);
+
 /* ---- cooled electron populations, per walker -------------------------------------------------
  * (new: the reference has none.)  An injection rate Q(E) [1/(eV s)] switched on for age_s under
  * the loss rate b(E) = (4/3) sigma_T c (B^2/8 pi) gamma^2 + sum_f u_f loss_f(E) [eV/s] leaves

@@ -13,7 +13,8 @@ from .core import (lnprob, lnprobmodel, log_uniform_prior, normal_prior,  # noqa
                    uniform_prior, get_sampler, run_sampler)
 from .models import (BrokenPowerLaw, ExponentialCutoffBrokenPowerLaw,  # noqa: F401
                      ExponentialCutoffPowerLaw, LogParabola, PowerLaw, TableModel,
-                     EblAbsorptionModel, PairAbsorptionModel, CooledElectrons)
+                     EblAbsorptionModel, PairAbsorptionModel, CooledElectrons,
+                     SynchrotronSelfAbsorption)
 from .radiative import (Bremsstrahlung, InverseCompton, PionDecay,  # noqa: F401
                         PionDecayKelner06, SecondaryLeptonsKelner06, Synchrotron)
 from .analysis import (find_ML, read_run, save_diagnostic_plots,  # noqa: F401

@@ -18,6 +18,7 @@ if os.environ.get("NAIMA_AMD_LIB"):  # (experiments: a variant of the library bu
 NH_PD_NPAR = 8
 NH_EBL_ONE, NH_EBL_HIGH, NH_EBL_OUTSIDE = 1, 2, 4  # nh_ebl_table's per-energy codes
 NH_PAIR_THERMAL, NH_PAIR_MONO, NH_PAIR_TABLE = 0, 1, 2  # nh_pairabs_rows' field kinds
+NH_SSA_GEOMETRY = {"sphere": 0, "slab": 1}  # nh_ssa_apply's geometries
 # nh_hist_columns' caps (include/naima_hip.h)
 NH_HIST_MAX_COLS, NH_HIST_MAX_PAIRS, NH_HIST_MAX_BINS_1D, NH_HIST_MAX_BINS_2D = 32, 496, 4096, 100
 NH_RANK_POOLED, NH_RANK_CHAIN = 0, 1   # nh_rank_normal_scores' layouts
@@ -178,6 +179,10 @@ _SIGS = {
     "nh_ebl_apply": [_dp, _dp, _i, _i, _dp, _i, _dp, _dp, _i, _dp, _i, _i, _dp, _i],
     "nh_pairabs_rows": [_dp, _i, _d, _dp, _dp, _dp, _dp, _i, _dp, _i, _i, _dp, _i],
     "nh_pairabs_apply": [_dp, _dp, _i, _dp, _i, _dp, _i, _i, _i, _dp, _i],
+    "nh_syn_absorption": [_dp, _dp, _dp, _dp, _i, _i, _dp, _dp, _i, _dp, _i, _dp, _i],
+    "nh_syn_absorption_plan": [_i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
+                               C.POINTER(_i)],
+    "nh_ssa_apply": [_dp, _dp, _ll, _dp, _i, _dp, _i, _dp, _i, _i, _i, _dp, _i],
     "nh_cooled_electrons": [_dp, _dp, _ll, _i, _dp, _i, _dp, _dp, _i, _dp, _dp, _dp, _dp],
     "nh_cooled_ic_rows": [_dp, _dp, _i, _dp, _i, _d, _dp, _i],
     "nh_cooled_weights": [_dp, _dp, _dp, _i, _i, _dp, _dp, _i, _d, _dp, _dp],

@@ -607,6 +607,35 @@ class DPairAbs(DFactor):
         return DMat.from_buffer(self.ctx, out, N, nE)
 
 
+class DSsa(DFactor):
+    """lazy (N, nE) synchrotron self-absorption escape fraction f(tau) of a homogeneous source
+    (or, with ``tau``, the optical depth itself): ``kappa`` is the DeviceArray of
+    nh_syn_absorption -- one shared row, or with ``per_walker`` one row per walker --, ``R_cm``
+    a number or a ``DVec`` and ``geometry`` 'sphere' or 'slab'.  Times a ``DMat`` it is one
+    ``nh_ssa_apply`` launch that also forms the matrix's linear combination."""
+    _what = "self-absorption"
+
+    def __init__(self, ctx, kappa, per_walker, R_cm, geometry, N, nE, tau=False):
+        if geometry not in _lib.NH_SSA_GEOMETRY:
+            raise ValueError("geometry should be one of: %s" % sorted(_lib.NH_SSA_GEOMETRY))
+        self.ctx, self.kappa, self.per_walker, self.R_cm = ctx, kappa, bool(per_walker), R_cm
+        self.geometry, self.tau = geometry, bool(tau)
+        self.shape = (int(N), int(nE))
+
+    def apply(self, m=None):
+        N, nE = self.shape
+        if self.tau and m is not None:
+            raise TypeError("an optical depth is not a factor of a flux: multiply with the "
+                            "transmission")
+        comps, ncomp, cf = self._terms_of(m)
+        lz = as_lazy(self.R_cm)
+        out = self.ctx.empty((N, nE))
+        self.ctx.call("nh_ssa_apply", self.kappa, nE if self.per_walker else 0, C.byref(lz),
+                      _lib.NH_SSA_GEOMETRY[self.geometry], comps, ncomp, cf, int(self.tau), N, nE,
+                      out, nE)
+        return DMat.from_buffer(self.ctx, out, N, nE)
+
+
 class LazyPrior:
     """sum of prior terms on device scalars, evaluated by nh_priors"""
     __array_priority__ = DEVICE_PRIORITY

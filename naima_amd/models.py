@@ -17,7 +17,8 @@ from .constants import AR_CGS, C_CGS, ERG_TO_EV, HBAR_CGS, MEC2_ERG, MEC2_EV, R0
 from .validator import validate_physical_type, validate_scalar_or_batch
 
 __all__ = ["PowerLaw", "ExponentialCutoffPowerLaw", "BrokenPowerLaw",
-           "ExponentialCutoffBrokenPowerLaw", "LogParabola", "CooledElectrons"]
+           "ExponentialCutoffBrokenPowerLaw", "LogParabola", "CooledElectrons",
+           "SynchrotronSelfAbsorption"]
 
 
 def _validate_ene(ene):
@@ -695,6 +696,111 @@ class PairAbsorptionModel:
 
     def transmission(self, e):
         """exp(-tau(E)), the factor to multiply a flux with; shapes as for ``opacity``"""
+        return self._result(e, False)
+
+
+class SynchrotronSelfAbsorption:
+    """Synchrotron self-absorption of the electron population of a ``Synchrotron`` model in a
+    homogeneous source of radius ``radius``: what turns the optically thin spectrum of a compact
+    source (a blazar zone, a radio supernova, a young nebula at radio frequencies) over into
+    nu^(5/2) below the frequency at which it becomes opaque to itself.
+
+    ``absorption_area(e)`` is kappa(E) = alpha(E) V in cm^2, the absorption coefficient times
+    the source's volume, from the same per-electron emissivity, field and particle weights as
+    the emission (nh_syn_absorption: the form integrated by parts, which holds no derivative of
+    the distribution and is right for a truncated one).  ``opacity(e)`` is the optical depth
+    and ``transmission(e)`` the fraction f(tau) of the optically thin flux that escapes:
+
+      'sphere' (default)  tau = 3 kappa / (2 pi R^2) along a diameter,
+                          f = 3 u / tau, u = 1/2 + exp(-tau)/tau - (1 - exp(-tau))/tau^2
+      'slab'              a face-on cylinder of face radius R, of any depth:
+                          tau = kappa / (pi R^2), f = (1 - exp(-tau)) / tau
+
+    ``B`` and the distribution's parameters (the synchrotron model's) and ``radius`` may each
+    be scalars, 1-D host arrays (one value per walker) or device parameters; the results are
+    then an (n_e,) array (the transmission a ``darray.FactorRow``), an (N, n_e) array, or a
+    lazy device factor (``darray.DSsa``) that multiplies a device flux in one launch.  All
+    three come from the same two kernels (nh_syn_absorption / nh_ssa_apply).
+
+    A scalar radius is validated as a positive length.  A walker of a batch whose radius is
+    <= 0, NaN or infinite, or whose field is, gets a NaN row: a prior that excludes it gives
+    -inf, and without one the sampler's ``nan_policy`` applies.  Eemin, Eemax or nEed per walker
+    raise ``NotImplementedError``."""
+
+    def __init__(self, synchrotron, radius, geometry="sphere"):
+        from ._lib import NH_SSA_GEOMETRY
+        from .validator import validate_physical_type, validate_scalar
+        if not (hasattr(synchrotron, "_absorption_rows") and hasattr(synchrotron, "B")):
+            raise TypeError("SynchrotronSelfAbsorption needs a naima_amd Synchrotron model, got %r"
+                            % type(synchrotron).__name__)
+        if geometry not in NH_SSA_GEOMETRY:
+            raise ValueError("geometry should be one of: %s" % sorted(NH_SSA_GEOMETRY))
+        validate_physical_type("radius", radius, "length")
+        if not (radius.on_device or np.ndim(radius.value) > 0):
+            validate_scalar("radius", radius, domain="strictly-positive", physical_type="length")
+        elif not radius.on_device and np.ndim(radius.value) != 1:
+            raise TypeError("a per-walker radius must be a 1-D array, got shape %r"
+                            % (np.shape(radius.value),))
+        self.synchrotron, self.radius, self.geometry = synchrotron, radius, geometry
+
+    @property
+    def on_device(self):
+        return bool(self.synchrotron.on_device) or wv.on_device([self.radius])
+
+    @property
+    def batch_size(self):
+        """walkers of the batch (None: scalars everywhere)"""
+        syn = self.synchrotron
+        form, n = wv.classify(self.radius)
+        mine = n if form is wv.DEVICE or (form is wv.HOST and n > 1) else None
+        return wv.merge([syn.batch_size if syn.is_batched else None, mine],
+                        "SynchrotronSelfAbsorption", broadcast_one=False)
+
+    def _energies(self, e):
+        return np.atleast_1d(_validate_ene(e).to("eV").value).astype(float).ravel()
+
+    def _factor(self, e, tau, rows=None):
+        """(the DSsa at energies e, the batch size or None); ``rows``: that many equal rows of
+        a model whose values are all scalars"""
+        from .darray import DSsa
+        E_eV = self._energies(e)
+        N = self.batch_size
+        ctx, Ns, kappa = self.synchrotron._absorption_rows(E_eV)
+        N1 = (rows or 1) if N is None else N
+        R = wv.resolve(ctx, self.radius, "cm", fold=True)
+        return DSsa(ctx, kappa, Ns == N1, R, self.geometry, N1, E_eV.size, tau=tau), N
+
+    def _result(self, e, tau):
+        f, N = self._factor(e, tau)
+        if self.on_device:
+            return f
+        if N is not None:
+            return f.get()
+        row = f.get()[0]
+        if tau:
+            return row
+        from .darray import FactorRow
+        return FactorRow(row, lambda n: self._factor(e, False, rows=n)[0])
+
+    def absorption_area(self, e):
+        """kappa(E) = alpha(E) V in cm^2: (n_e,) for scalars, (N, n_e) for a batched population
+        (on the device a lazy matrix)"""
+        from .darray import DMat
+        E_eV = self._energies(e)
+        ctx, Ns, kappa = self.synchrotron._absorption_rows(E_eV)
+        if self.synchrotron.on_device:
+            return u.Quantity(DMat.from_buffer(ctx, kappa, Ns, E_eV.size), u.cm ** 2)
+        k = kappa.get()
+        return u.Quantity(k if self.synchrotron.is_batched else k[0], u.cm ** 2)
+
+    def opacity(self, e):
+        """tau(E): (n_e,) for scalars, (N, n_e) for a host batch, a lazy device factor for
+        device values"""
+        return self._result(e, True)
+
+    def transmission(self, e):
+        """f(tau(E)), the factor to multiply the optically thin flux with; shapes as for
+        ``opacity``"""
         return self._result(e, False)
 
 

@@ -565,6 +565,11 @@ class Synchrotron(BaseElectron):
     Parameters as in naima: ``particle_distribution``, ``B`` (default 3.24e-6 G),
     and the keyword overrides ``Eemin`` (1 GeV), ``Eemax`` (1e9 mec2), ``nEed`` (100).
     ``B`` may be a 1-D array over walkers.
+
+    ``flux`` and ``sed`` take ``radius`` (and ``geometry``, 'sphere' or 'slab'): the spectrum
+    is then absorbed by the population itself in a homogeneous source of that radius
+    (``self_absorption``, ``models.SynchrotronSelfAbsorption``).  Without a radius the source is
+    optically thin at every frequency.
     """
 
     _walker_scalars = ("B",)
@@ -610,21 +615,87 @@ class Synchrotron(BaseElectron):
             ctx, N, out = self._general_launch(0, E_eV, B=self.B)
             return self._result(ctx, out, N, E_eV.size, E)
         ctx, N, w, lw, gd, lx, gam = self._electron_weights()
-        Bv = self.B.to("G").value
-        ldB = 1
-        if isinstance(Bv, DVec) and self._B_in_rows(Bv):
-            Bd = self.particle_distribution.device_rows(ctx, N, amplitude_to=_PER_EV)
-            Bp, ldB = Bd.ptr + 8 * 7, 8
-        elif isinstance(Bv, DVec):
-            Bd = self.__dict__.get("_B_dense") or Bv.dense()
-            Bp = Bd.ptr
-        else:
-            Bd = ctx.array(np.broadcast_to(np.asarray(Bv, dtype=float), (N,)))
-            Bp = Bd.ptr
+        Bd, Bp, ldB = self._B_arg(ctx, N)
         out = ctx.emit_synchrotron(w, lw, Bp, ldB, N, gd, lx, gam.size, ctx.const(E_eV),
                                    E_eV.size, keep=(Bd,), E_host=E_eV)
         del Bd
         return self._result(ctx, out, N, E_eV.size, E)
+
+    def _B_arg(self, ctx, N):
+        """(the buffer to keep alive, the address, the stride) of the N walkers' fields in gauss:
+        slot 7 of the packed rows when B rides there (ldB = 8), else a plain vector"""
+        Bv = self.B.to("G").value
+        if isinstance(Bv, DVec) and self._B_in_rows(Bv):
+            Bd = self.particle_distribution.device_rows(ctx, N, amplitude_to=_PER_EV)
+            return Bd, Bd.ptr + 8 * 7, 8
+        if isinstance(Bv, DVec):
+            Bd = self.__dict__.get("_B_dense") or Bv.dense()
+            return Bd, Bd.ptr, 1
+        Bd = ctx.array(np.broadcast_to(np.asarray(Bv, dtype=float), (N,)))
+        return Bd, Bd.ptr, 1
+
+    # -- self-absorption ----------------------------------------------------------------------
+    def _absorption_supported(self):
+        if self._general_limits():
+            raise NotImplementedError(
+                "synchrotron self-absorption needs Eemin, Eemax and nEed that are the same for "
+                "every walker (the per-walker particle grids of nh_general_electron have no "
+                "absorption kernel); evaluate such walkers in separate calls")
+
+    def _absorption_rows(self, E_eV):
+        """(ctx, N, kappa [N][nE] in cm^2) of nh_syn_absorption: one launch through ctx.call, on
+        the weights and the field the emission uses"""
+        self._absorption_supported()
+        ctx, N, w, lw, gd, lx, gam = self._electron_weights()
+        Bd, Bp, ldB = self._B_arg(ctx, N)
+        nE = E_eV.size
+        out = ctx.empty((N, nE))
+        ctx.call("nh_syn_absorption", w, lw, Bp, ldB, N, gd, lx, gam.size, ctx.const(E_eV), nE,
+                 out, nE)
+        del Bd
+        return ctx, N, out
+
+    def self_absorption(self, radius, geometry="sphere"):
+        """the ``models.SynchrotronSelfAbsorption`` of this population in a homogeneous source
+        of radius ``radius``"""
+        from .models import SynchrotronSelfAbsorption
+        return SynchrotronSelfAbsorption(self, radius, geometry=geometry)
+
+    def _absorbed(self, spec, photon_energy, radius, geometry):
+        E = _validate_ene(photon_energy)
+        ssa = self.self_absorption(radius, geometry)
+        T = ssa.transmission(E)
+        if wv.on_device([T]) and not spec.on_device:
+            # (a device radius on a host population: the flux joins it in HBM)
+            ctx = get_context()
+            N, nE = T.shape
+            v = np.asarray(spec.value, dtype=float)
+            v = v[..., None] if E.isscalar else v
+            buf = ctx.array(np.ascontiguousarray(np.broadcast_to(v, (N, nE))))
+            spec = u.Quantity(DMat.from_buffer(ctx, buf, N, nE), spec.unit)
+        elif E.isscalar and not wv.on_device([T]):
+            T = np.asarray(T)[..., 0]
+        return spec * T
+
+    def flux(self, photon_energy, distance=1 * u.kpc, radius=None, geometry="sphere"):
+        """``BaseRadiative.flux``; with ``radius`` the spectrum that escapes a homogeneous source
+        of that radius: the optically thin flux times
+        ``self_absorption(radius, geometry).transmission(photon_energy)``"""
+        if radius is None:
+            return super().flux(photon_energy, distance)
+        self.self_absorption(radius, geometry)  # (the radius' and the geometry's errors first)
+        self._absorption_supported()
+        spec = super().flux(photon_energy, distance)
+        return self._absorbed(spec, photon_energy, radius, geometry)
+
+    def sed(self, photon_energy, distance=1 * u.kpc, radius=None, geometry="sphere"):
+        """``BaseRadiative.sed``; ``radius`` and ``geometry`` as in ``flux``"""
+        if radius is None:
+            return super().sed(photon_energy, distance)
+        out_unit = "erg/s" if _dist_is_zero(distance) else "erg/(cm2 s)"
+        photon_energy = _validate_ene(photon_energy)
+        return (self.flux(photon_energy, distance, radius, geometry)
+                * photon_energy ** 2.0).to(out_unit)
 
 
 class InverseCompton(BaseElectron):
